@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — fwd+bwd views/s of the 3DGS hot path on synthetic Gaussians (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S3] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -45,6 +45,48 @@ def _grad_errors(got, ref):
 
 
 GRAD_NAMES = ("means3D", "means2D", "opacities", "shs", "scales", "rotations")
+
+
+PARAM_NAMES = ("xyz", "features_dc", "features_rest", "scaling", "rotation", "opacity")   # the order of `params` in main()
+DUMP_BYTES = 60 << 20      # --dump-outputs: at most this much in all, each array's share equal
+DUMP_ARRAY_ELEMS = 1 << 20  # ... and at most this many elements per array
+
+
+def caller_outputs(out, loss, params):
+    """What a caller of the timed step receives: the tensors of the render dict, the screen-space gradient, the loss and
+    the gradient of every parameter leaf (held by reference, no device work)."""
+    arrs = {k: v for k, v in out.items() if torch.is_tensor(v) and k != "viewspace_points"}
+    vsp = out.get("viewspace_points")
+    if vsp is not None and getattr(vsp, "grad", None) is not None:
+        arrs["viewspace_points_grad"] = vsp.grad
+    arrs["loss"] = loss
+    for name, p in zip(PARAM_NAMES, params):
+        if p.grad is not None:
+            arrs["grad_" + name] = p.grad
+    return arrs
+
+
+def dump_outputs(path, arrays):
+    """Writes `arrays` as path/<name>.npy: float32 arrays as float32, everything else as float64 (exact for the integer and
+    boolean outputs).  An array with more elements than its share of DUMP_BYTES (or than DUMP_ARRAY_ELEMS) is stored as a
+    fixed sample of its flattened elements: sorted indices drawn by a generator seeded with the array's element count, so
+    the same arguments give the same sample in every run and every build.  Returns the bytes written."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        dtype = np.float32 if t.dtype == torch.float32 else np.float64
+        cap = min(DUMP_ARRAY_ELEMS, share // np.dtype(dtype).itemsize)
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(flat.numel()).choice(flat.numel(), cap, replace=False))
+            t = flat[torch.from_numpy(idx).to(flat.device)]
+        a = t.cpu().numpy().astype(dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+    return total
 
 
 class Pipe:
@@ -502,6 +544,11 @@ def main():
     ap.add_argument("--split-backward", action="store_true",
                     help="headline = the library's default backward (two-term fp16 split of the pixel->splat reduction, 22 mantissa bits) "
                          "instead of the all-fp32 one")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller (render maps, loss, "
+                         "gradients of every parameter) as DIR/<name>.npy, float32 / float64, at most 64 MB (large arrays as a "
+                         "fixed, seeded sample of their elements); rank 0's view.  Same arguments, same inputs: the render "
+                         "maps and the loss repeat bit for bit, the gradients up to the order of the backward's float atomics")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -606,16 +653,23 @@ def main():
     if headline_exact or args.exact_backward:
         R._tls.backward_flags = _C.BACKWARD_EXACT_FP32     # every forward (and one-call view) from here on asks for the all-fp32 backward
 
-    def step(i):
+    def step(i, keep=None):
+        """One view; `keep` (a dict): filled with what the caller of the step receives (caller_outputs)."""
         cam, gt = my_cams[i % len(my_cams)], gts[i % len(my_cams)]
         if side_streams is not None:
             with torch.cuda.stream(side_streams[i % args.streams]):
-                loss = train_view(cam, model, pipe, bg, gt, 0.2)["loss"]
+                out = train_view(cam, model, pipe, bg, gt, 0.2)
+                loss = out["loss"]
+                if keep is not None:
+                    keep.update(caller_outputs(out, loss, params))
                 for p in params:
                     p.grad = None
             return loss
         if fused_view:      # render + loss + backward enqueued by one library call (scorp_gs3d_train_view): same kernels
-            loss = train_view(cam, model, pipe, bg, gt, 0.2)["loss"]
+            out = train_view(cam, model, pipe, bg, gt, 0.2)
+            loss = out["loss"]
+            if keep is not None:
+                keep.update(caller_outputs(out, loss, params))
             for p in params:
                 p.grad = None
             return loss
@@ -625,6 +679,8 @@ def main():
             nl, dl = surfel_regularizers(out, 0.05, 100.0)
             loss = loss + nl + dl
         loss.backward()
+        if keep is not None:
+            keep.update(caller_outputs(out, loss, params))
         for p in params:
             p.grad = None
         return loss
@@ -664,7 +720,7 @@ def main():
         reconcile["bracketing_cost_us_per_view"] = round(reconcile["bracketed_view_us"] - reconcile["plain_view_us"], 1)
         reconcile["bracketing_cost_us_per_bracket"] = round(reconcile["bracketing_cost_us_per_view"] / max(reconcile["brackets_per_view"], 1), 2)
 
-    def timed_run(n_warm, n_steps, bracket=None, lead_in=args.lead_in):
+    def timed_run(n_warm, n_steps, bracket=None, lead_in=args.lead_in, keep=None):
         """n_warm untimed views, then EXACTLY n_steps views between two hipEvents recorded on the launch stream directly
         behind the warm-up: no host synchronisation opens the timed region (a synchronise leaves the chip idle for a
         moment and the first ~20 views after it run 5-20 % slow, scripts/dev/ramp.py - at the driver's --steps 20 that
@@ -673,7 +729,8 @@ def main():
         would otherwise sit on the ramp (measured at --steps 20 --warmup 5 on one box: 1 315-1 320 views/s with 12 lead-in
         views, 1 352-1 355 with 40, 1 355-1 356 with 100; the default 200-step run gives the same with any of them: 40 it is,
         30 ms per timed run).  barrier + synchronize bracket the whole; the host clock over the region (enqueue
-        start -> synchronize) is kept as a cross-check.  Returns (event s, host s, host enqueue s, last loss)."""
+        start -> synchronize) is kept as a cross-check.  `keep`: filled by the last timed view with what it returned to its
+        caller (references only: no device work in the region).  Returns (event s, host s, host enqueue s, last loss)."""
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -688,7 +745,7 @@ def main():
         h0 = time.perf_counter()
         loss_ = None
         for i in range(n_steps):
-            loss_ = step(n_warm + i)
+            loss_ = step(n_warm + i, keep if i == n_steps - 1 else None)
         h_enq = time.perf_counter() - h0
         ev1.record()
         PairPolicy.drain()
@@ -702,9 +759,14 @@ def main():
     if dominant:
         names_ = [_C.lib().scorp_prof_kernel_name(k).decode() for k in range(_C.lib().scorp_prof_num_kernels())]
         dom_mask = 1 << names_.index(dominant)
-    dt, dt_host, t_host, loss = timed_run(args.warmup, args.steps, dom_mask)
+    last_outputs = {} if args.dump_outputs and rank == 0 else None
+    dt, dt_host, t_host, loss = timed_run(args.warmup, args.steps, dom_mask, keep=last_outputs)
     kern = {} if args.no_kernel_events else _C.prof_collect()
     _C.prof_enable(False)
+    if last_outputs:
+        nbytes = dump_outputs(args.dump_outputs, last_outputs)
+        print(f"[bench] --dump-outputs: {len(last_outputs)} arrays, {nbytes} bytes -> {args.dump_outputs}", file=sys.stderr)
+    last_outputs = None
     # the same step with the OTHER form of the blend backward's pixel->splat reduction (the two-term fp16 split if the headline
     # is all-fp32, and the other way round), same protocol: the headline next to its twin
     dt_twin = dt_det = None
