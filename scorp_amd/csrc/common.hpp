@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "scorp_gs.h"
 
 namespace scorp {
@@ -135,6 +137,13 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// fp16 pairs of the blend backwards' split form (gs3d_backward.hip, gs2d.hip)
+__device__ __forceinline__ uint32_t pack_rtz16(float lo, float hi) {   // (fp16 rtz(lo)) | (fp16 rtz(hi)) << 16
+  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lo, hi));
+}
+__device__ __forceinline__ float half_lo(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p & 0xFFFFu)); }
+__device__ __forceinline__ float half_hi(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p >> 16)); }
+
 // Tile mask convention: bit (ty - y0) * 8 + (tx - x0) for rectangles of at most 8 x 8 tiles; ~0 = whole rectangle.
 constexpr uint64_t kMaskAll = ~0ull;
 template <typename F>
@@ -161,6 +170,24 @@ __device__ __forceinline__ void for_each_tile(int x0, int y0, int x1, int y1, ui
       mask &= mask - 1;
       f((y0 + (b >> 3)) * tiles_x + x0 + (b & 7));
     }
+  }
+}
+
+// Host side: calls f(std::integral_constant<int, D>{}, std::bool_constant<S>{}) with D = the SH degree (3 for anything
+// above 2) and S = split SH layout, so that f can launch kernel<D, S>.  The calls are written split first, degrees 0..3,
+// then not split: the order in which the per-Gaussian kernels are instantiated (and emitted).
+template <typename F>
+inline void dispatch_sh_degree(int deg, bool split, F f) {
+  using D0 = std::integral_constant<int, 0>;
+  using D1 = std::integral_constant<int, 1>;
+  using D2 = std::integral_constant<int, 2>;
+  using D3 = std::integral_constant<int, 3>;
+  if (split) {
+    switch (deg) { case 0: f(D0{}, std::true_type{}); break; case 1: f(D1{}, std::true_type{}); break;
+                   case 2: f(D2{}, std::true_type{}); break; default: f(D3{}, std::true_type{}); }
+  } else {
+    switch (deg) { case 0: f(D0{}, std::false_type{}); break; case 1: f(D1{}, std::false_type{}); break;
+                   case 2: f(D2{}, std::false_type{}); break; default: f(D3{}, std::false_type{}); }
   }
 }
 #endif
@@ -392,41 +419,18 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
 // The optimizer's streams are NONTEMPORAL: the two moments are touched once per iteration and by nobody else, the parameters'
 // next reader (the next view's preprocess) comes ~1 ms and > 2 GB of traffic later.  Same box, S3 training iteration:
 // 985 - 988 it/s with plain loads and stores, 1 070 with nontemporal ones on the SH streams alone (profiles/r06_fused_adam_step.txt).
-#ifndef SCORP_ADAM_NT
-#define SCORP_ADAM_NT 1   // nontemporal loads / stores on the optimizer's streams (0: plain, for A/B builds)
-#endif
 __device__ __forceinline__ float4 adam_ld4(const float4 *p) {
-#if SCORP_ADAM_NT
   typedef float f4 __attribute__((ext_vector_type(4)));
   const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(p));
   return make_float4(t.x, t.y, t.z, t.w);
-#else
-  return *p;
-#endif
 }
 __device__ __forceinline__ void adam_st4(float4 *p, const float4 x) {
-#if SCORP_ADAM_NT
   typedef float f4 __attribute__((ext_vector_type(4)));
   f4 t; t.x = x.x; t.y = x.y; t.z = x.z; t.w = x.w;
   __builtin_nontemporal_store(t, reinterpret_cast<f4 *>(p));
-#else
-  *p = x;
-#endif
 }
-__device__ __forceinline__ float adam_ld1(const float *p) {
-#if SCORP_ADAM_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void adam_st1(float *p, float x) {
-#if SCORP_ADAM_NT
-  __builtin_nontemporal_store(x, p);
-#else
-  *p = x;
-#endif
-}
+__device__ __forceinline__ float adam_ld1(const float *p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void adam_st1(float *p, float x) { __builtin_nontemporal_store(x, p); }
 #endif
 
 // ---- binning shared by the 3DGS and 2DGS paths (gs3d_forward.hip) ----

@@ -90,7 +90,7 @@ __device__ __forceinline__ void preprocess2d_body(const Pg2Args &a, float *s_sh,
   if constexpr (LIN) {
     RawParams r;
     raw_issue_params<2>(r, a.means3D + 3 * (size_t)i, a.rotations + 4 * (size_t)i, a.scales + 2 * (size_t)i, a.opacities + i);
-    stage_sh_linear_async<SCORP_NT_SH ? 2 : 0>(s_sh, a.shs, a.shs_rest, i0);   // (nontemporal: see preprocess_body, gs3d_pergaussian.hip)
+    stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);   // (nontemporal: see preprocess_body, gs3d_pergaussian.hip)
     raw_take_params(r, pre);
   }
   float vm[16], pm[16];
@@ -324,14 +324,6 @@ __device__ __forceinline__ bool eval_surfel(const float4 e0, const float4 e1, co
   const float p0 = __builtin_fmaf(e0.x, qx, __builtin_fmaf(e0.w, qy, e1.z));
   const float p1 = __builtin_fmaf(e0.y, qx, __builtin_fmaf(e1.x, qy, e1.w));
   h.pz = __builtin_fmaf(e0.z, qx, __builtin_fmaf(e1.y, qy, e2.x));
-#ifdef SCORP_2D_PROBE_P
-  {   // measurement build only: the six multiply-adds of p a second time (what taking them off the vector pipe could save)
-    const float x0 = __builtin_fmaf(e0.y, qx, __builtin_fmaf(e0.z, qy, e1.w));
-    const float x1 = __builtin_fmaf(e0.w, qx, __builtin_fmaf(e1.y, qy, e2.x));
-    const float x2 = __builtin_fmaf(e0.x, qx, __builtin_fmaf(e1.x, qy, e1.z));
-    asm volatile("" ::"v"(x0), "v"(x1), "v"(x2));
-  }
-#endif
   h.rz = __builtin_amdgcn_rcpf(h.pz);
   h.s0 = p0 * h.rz; h.s1 = p1 * h.rz;
   const float rho3d = __builtin_fmaf(h.s0, h.s0, h.s1 * h.s1);
@@ -558,8 +550,6 @@ constexpr int k2TargetExp = SCORP_2D_TARGET_EXP;   // the block's largest |upstr
                                              // scale alone, [1, 2) with a factor of nine of head room for a depth-loss-dominated block at the
                                              // far plane - tests/test_gs2d_gpu.py "far_depth" - and an absolute floor of 2^-24 under them)
 constexpr float k2WScale = 1024.0f;
-__device__ __forceinline__ uint32_t pack_rtz16_2d(float lo, float hi) { return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lo, hi)); }
-__device__ __forceinline__ float half_lo_2d(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p & 0xFFFFu)); }
 // x -> (h1(x) | h2(x) << 16), h1 = rtz16(x), h2 = rtz16(x - h1).  h1 as an fp32 value is x with the low thirteen mantissa
 // bits cleared (fp16 carries ten), so the remainder needs no conversion back and ONE v_cvt_pkrtz makes the whole dword:
 // three instructions per value (it was nine per two: two packs, two conversions back, two fma, two v_perm).  Below the
@@ -569,7 +559,7 @@ __device__ __forceinline__ float half_lo_2d(uint32_t p) { return (float)__builti
 // remainder is rounded to nearest where it was truncated (either way x = h1 + h2 to 2^-22 relative); a value beyond the fp16
 // range (not reachable: the hit's largest is held below 1.4e4, see `sg`) now ends as inf instead of a silently wrong pair.
 __device__ __forceinline__ uint32_t split_one(float x) {
-  uint32_t d = pack_rtz16_2d(x, 0.0f);
+  uint32_t d = pack_rtz16(x, 0.0f);
   asm("v_fma_mixhi_f16 %0, %0, -1.0, %1 op_sel_hi:[1,0,0]" : "+v"(d) : "v"(x));
   return d;
 }
@@ -594,9 +584,6 @@ __device__ __forceinline__ ReadOut read_out_of(int o) {
 
 #ifndef SCORP_2D_BCHUNK
 #define SCORP_2D_BCHUNK 32
-#endif
-#ifndef SCORP_2D_MFMA_CHAINS
-#define SCORP_2D_MFMA_CHAINS 1
 #endif
 constexpr int k2BChunk = SCORP_2D_BCHUNK;   // hits staged per chunk: 32 (the staging arrays are 112 bytes per hit; with 64 the wave's 11.5 KB of
                                             // LDS held the kernel at 13 waves per CU where its 124 registers allow 16: 706 -> 665 us)
@@ -716,10 +703,10 @@ blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint
         } else {
           if (bn >= 3 && bn <= 14) {
             const float g = xs[q * 6 + (bn - 3) % 6];
-            const float g1 = half_lo_2d(pack_rtz16_2d(g, 0.0f));
+            const float g1 = half_lo(pack_rtz16(g, 0.0f));
             b = bn <= 8 ? g1 : g - g1;                       // columns 3..8: first fp16 term, 9..14: the remainder
           }
-          const uint32_t hb = pack_rtz16_2d(b, 0.0f) & 0xFFFFu;
+          const uint32_t hb = pack_rtz16(b, 0.0f) & 0xFFFFu;
           bh[m].d[j] = hb | (hb << 16);
         }
       }
@@ -746,12 +733,9 @@ blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint
       // MFMAs 4 m .. 4 m + 3 cover the pixels 16 m .. 16 m + 15 (two rows of the block).  A surfel's footprint is a few pixels
       // across: where neither hit of the pair is live on those two rows every A value is an exact zero and the four fp32
       // MFMAs (34 cycles each at the vector rate) are skipped - a wave-uniform branch on the pair's live-pixel mask.
-#ifndef SCORP_2D_EXACT_NOSKIP
-#define SCORP_2D_EXACT_NOSKIP 0
-#endif
 #pragma unroll
       for (int m = 0; m < 4; m++) {
-        if (SCORP_2D_EXACT_NOSKIP || ((pend_live >> (16 * m)) & 0xFFFFull) != 0) {
+        if (((pend_live >> (16 * m)) & 0xFFFFull) != 0) {
           d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m].x, bb[4 * m], d, 0, 0, 0);
           d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m].y, bb[4 * m + 1], d, 0, 0, 0);
           d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m].z, bb[4 * m + 2], d, 0, 0, 0);
@@ -762,17 +746,8 @@ blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint
       Frag2 af[4];
 #pragma unroll
       for (int m = 0; m < 4; m++) af[m].q = *reinterpret_cast<const uint4 *>(&xm2[abase + 16 * m]);
-#if SCORP_2D_MFMA_CHAINS == 2   // two independent accumulation chains of two MFMAs each (latency) + four adds
-      f32x4_2d d1 = {0.0f, 0.0f, 0.0f, 0.0f};
-      d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0].v, bh[0].v, d, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1].v, bh[1].v, d1, 0, 0, 0);
-      d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[2].v, bh[2].v, d, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[3].v, bh[3].v, d1, 0, 0, 0);
-      d += d1;
-#else
 #pragma unroll
       for (int m = 0; m < 4; m++) d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m].v, bh[m].v, d, 0, 0, 0);
-#endif
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();   // every lane has its A operands: the result tile may overwrite the matrix
@@ -1002,7 +977,7 @@ __device__ __forceinline__ void preprocess2d_backward_body(const Pg2Args &a, flo
     pre[0] = a.means3D[3 * (size_t)i]; pre[1] = a.means3D[3 * (size_t)i + 1]; pre[2] = a.means3D[3 * (size_t)i + 2];
     pre[10] = a.opacities[i];
     // (nontemporal unless the optimizer step in the epilogue reads the rows again: see preprocess_backward_body, gs3d_pergaussian.hip)
-    if (SCORP_NT_SH && !(SPLIT && ad.on != 0)) stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);
+    if (!(SPLIT && ad.on != 0)) stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);
     else stage_sh_linear_async<0>(s_sh, a.shs, a.shs_rest, i0);
     pre[3] = q_in.x; pre[4] = q_in.y; pre[5] = q_in.z; pre[6] = q_in.w; pre[7] = s_in0; pre[8] = s_in1;
     acc_lo[0] = a0.x; acc_lo[1] = a0.y; acc_lo[2] = a0.z; acc_lo[3] = a0.w; acc_lo[4] = a1.x; acc_lo[5] = a1.y; acc_lo[6] = a1.z;
@@ -1333,10 +1308,9 @@ extern "C" int scorp_gs2d_preprocess(const ScorpGs3dInputs *in, int32_t *out_rad
     const int deg = in->shs ? in->sh_degree : 0;
     Surfel *rec = (Surfel *)(base + L.rec);
     BinRec *bin = (BinRec *)(base + L.bin);
-#define SCORP_L2(D, S) preprocess2d_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, (uint64_t *)(base + L.tile_mask), out_radii, tile_count)
-    if (in->shs_rest) { switch (deg) { case 0: SCORP_L2(0, true); break; case 1: SCORP_L2(1, true); break; case 2: SCORP_L2(2, true); break; default: SCORP_L2(3, true); } }
-    else { switch (deg) { case 0: SCORP_L2(0, false); break; case 1: SCORP_L2(1, false); break; case 2: SCORP_L2(2, false); break; default: SCORP_L2(3, false); } }
-#undef SCORP_L2
+    dispatch_sh_degree(deg, in->shs_rest != nullptr, [&](auto D, auto S) {
+      preprocess2d_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, (uint64_t *)(base + L.tile_mask), out_radii, tile_count);
+    });
     SCORP_KERNEL_CHECK("preprocess_2d", in->debug, stream);
   }
   return bin_count_and_scan(L, base, N, in->debug, stream);
@@ -1453,10 +1427,9 @@ int scorp::backward2d_impl(const ScorpGs3dInputs *in, const void *state, const v
     AdamEpi ad;
     memset(&ad, 0, sizeof(ad));
     if (adam && in->shs_rest) ad = *adam;   // (the fused step is defined for the training layout: dc / rest split leaves)
-#define SCORP_B2(D, S) preprocess2d_backward_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, acc, g, ad)
-    if (in->shs_rest) { switch (deg) { case 0: SCORP_B2(0, true); break; case 1: SCORP_B2(1, true); break; case 2: SCORP_B2(2, true); break; default: SCORP_B2(3, true); } }
-    else { switch (deg) { case 0: SCORP_B2(0, false); break; case 1: SCORP_B2(1, false); break; case 2: SCORP_B2(2, false); break; default: SCORP_B2(3, false); } }
-#undef SCORP_B2
+    dispatch_sh_degree(deg, in->shs_rest != nullptr, [&](auto D, auto S) {
+      preprocess2d_backward_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, acc, g, ad);
+    });
   }
   SCORP_KERNEL_CHECK("preprocess_backward_2d", in->debug, stream);
   return SCORP_OK;

@@ -50,17 +50,8 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// Timing probes only (scripts/dev/lds_conflicts.py; profiles/r06_3d_backward_bank_conflicts.txt): SCORP_BWD_XSTRIDE=72 with
-// SCORP_BWD_KOFF=4 is the conflict-free A-operand read of the 2-D kernel (its K mapping does not match this kernel's B operand:
-// WRONG gradients, same instructions and LDS traffic), SCORP_BWD_LDS_PAD pads the other arm to the same LDS footprint.
 #ifndef SCORP_BWD_XSTRIDE
 #define SCORP_BWD_XSTRIDE 68
-#endif
-#ifndef SCORP_BWD_KOFF
-#define SCORP_BWD_KOFF 16
-#endif
-#ifndef SCORP_BWD_LDS_PAD
-#define SCORP_BWD_LDS_PAD 0
 #endif
 constexpr int kXStride = SCORP_BWD_XSTRIDE;  // dwords per slot row of the wave-private matrices: rows stay 16-byte
                                              // aligned for the A-operand's ds_read_b128; row writes are conflict-free
@@ -74,12 +65,6 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kVTargetExp = 7;               // split form: the block's largest |dL/dpixel| is scaled into [2^7, 2^8)
 constexpr int kVTargetExpDA = 4;             // ... [2^4, 2^5) when depth / alpha gradients (depth values!) take part
 constexpr float kWScale = 1024.0f;           // split form: blend weights (<= 1) are carried as w * 2^10
-
-__device__ __forceinline__ uint32_t pack_rtz16(float lo, float hi) {   // (fp16 rtz(lo)) | (fp16 rtz(hi)) << 16
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lo, hi));
-}
-__device__ __forceinline__ float half_lo(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p & 0xFFFFu)); }
-__device__ __forceinline__ float half_hi(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p >> 16)); }
 
 // ---------------------------------------------------------------------------------------------------------
 // B1w: the replay with ONE WAVE PER 8x8 PIXEL BLOCK as the unit of work (64-thread workgroups, no workgroup
@@ -147,13 +132,9 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   float *dbuf = reinterpret_cast<float *>(xm);   // the 2 x 16 x 14 result tile reuses the matrix once the MFMAs have consumed it
   float *xs = reinterpret_cast<float *>(xm);     // prologue scratch: 64 x 4 floats
   static_assert(2 * kGroup * kDStride <= 13 * kXStride && 64 * 4 <= 13 * kXStride, "scratch fits below the zero fragments");
-  static_assert(kXStride != 68 || SCORP_BWD_LDS_PAD != 0 ||
+  static_assert(kXStride != 68 ||
                 sizeof(uint4) * 3 * kChunk + sizeof(float4) * 2 * kChunk + sizeof(float2) * kChunk + 4 * kChunk + 4 * 16 * kXStride == 10240,
                 "10 KiB of LDS per wave: four waves per SIMD fill the CU's 160 KiB exactly");
-#if SCORP_BWD_LDS_PAD
-  __shared__ uint32_t lds_pad[SCORP_BWD_LDS_PAD];
-  if (W < 0) lds_pad[threadIdx.x] = 1u;   // (never taken: keeps the padding allocated)
-#endif
   const int lane = threadIdx.x;
   const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
   const int tile = (kk >> 2) * 8 + xcd, quad = kk & 3;
@@ -255,8 +236,8 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
     dpix0 *= sq; dpix1 *= sq; dpix2 *= sq; ddep *= sq; dalp *= sq;
   }
   float T = kExact ? T_final : kWScale * T_final, R = 0.0f, s_last = 0.0f, last_alpha = 0.0f;
-  const int abase = (lane & 15) * kXStride + SCORP_BWD_KOFF * (lane >> 4);
-  constexpr int kAStep = SCORP_BWD_KOFF == 16 ? 4 : 16;   // dwords between the lane's four 16-byte reads
+  const int abase = (lane & 15) * kXStride + 16 * (lane >> 4);
+  constexpr int kAStep = 4;   // dwords between the lane's four 16-byte reads
   float park_v[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // a group's sums, parked until flush_sums
   uint32_t park_o[4] = {det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u};
                                                 // ... and their float offsets in acc (N * 16 < 2^32, checked at the entry
@@ -272,11 +253,7 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-#ifdef SCORP_BWD_NOATOMIC
-      if (park_v[k] != 0.0f && capacity == 0xFFFFFFFFu) atomicAdd(acc + park_o[k], park_v[k]);
-#else
       if (park_v[k] != 0.0f) atomicAdd(acc + park_o[k], park_v[k]);
-#endif
       park_v[k] = 0.0f;
     }
   };
@@ -365,9 +342,6 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
           float4 av[4];
 #pragma unroll
           for (int t4 = 0; t4 < 4; t4++) av[t4] = *reinterpret_cast<const float4 *>(&xm[abase + kAStep * t4]);
-#ifdef SCORP_BWD_PROBE_HALF_MFMA
-          if (h == 0)     // diagnostic build (wrong gradients): what halving the fp32 matrix work would buy
-#endif
 #pragma unroll
           for (int t4 = 0; t4 < 4; t4++) {
             d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t4].x, bb[4 * t4], d, 0, 0, 0);
@@ -397,11 +371,7 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-#ifdef SCORP_BWD_NOTAIL
-    if (false) {
-#else
     if (lane < nslots) {  // block-frame moments -> the ten screen-space gradients of slot `lane`
-#endif
       float *m = dbuf + lane * kDStride;
       const float *m2 = m + kGroup * kDStride;
       const float4 a = gt0[lane];     // x - cx, y - cy, A, B
@@ -436,14 +406,9 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
         const float svdx2 = xl * xl * m0 - 2.0f * xl * mx + mxx;
         const float svdxdy = xl * yl * m0 - xl * my - yl * mx + mxy;
         const float svdy2 = yl * yl * m0 - 2.0f * yl * my + myy;
-#ifdef SCORP_BWD_RAWMOM
-        *reinterpret_cast<float4 *>(m) = make_float4(svdx, svdy, -0.5f * svdx2, -svdxdy);
-        *reinterpret_cast<float4 *>(m + 4) = make_float4(-0.5f * svdy2, m0, mm[6], mm[7]);
-#else
         *reinterpret_cast<float4 *>(m) = make_float4(0.5f * W * (-cA * svdx - cB * svdy), 0.5f * H * (-cC * svdy - cB * svdx),
                                                      -0.5f * svdx2, -svdxdy);
         *reinterpret_cast<float4 *>(m + 4) = make_float4(-0.5f * svdy2, m0 / opac, mm[6], mm[7]);
-#endif
         *reinterpret_cast<float2 *>(m + 8) = make_float2(mm[8], mm[9]);
       }
     }

@@ -14,9 +14,6 @@
 
 #include "common.hpp"
 #include "exp_mfma.hpp"
-#if defined(SCORP_FWD_MERGE) && SCORP_FWD_MERGE
-#include "blend_group_asm.hpp"   // generated: python scripts/dev/gen_blend_group_asm.py (a parked experiment, off by default)
-#endif
 
 namespace scorp {
 namespace {
@@ -765,18 +762,8 @@ sort_tiles_long_kernel(const uint32_t *__restrict__ tile_start, uint64_t *__rest
 // two threshold selects, the T update and four accumulations - the seven VALU instructions of the Horner form (35 % of the
 // old loop's issue time together with its LDS reads of the conic) are gone.  A hit's 1-based position in the block's hit
 // list is arithmetic (hits are blended in ring order): no position array.
-#ifndef SCORP_FWD_DB
-#define SCORP_FWD_DB 0
-#endif
-#ifndef SCORP_FWD_FMA
-#define SCORP_FWD_FMA 1
-#endif
 #ifndef SCORP_FWD_RING
 #define SCORP_FWD_RING 80
-#endif
-#ifndef SCORP_FWD_MERGE
-#define SCORP_FWD_MERGE 0     // 1: clamp-free full groups let adjacent hits with disjoint live pixels share an iteration (the parked
-                              // experiment scripts/dev/gen_blend_group_asm.py: correct, fewer vector instructions, not faster)
 #endif
 constexpr int kFRing = SCORP_FWD_RING, kFChunk = 64, kFGroup = 16;   // ring: at most 15 left-over hits + 64 new ones
 
@@ -786,16 +773,6 @@ constexpr int kFRing = SCORP_FWD_RING, kFChunk = 64, kFGroup = 16;   // ring: at
 // the backward).  The MFMA results stay in VGPRs either way (no accumulator-register reads in front of the v_exp).
 #ifndef SCORP_FWD_WAVES
 #define SCORP_FWD_WAVES 6
-#endif
-#ifdef SCORP_FWD_TRACE
-// diagnostic build only (scripts/dev/trace_forward.py): per wave (start, end) on the 100 MHz real-time counter and the
-// hardware id words, to draw the occupancy timeline of one launch
-__device__ unsigned long long g_fwd_trace[3 * 40000];
-#endif
-#ifdef SCORP_FWD_STATS
-// diagnostic build only (scripts/dev/stats_forward.py): how full the 64 lanes are per blended hit, and how many
-// iterations a wave would run if its hits were listed per 8x4 half / per 4x4 quadrant / per pixel instead of per block
-__device__ unsigned long long g_fwd_stats[12];
 #endif
 // kScore (scorp_gs3d_render_score; never with kForBackward): the render-and-compare scoring of a pose hypothesis
 // (align.StackedSweep) needs depth and alpha only and needs them only to be compared with a target: no colour is
@@ -818,18 +795,6 @@ blend_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_
   __shared__ float4 q_col[kFRing];       // r, g, b, depth
   __shared__ uint32_t q_id[kFRing];      // the hit's splat: written to the block's hit list only if some pixel took it (blend_group)
   const int lane = threadIdx.x;
-#ifdef SCORP_FWD_TRACE
-  struct TraceEnd {
-    unsigned long long t0; int lane; unsigned b;
-    __device__ ~TraceEnd() {
-      if (lane == 0 && b < 40000u) {
-        g_fwd_trace[3 * b] = t0; g_fwd_trace[3 * b + 1] = __builtin_amdgcn_s_memrealtime();
-        g_fwd_trace[3 * b + 2] = ((unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) << 32) |   // HW_REG_HW_ID
-                                 (unsigned)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));                       // HW_REG_XCC_ID
-      }
-    }
-  } trace_end{__builtin_amdgcn_s_memrealtime(), lane, blockIdx.x};
-#endif
   if (zero_buf) {   // this wave's share of the buffer the launch was asked to clear (every workgroup of the grid takes part)
     const uint32_t z0 = blockIdx.x * zero_per_wave, z1 = min(z0 + zero_per_wave, zero_total);
     typedef float f4v __attribute__((ext_vector_type(4)));
@@ -862,12 +827,6 @@ blend_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_
   uint32_t consumed = 0;     // hits blended so far ((block, splat) iterations: the P statistic)
   uint32_t kept_n = 0;       // ... of which some pixel took: the length of the hit list left for the backward (wave-uniform)
   uint32_t hot_end = 0;      // hits [0, hot_end) may hold a splat with opacity > 0.99 (wave-uniform; see blend_group)
-#ifdef SCORP_FWD_STATS
-  uint32_t st_hits = 0, st_live = 0, st_any = 0, st_q[4] = {0, 0, 0, 0}, st_h[2] = {0, 0}, st_lane = 0, st_pairs = 0;
-  uint32_t st_g16 = 0, st_g64 = 0, st_g8 = 0, st_gq[4] = {0, 0, 0, 0}, st_cq[4] = {0, 0, 0, 0}, st_hq[4] = {0, 0, 0, 0}, st_cn = 0;
-  uint64_t st_prev = 0;
-  bool st_have = false;
-#endif
   // The chunk's gathers (list entry -> record) are dependent loads of ~1 us each; they are software-pipelined: while
   // chunk c is blended the records of chunk c+1 and the list entries of chunk c+2 are already in flight.
   auto fetch_id = [&](uint32_t bs) { return (bs + lane < n) ? point_list[beg + bs + lane] : 0xFFFFFFFFu; };
@@ -945,11 +904,7 @@ blend_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_
           // A saturated pixel is latched by the SIGN of T: the splat that would take T below 1e-4 is not blended and
           // flips T negative, after which every test_T is negative too (a live pixel always has T >= 1e-4, and
           // alpha = 0 leaves test_T = T exactly).
-#if SCORP_FWD_FMA
           const float test_T = __builtin_fmaf(-al, T, T);
-#else
-          const float test_T = T * (1.0f - al);
-#endif
           const bool ok = test_T >= kTMin;
           const float ae = ok ? al : 0.0f;
           const float w = ae * T;
@@ -963,37 +918,12 @@ blend_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_
             // ballot of `took` itself - an AND of two conditions - goes through a VGPR 0 / 1 and a second v_cmp: +2 VALU per hit)
             kept16 |= ((__builtin_amdgcn_ballot_w64(ok) & __builtin_amdgcn_ballot_w64(live)) != 0ull ? 1u : 0u) << i;
           }
-#ifdef SCORP_FWD_STATS
-          {
-            const uint64_t m = __ballot(ok & live);
-            st_hits += 1; st_live += (uint32_t)__builtin_popcountll(m);
-            st_any += m != 0;
-            st_q[0] += (m & 0x000000000F0F0F0Full) != 0; st_q[1] += (m & 0x00000000F0F0F0F0ull) != 0;
-            st_q[2] += (m & 0x0F0F0F0F00000000ull) != 0; st_q[3] += (m & 0xF0F0F0F000000000ull) != 0;
-            st_h[0] += (m & 0x00000000FFFFFFFFull) != 0; st_h[1] += (m & 0xFFFFFFFF00000000ull) != 0;
-            st_lane += (ok & live) ? 1u : 0u;
-            // lock-step cost of per-quadrant lists when the four lists are synchronised every 8 / 16 / 64 block hits
-            // (the backward's matrix pass holds a fixed number of slots): sum over such windows of the largest quadrant count
-            if (m != 0) {
-              const uint32_t qb[4] = {(m & 0x000000000F0F0F0Full) != 0, (m & 0x00000000F0F0F0F0ull) != 0,
-                                      (m & 0x0F0F0F0F00000000ull) != 0, (m & 0xF0F0F0F000000000ull) != 0};
-              for (int q_ = 0; q_ < 4; q_++) { st_gq[q_] += qb[q_]; st_cq[q_] += qb[q_]; st_hq[q_] += qb[q_]; }
-              st_cn += 1;
-              if ((st_cn & 7) == 0) { st_g8 += max(max(st_hq[0], st_hq[1]), max(st_hq[2], st_hq[3])); st_hq[0] = st_hq[1] = st_hq[2] = st_hq[3] = 0; }
-              if ((st_cn & 15) == 0) { st_g16 += max(max(st_gq[0], st_gq[1]), max(st_gq[2], st_gq[3])); st_gq[0] = st_gq[1] = st_gq[2] = st_gq[3] = 0; }
-              if ((st_cn & 63) == 0) { st_g64 += max(max(st_cq[0], st_cq[1]), max(st_cq[2], st_cq[3])); st_cq[0] = st_cq[1] = st_cq[2] = st_cq[3] = 0; }
-            }
-            // greedy pairing of ADJACENT hits whose live lanes are disjoint (no pixel sees both: they could share an iteration)
-            if (st_have && (st_prev & m) == 0) { st_pairs += 1; st_have = false; }
-            else { st_prev = m; st_have = true; }
-          }
-#endif
         }
       }
       if constexpr (kForBackward) {
         // The block's HIT LIST keeps only the hits some pixel took.  A hit passes the exact block test when the conic's
         // minimum over the 8x8 box is below the cutoff - a minimum that may lie between pixel centres, or behind pixels that
-        // are already saturated: 6.6 % of the hits of an S3 view have no taker (scripts/dev/stats_forward.py), and the
+        // are already saturated: 6.6 % of the hits of an S3 view have no taker (profiles/r05_lane_occupancy_stats.txt), and the
         // backward, which replays the list, would run its whole per-hit pipeline (and an atomic row of zeros' worth of
         // bookkeeping) for each.  Positions are those of the compacted list: kept hits before this group + rank in it.
         if (lastg) last = kept_n + (uint32_t)__builtin_popcount(kept16 & ((1u << lastg) - 1u));
@@ -1008,59 +938,13 @@ blend_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_
       consumed += (uint32_t)nslots;
       return all_done;
     };
-#if SCORP_FWD_MERGE
-    // full clamp-free groups: adjacent hits whose live pixels are disjoint share an iteration (blend_group_asm.hpp: the
-    // sixteen slots as one hand-allocated assembly block; profiles/DESIGN_history_r01-r05.md section 8.0 (2))
-    auto blend_group_merged = [&](const f32x16 &e) -> bool {
-      const uint32_t gcb = (uint32_t)(size_t)(const void *)(q_col + head);   // LDS byte address of the group's first slot
-      bool all_done;
-      if constexpr (kForBackward) {
-        uint32_t lastg = 0, kept16 = 0;
-        all_done = blend_group_merged_asm_fb(e, gcb, T, C0, C1, C2, Dp, lastg, kept16);
-        int hv = head;
-        asm volatile("" : "+v"(hv));
-        if (lastg) last = kept_n + (uint32_t)__builtin_popcount(kept16 & ((1u << lastg) - 1u));
-        if (lane < kFGroup && ((kept16 >> lane) & 1u)) my_hits[kept_n + __builtin_amdgcn_mbcnt_lo(kept16, 0u)] = q_id[hv + lane];
-        kept_n += (uint32_t)__builtin_popcount(kept16);
-        __builtin_amdgcn_sched_barrier(0);
-      } else {
-        all_done = blend_group_merged_asm_img(e, gcb, T, C0, C1, C2, Dp);
-      }
-      head = head + kFGroup == kFRing ? 0 : head + kFGroup;
-      count -= kFGroup;
-      consumed += (uint32_t)kFGroup;
-      return all_done;
-    };
-#endif
     bool all_done = false;   // every pixel saturated: checked twice per group, not only once per 64 list entries
-#if SCORP_FWD_DB
-    // The exponents of the NEXT group are issued to the matrix cores before the current group is blended: the three
-    // dependent MFMAs (~100 cycles before the first result can be read) then run under the blend instead of in front of it.
-    if (count >= kFGroup) {
-      f32x16 e = exponents(head);
-      for (;;) {
-        const bool more = count >= 2 * kFGroup;
-        f32x16 e2 = e;
-        if (more) e2 = exponents(head + kFGroup == kFRing ? 0 : head + kFGroup);
-        const bool gd = consumed < hot_end ? blend_group(std::true_type{}, std::true_type{}, kFGroup, e)
-                                           : blend_group(std::true_type{}, std::false_type{}, kFGroup, e);
-        if (gd || __ballot(T > 0.0f) == 0) { all_done = true; break; }
-        if (!more) break;
-        e = e2;
-      }
-    }
-#else
     while (count >= kFGroup) {
       const f32x16 e = exponents(head);
-#if SCORP_FWD_MERGE
-      const bool gd = consumed < hot_end ? blend_group(std::true_type{}, std::true_type{}, kFGroup, e) : blend_group_merged(e);
-#else
       const bool gd = consumed < hot_end ? blend_group(std::true_type{}, std::true_type{}, kFGroup, e)
                                          : blend_group(std::true_type{}, std::false_type{}, kFGroup, e);
-#endif
       if (gd || __ballot(T > 0.0f) == 0) { all_done = true; break; }
     }
-#endif
     if (all_done) break;
     if (last_chunk && count > 0) blend_group(std::false_type{}, std::true_type{}, count, exponents(head));   // (one group per wave: not worth a variant)
     id0 = id1; a = a1; b = b1; c = c1; id1 = id2;
@@ -1068,25 +952,6 @@ blend_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_
   if constexpr (kForBackward) {
     if (lane == 0) block_hits[tile * 4 + quad] = consumed;   // (block, splat) iterations this wave ran: the P statistic
   }
-#ifdef SCORP_FWD_STATS
-  {
-    uint32_t lm = st_lane;
-    for (int off = 32; off >= 1; off >>= 1) lm = max(lm, (uint32_t)__shfl_xor((int)lm, off, 64));
-    if (lane == 0) {
-      atomicAdd(&g_fwd_stats[0], (unsigned long long)st_hits); atomicAdd(&g_fwd_stats[1], (unsigned long long)st_live);
-      atomicAdd(&g_fwd_stats[2], (unsigned long long)st_any);
-      atomicAdd(&g_fwd_stats[3], (unsigned long long)(st_q[0] + st_q[1] + st_q[2] + st_q[3]));
-      atomicAdd(&g_fwd_stats[4], (unsigned long long)max(max(st_q[0], st_q[1]), max(st_q[2], st_q[3])));
-      atomicAdd(&g_fwd_stats[5], (unsigned long long)(st_h[0] + st_h[1]));
-      atomicAdd(&g_fwd_stats[6], (unsigned long long)max(st_h[0], st_h[1]));
-      atomicAdd(&g_fwd_stats[7], (unsigned long long)lm);
-      atomicAdd(&g_fwd_stats[8], (unsigned long long)st_pairs);
-      atomicAdd(&g_fwd_stats[9], (unsigned long long)(st_g8 + max(max(st_hq[0], st_hq[1]), max(st_hq[2], st_hq[3]))));
-      atomicAdd(&g_fwd_stats[10], (unsigned long long)(st_g16 + max(max(st_gq[0], st_gq[1]), max(st_gq[2], st_gq[3]))));
-      atomicAdd(&g_fwd_stats[11], (unsigned long long)(st_g64 + max(max(st_cq[0], st_cq[1]), max(st_cq[2], st_cq[3]))));
-    }
-  }
-#endif
   if constexpr (kScore) {
     float term = 0.0f;
     if (inside) {
@@ -1535,16 +1400,3 @@ extern "C" int scorp_gs3d_debug_tiles(const void *state, const void *pairs, uint
   SCORP_HIP_CHECK(hipStreamSynchronize(stream));
   return copy_tile_lists_raster(L, P, state, pairs, capacity, h.num_pairs, tile_start, point_list, stream);
 }
-
-#ifdef SCORP_FWD_STATS
-extern "C" int scorp_debug_fwd_stats(unsigned long long *out, int reset) {
-  static const unsigned long long zero[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(scorp::g_fwd_stats), 96) != hipSuccess) return -2;
-  return reset && hipMemcpyToSymbol(HIP_SYMBOL(scorp::g_fwd_stats), zero, 96) != hipSuccess ? -2 : 0;
-}
-#endif
-#ifdef SCORP_FWD_TRACE
-extern "C" int scorp_debug_fwd_trace(unsigned long long *out, int n_waves) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(scorp::g_fwd_trace), (size_t)n_waves * 24) == hipSuccess ? 0 : -2;
-}
-#endif

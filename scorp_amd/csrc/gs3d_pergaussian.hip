@@ -198,7 +198,7 @@ __device__ __forceinline__ void preprocess_body(const PgArgs &a, float *s_sh, Sp
     raw_issue_params(r, a.means3D + 3 * (size_t)i, a.rotations + 4 * (size_t)i, a.scales + 3 * (size_t)i, a.opacities + i);
     // One view per launch: nobody reads these rows again before the backward, > 1 GB of traffic later - nontemporal (same box,
     // S3: 63 - 66 -> 57 us).  A stacked launch (a.views > 1) re-reads them once per view, from L2: default policy there.
-    if (SCORP_NT_SH && a.views <= 1) stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);
+    if (a.views <= 1) stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);
     else stage_sh_linear_async<0>(s_sh, a.shs, a.shs_rest, i0);
     raw_take_params(r, p);
     px_ = p[0]; py_ = p[1]; pz_ = p[2];
@@ -308,7 +308,7 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
     raw_issue_params(ra, ap, ap + 3, ap + 7, reinterpret_cast<const float *>(&bin[i].radius));
     // nontemporal as in the forward (94 -> 90.5 us) - unless the optimizer step runs in the epilogue: the block then reads its SH
     // parameters a second time, from L2
-    if (SCORP_NT_SH && !(SPLIT && ad.on != 0)) stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);
+    if (!(SPLIT && ad.on != 0)) stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);
     else stage_sh_linear_async<0>(s_sh, a.shs, a.shs_rest, i0);
     raw_take_params(r, pre);
     raw_take_params(ra, pre_acc);   // (its vmcnt(12) is already satisfied)
@@ -632,15 +632,9 @@ void launch_preprocess(const ScorpGs3dInputs *in, const StateLayout &L, SplatRec
   const dim3 grid((a.N + 255) / 256, a.views), block(256);
   const int deg = in->shs ? in->sh_degree : 0;
   const bool split = in->shs_rest != nullptr;
-#define SCORP_LAUNCH_PRE(D, S) preprocess_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, tile_mask, radii, tile_count)
-  if (split) {
-    switch (deg) { case 0: SCORP_LAUNCH_PRE(0, true); break; case 1: SCORP_LAUNCH_PRE(1, true); break;
-                   case 2: SCORP_LAUNCH_PRE(2, true); break; default: SCORP_LAUNCH_PRE(3, true); }
-  } else {
-    switch (deg) { case 0: SCORP_LAUNCH_PRE(0, false); break; case 1: SCORP_LAUNCH_PRE(1, false); break;
-                   case 2: SCORP_LAUNCH_PRE(2, false); break; default: SCORP_LAUNCH_PRE(3, false); }
-  }
-#undef SCORP_LAUNCH_PRE
+  dispatch_sh_degree(deg, split, [&](auto D, auto S) {
+    preprocess_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, tile_mask, radii, tile_count);
+  });
 }
 
 void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L, const BinRec *bin, const float *acc,
@@ -653,15 +647,9 @@ void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L,
   AdamEpi ad;
   memset(&ad, 0, sizeof(ad));
   if (adam && split) ad = *adam;   // (the fused step is defined for the training layout: dc / rest split leaves)
-#define SCORP_LAUNCH_PB(D, S) preprocess_backward_kernel<D, S><<<grid, block, 0, stream>>>(a, bin, acc, g, ad)
-  if (split) {
-    switch (deg) { case 0: SCORP_LAUNCH_PB(0, true); break; case 1: SCORP_LAUNCH_PB(1, true); break;
-                   case 2: SCORP_LAUNCH_PB(2, true); break; default: SCORP_LAUNCH_PB(3, true); }
-  } else {
-    switch (deg) { case 0: SCORP_LAUNCH_PB(0, false); break; case 1: SCORP_LAUNCH_PB(1, false); break;
-                   case 2: SCORP_LAUNCH_PB(2, false); break; default: SCORP_LAUNCH_PB(3, false); }
-  }
-#undef SCORP_LAUNCH_PB
+  dispatch_sh_degree(deg, split, [&](auto D, auto S) {
+    preprocess_backward_kernel<D, S><<<grid, block, 0, stream>>>(a, bin, acc, g, ad);
+  });
 }
 
 }  // namespace scorp

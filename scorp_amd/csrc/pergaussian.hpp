@@ -135,9 +135,6 @@ __device__ __forceinline__ void sh_row_zero(ShRow r) {
 // issued as direct global -> LDS loads (global_load_lds_dwordx4: each lane's 16 bytes land at
 // M0 base + lane * 16, no VGPR round trip).  Fire-and-forget: the caller does its other work, then
 // stage_sh_wait() + a workgroup barrier before anyone reads the rows.  48 wave-chunks of 1 KiB, 12 per wave.
-#ifndef SCORP_NT_SH
-#define SCORP_NT_SH 1   // nontemporal SH staging where the rows have no second reader nearby (0: A/B builds)
-#endif
 // AUX: the loads' cache-policy bits (0: default; 2: nontemporal - rows that nobody reads again before > 1 GB of other traffic)
 template <int AUX = 0>
 __device__ __forceinline__ void stage_sh_linear_async(float *__restrict__ lds, const float *__restrict__ dc,

@@ -11,11 +11,11 @@ out = os.path.join(ROOT, "build", "variants", "probe")
 os.makedirs(out, exist_ok=True)
 src = open(os.path.join(C, "gs3d_pergaussian.hip")).read()
 hpp = open(os.path.join(C, "pergaussian.hpp")).read()
-h2 = hpp.replace("(LPtr)(l4 + c * 64), 16, 0, 0)", "(LPtr)(l4 + (c % 24) * 64), 16, 0, 0)")
-h2 = h2.replace("(LPtr)(lr4 + (c - 3) * 64), 16, 0, 0)", "(LPtr)(l4 + (c % 24) * 64), 16, 0, 0)")
+h2 = hpp.replace("(LPtr)(l4 + c * 64), 16, 0, AUX)", "(LPtr)(l4 + (c % 24) * 64), 16, 0, AUX)")
+h2 = h2.replace("(LPtr)(lr4 + (c - 3) * 64), 16, 0, AUX)", "(LPtr)(l4 + (c % 24) * 64), 16, 0, AUX)")
 h2 = h2.replace("r.p0 = lds + 3 * t; r.pr = lds + kShLinearRest + 45 * t - 3;", "r.p0 = lds + (3 * t) % 6000; r.pr = lds + (kShLinearRest + 45 * t - 3) % 6000;")
 assert h2.count("% 24") == 2 and "% 6000" in h2
-a = "int32_t *__restrict__ radii, uint32_t *__restrict__ tile_count) {\n  __shared__ __attribute__((aligned(16))) float s_sh[256 * kShStride];"
+a = "int32_t *__restrict__ radii, uint32_t *__restrict__ tile_count) {\n  __shared__ __attribute__((aligned(16))) float s_sh[DEG == 0 ? 4 : 256 * kShStride];"
 assert src.count(a) == 1      # the forward kernel only (the backward's declaration differs)
 open(os.path.join(out, "pergaussian.hpp"), "w").write(h2)
 open(os.path.join(out, "gs3d_pergaussian.hip"), "w").write(src.replace(a, a.replace("256 * kShStride", "128 * kShStride")))
