@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — fwd+bwd views/s of the 3DGS hot path on synthetic Gaussians (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S3] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,8 +12,12 @@ in the timed region.  Inputs (parameters, cameras, GT images) are resident in HB
 With N > 1 every rank holds a replica of the scene (broadcast once from rank 0 over RCCL) and renders its own
 views (view i -> rank i mod N): weak scaling, no collective on the data path; value = views of all ranks / time.
 Rank 0 prints ONE JSON line: numbers only (what every field means, and the prose that used to ride in the line, is
-DESIGN.md section 5), short enough for a log tail, with `value`, `value_exact_fp32`, `value_deterministic_backward`,
-`roofline` and `cpu_baseline` as its LAST keys.
+DESIGN.md section 5), short enough for a log tail.
+A plain run does only what the headline needs: set-up, the probe views that find the kernel the timed region brackets,
+the warm-up and timed steps, --dump-outputs, the line, which ends in `ms_per_step` and `value`.  With --full the same
+run goes on to the per-kernel table and roofline, the other backward forms, the extras, the secondary records, the CPU
+baseline and the parity against the CPU oracle, and its line ends in `value`, `value_exact_fp32`,
+`value_deterministic_backward`, `roofline` and `cpu_baseline`.
 """
 import argparse
 import json
@@ -516,7 +520,7 @@ def launch_ranks(n):
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)      # >= 200 views after 20 warm-up views
@@ -537,7 +541,7 @@ def main():
                          "pattern) instead of the single-call scorp_gs3d_train_view; same kernels, more host work per view")
     ap.add_argument("--unfused", action="store_true", help="reference call-site convention: torch activations + cat per view")
     ap.add_argument("--spatial-sort", action="store_true", help="GaussianModel.sort_spatially() first: Gaussians stored along a Z-order curve (not the default)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary record (the 2DGS workload S6) of the default N=1 run")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary records and the drop-in, two-in-flight and training extras")
     ap.add_argument("--lead-in", type=int, default=40, help="untimed views enqueued in front of the warm-up of every timed run (see timed_run)")
     ap.add_argument("--no-twins", action="store_true", help="skip the two extra timed runs (all-fp32 backward, deterministic backward): profiling passes")
     ap.add_argument("--exact-backward", action="store_true", help="(kept for old command lines: the all-fp32 backward IS the headline now) also skips the secondary records")
@@ -549,7 +553,15 @@ def main():
                          "gradients of every parameter) as DIR/<name>.npy, float32 / float64, at most 64 MB (large arrays as a "
                          "fixed, seeded sample of their elements); rank 0's view.  Same arguments, same inputs: the render "
                          "maps and the loss repeat bit for bit, the gradients up to the order of the backward's float atomics")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: the per-kernel table and roofline, the other "
+                         "backward forms, the extras, the secondary records, the CPU baseline and the parity against the CPU "
+                         "oracle (--no-twins, --no-secondary and --no-cpu-baseline leave parts of it out)")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))      # bare `python bench.py --gpus N`: this process only starts the N ranks (no GPU call made here)
@@ -687,7 +699,8 @@ def main():
 
     PairPolicy.mode, PairPolicy.reserve = "reserve", int(max(Ds) * 1.25) + 1024
     # probe (setup, untimed, before the warm-up): a few views with EVERY kernel bracketed by hipEvents give the per-kernel
-    # table and tell which kernel dominates
+    # table and tell which kernel dominates.  A plain run probes too: the timed region brackets the dominant kernel in
+    # every run, so that `ms_per_step` is the same figure with and without --full.
     kern_all, dominant, reconcile = {}, None, None
     if not args.no_kernel_events:
         for i in range(3):       # first launches of the step's kernels (code objects, scratch): not in the per-kernel table
@@ -700,6 +713,7 @@ def main():
         torch.cuda.synchronize()
         kern_all = _C.prof_collect()
         dominant = max(kern_all, key=lambda k: kern_all[k][0]) if any(c for _, c in kern_all.values()) else None
+    if not args.no_kernel_events and args.full:
         # Reconciliation of the per-kernel table with the step: the same few views once more with every
         # kernel bracketed and ONE event pair around them, then with nothing bracketed.  kernel sum + gaps = bracketed view;
         # bracketed view - plain view = what the brackets themselves cost (an event pair is a few microseconds of stream time,
@@ -770,7 +784,7 @@ def main():
     # the same step with the OTHER form of the blend backward's pixel->splat reduction (the two-term fp16 split if the headline
     # is all-fp32, and the other way round), same protocol: the headline next to its twin
     dt_twin = dt_det = None
-    if fused_view and side_streams is None and not args.no_twins:
+    if args.full and fused_view and side_streams is None and not args.no_twins:
         prev_flags = getattr(R._tls, "backward_flags", 0)
         R._tls.backward_flags = 0 if (prev_flags & _C.BACKWARD_EXACT_FP32) else _C.BACKWARD_EXACT_FP32
         try:
@@ -793,7 +807,7 @@ def main():
     # `torch_activations_and_ssim`: the same step with both switched off (pipe.fused_activations = False, ssim_torch) -
     # torch sigmoid / exp / normalize / cat and five depthwise 11x11 conv2d per view: round 6's first definition of the figure.
     dropin = None
-    if world == 1 and not surfels and side_streams is None and not args.no_secondary:
+    if args.full and world == 1 and not surfels and side_streams is None and not args.no_secondary:
         try:
             from scorp_amd.loss import l1_loss as ref_l1, ssim as ref_ssim, ssim_torch
 
@@ -832,20 +846,22 @@ def main():
             for p in params:
                 p.grad = None
     # extra (not part of `value`): forward-only render rate, the unit of the alignment sweep / test-view rendering
-    nf = max(args.steps // 2, 1)
-    torch.cuda.synchronize()
-    tf0 = time.perf_counter()
-    with torch.no_grad():
-        for i in range(nf):
-            render(my_cams[i % len(my_cams)], model, pipe, bg)
-    PairPolicy.drain()
-    torch.cuda.synchronize()
-    fwd_only = nf / (time.perf_counter() - tf0)
+    fwd_only = None
+    if args.full:
+        nf = max(args.steps // 2, 1)
+        torch.cuda.synchronize()
+        tf0 = time.perf_counter()
+        with torch.no_grad():
+            for i in range(nf):
+                render(my_cams[i % len(my_cams)], model, pipe, bg)
+        PairPolicy.drain()
+        torch.cuda.synchronize()
+        fwd_only = nf / (time.perf_counter() - tf0)
     # extra (not part of `value`): the same step with TWO views in flight on two HIP streams - the batch-of-views form of
     # training (data-parallel ranks sharing a GPU, multi-view evaluation): the second view's kernels fill the SIMDs that
     # the first one's latency-bound kernels (binning, loss) and kernel tails leave idle
     in_flight2 = None
-    if fused_view and side_streams is None and not args.no_secondary:
+    if args.full and fused_view and side_streams is None and not args.no_secondary:
         pair = [torch.cuda.Stream(), torch.cuda.Stream()]
         for st_ in pair:
             st_.wait_stream(torch.cuda.current_stream())
@@ -873,7 +889,7 @@ def main():
     # work statistics of view 0 (SURVEY §8d asks for an honest pixel-splat figure next to HBM): (8x8 block, splat)
     # iterations of the two blend kernels, each of which evaluates 64 pixel-splat pairs
     work = None
-    if rank == 0 and not surfels:
+    if args.full and rank == 0 and not surfels:
         import ctypes
         R.KEEP_LAST_FORWARD = True
         render(my_cams[0], model, pipe, bg)      # grad-enabled: the forward leaves its per-block statistics
@@ -896,14 +912,14 @@ def main():
 
     # view 0 of the UNTRAINED parameters for the full-size parity figures (the training extra below moves the model)
     hip_view0 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not surfels:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not surfels:
         with torch.no_grad():
             hip_view0 = render(my_cams[0], model, pipe, bg)["render"].cpu().numpy()
     # extra (not part of `value`), N = 1: FULL training iterations on the same model and cameras - the one-call view, the
     # per-view densification statistics (scorp_densification_stats) and the guarded FusedAdam step over all 59 parameters
     # per Gaussian (train_3dgs.py:74-193 / train_2dgs.py without the densification itself, which runs every 100th iteration)
     train_its = None
-    if world == 1 and fused_view and side_streams is None and not args.no_secondary and not args.exact_backward:
+    if args.full and world == 1 and fused_view and side_streams is None and not args.no_secondary and not args.exact_backward:
         try:
             from scorp_amd.gaussian_model import OptimizationParams, OptimizationParams2D
             from scorp_amd.train import training_iteration
@@ -940,7 +956,7 @@ def main():
     # costs the headline): every N the 128-rotation sweep (the workload north_star's 8-GPU scaling target is set on) and
     # the object-sharded post-refinement; N > 1 the data-parallel training of one scene; N = 1 the 2DGS workload S6
     secondary = {}
-    if args.scene == "S3" and not args.no_secondary and not args.exact_backward and args.streams == 1:
+    if args.full and args.scene == "S3" and not args.no_secondary and not args.exact_backward and args.streams == 1:
         secondary["sweep_128"] = secondary_sweep(dev, cdev, rank, world)
         secondary["post_refine_4obj"] = secondary_post_refine_objects(dev, cdev, rank, world)
         if world > 1:
@@ -951,7 +967,7 @@ def main():
         value = views / dt
         HW = W * H
         roof, kernels = None, {}
-        if kern:
+        if args.full and kern:
             merged = dict(kern_all)
             merged.update({k: v for k, v in kern.items() if v[1]})   # dominant kernel: live numbers of the timed region
             for name, (ms, cnt) in merged.items():
@@ -1009,18 +1025,20 @@ def main():
             "precision": "f32 throughout (blend backward's pixel->splat reduction on fp32 MFMAs)" if exact_is_headline
                          else "f32; backward pixel->splat reduction: 2-term fp16 split MFMA (22 bits), fp32 accumulate",
             "library_default_backward": "2-term fp16 split (value_split22); the headline asks for SCORP_BACKWARD_EXACT_FP32 per view",
-
-            "kernels_us_GBs": kernels,
-            "kernel_table_reconciliation": reconcile,
-            "pairs_per_s": (_sig(value * (P_f + P_b), 4) if work else None),
-            "forward_only_views_per_s_per_gpu": round(fwd_only, 1),
-            "views_per_s_two_in_flight": None if in_flight2 is None else round(in_flight2, 1),
-            "train_iterations_per_s": train_its,
-            "view_hbm": {"algorithmic_bytes_per_view": int(B_view), "achieved_GBs": round(value / world * B_view / 1e9, 1),
-                         "frac_of_8TBs": round(value / world * B_view / 8e12, 5)},
         }
+        if args.full:
+            line.update({
+                "kernels_us_GBs": kernels,
+                "kernel_table_reconciliation": reconcile,
+                "pairs_per_s": (_sig(value * (P_f + P_b), 4) if work else None),
+                "forward_only_views_per_s_per_gpu": round(fwd_only, 1),
+                "views_per_s_two_in_flight": None if in_flight2 is None else round(in_flight2, 1),
+                "train_iterations_per_s": train_its,
+            })
+        line["view_hbm"] = {"algorithmic_bytes_per_view": int(B_view), "achieved_GBs": round(value / world * B_view / 1e9, 1),
+                            "frac_of_8TBs": round(value / world * B_view / 8e12, 5)}
         cpu_rec = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu_rec, orc = cpu_baseline(raw, my_cams[0].to("cpu"), deg, W, H)
             line["parity"] = small_parity(dev)
             my_cams[0].to(dev)     # (.to() moves in place)
@@ -1043,7 +1061,7 @@ def main():
                 line["parity_ok"] = bool(line["parity"]["full_size"]["l1"] < 1e-4 and all(v[1] < 1e-4 for v in errs.values()))
                 if not line["parity_ok"]:
                     print("[bench] full-size parity outside 1e-4: " + json.dumps(line["parity"]["full_size"]), file=sys.stderr)
-        if world == 1 and args.scene == "S3" and not args.no_secondary and not args.exact_backward:
+        if args.full and world == 1 and args.scene == "S3" and not args.no_secondary and not args.exact_backward:
             try:
                 secondary["S6"] = secondary_s6(dev, parity=not args.no_cpu_baseline)
             except Exception as e:   # noqa: BLE001
@@ -1053,17 +1071,18 @@ def main():
         # the figures the record is read for come LAST (a log tail keeps the end of the line)
         line["ms_per_step"] = round(dt / args.steps * 1e3, 4)
         line["value"] = round(value, 3)
-        line["value_exact_fp32"] = round(value, 3) if exact_is_headline else (None if dt_exact is None else round(views / dt_exact, 3))
-        line["ms_per_step_exact_fp32"] = line["ms_per_step"] if exact_is_headline else (None if dt_exact is None else round(dt_exact / args.steps * 1e3, 4))
-        line["value_split22"] = (None if dt_split is None else round(views / dt_split, 3)) if exact_is_headline else round(value, 3)
-        line["ms_per_step_split22"] = (None if dt_split is None else round(dt_split / args.steps * 1e3, 4)) if exact_is_headline else line["ms_per_step"]
-        line["value_dropin"] = None if dropin is None else dropin.get("value")
-        line["dropin"] = dropin
-        line["value_deterministic_backward"] = None if dt_det is None else round(views / dt_det, 3)
-        line["ms_per_step_deterministic_backward"] = None if dt_det is None else round(dt_det / args.steps * 1e3, 4)
-        line["roofline"] = roof
-        if cpu_rec is not None:
-            line["cpu_baseline"] = cpu_rec
+        if args.full:
+            line["value_exact_fp32"] = round(value, 3) if exact_is_headline else (None if dt_exact is None else round(views / dt_exact, 3))
+            line["ms_per_step_exact_fp32"] = line["ms_per_step"] if exact_is_headline else (None if dt_exact is None else round(dt_exact / args.steps * 1e3, 4))
+            line["value_split22"] = (None if dt_split is None else round(views / dt_split, 3)) if exact_is_headline else round(value, 3)
+            line["ms_per_step_split22"] = (None if dt_split is None else round(dt_split / args.steps * 1e3, 4)) if exact_is_headline else line["ms_per_step"]
+            line["value_dropin"] = None if dropin is None else dropin.get("value")
+            line["dropin"] = dropin
+            line["value_deterministic_backward"] = None if dt_det is None else round(views / dt_det, 3)
+            line["ms_per_step_deterministic_backward"] = None if dt_det is None else round(dt_det / args.steps * 1e3, 4)
+            line["roofline"] = roof
+            if cpu_rec is not None:
+                line["cpu_baseline"] = cpu_rec
         sys.stdout.flush()
         os.write(line_fd, (json.dumps(line, separators=(",", ":")) + "\n").encode())
         parity_failed = line.get("parity_ok") is False

@@ -10,7 +10,7 @@ for spec in "$@"; do
   (
     if [ "$lib" != default ]; then export SCORP_GS_LIB=$PWD/$lib; fi
     for e in "${envs[@]}"; do export "$e"; done
-    python3 bench.py --no-cpu-baseline --no-secondary --steps ${STEPS:-40} --warmup 10 ${BENCH_ARGS} > $out/tmp.json 2> $out/tmp.err || { echo "$spec FAILED" >> $out/ab.txt; tail -3 $out/tmp.err >> $out/ab.txt; exit 0; }
+    python3 bench.py --full --no-cpu-baseline --no-secondary --steps ${STEPS:-40} --warmup 10 ${BENCH_ARGS} > $out/tmp.json 2> $out/tmp.err || { echo "$spec FAILED" >> $out/ab.txt; tail -3 $out/tmp.err >> $out/ab.txt; exit 0; }
     python3 - "$spec" $out/tmp.json >> $out/ab.txt << 'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

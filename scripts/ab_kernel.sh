@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 for lib in "$@"; do
   name=$(basename $lib .so)
   ( if [ "$lib" != default ]; then export SCORP_GS_LIB=$PWD/$lib; fi
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/$name -- python3 bench.py --steps 20 --warmup 3 --lead-in 5 --no-cpu-baseline --no-secondary --no-kernel-events $AB_BENCH_ARGS > $out/$name.log 2>&1 )
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/$name -- python3 bench.py --full --steps 20 --warmup 3 --lead-in 5 --no-cpu-baseline --no-secondary --no-kernel-events $AB_BENCH_ARGS > $out/$name.log 2>&1 )
   f=$(find $out/$name -name '*kernel_stats.csv' | head -1)
   python3 - "$name" "$f" "$pat" <<'PY' | tee -a $out/ab_kernel.txt
 import csv, sys

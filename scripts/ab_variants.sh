@@ -5,7 +5,7 @@ tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
 for lib in default "$@"; do
   if [ "$lib" = default ]; then unset SCORP_GS_LIB; else export SCORP_GS_LIB=$PWD/$lib; fi
-  python3 bench.py --no-cpu-baseline --steps ${STEPS:-40} --warmup 10 ${BENCH_ARGS} > $out/tmp.json 2> $out/tmp.err || { echo "$lib FAILED" >> $out/ab.txt; tail -3 $out/tmp.err >> $out/ab.txt; continue; }
+  python3 bench.py --full --no-cpu-baseline --steps ${STEPS:-40} --warmup 10 ${BENCH_ARGS} > $out/tmp.json 2> $out/tmp.err || { echo "$lib FAILED" >> $out/ab.txt; tail -3 $out/tmp.err >> $out/ab.txt; continue; }
   python3 - "$lib" $out/tmp.json >> $out/ab.txt << 'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -76,6 +76,15 @@ def test_bench_self_launcher_builds_the_torchrun_command(monkeypatch):
     assert seen["env"]["MASTER_ADDR"] == "127.0.0.1" and seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_plain_run_is_the_default_and_full_is_opt_in():
+    """`bench.py --gpus N --steps K --warmup W` measures the headline alone; everything else waits for --full."""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup) == (1, 20, 5)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full is True and (full.gpus, full.steps, full.warmup) == (1, 20, 5)
+
+
 def test_add_densification_stats_without_mask_compaction_equals_the_reference_statements():
     """gaussian_model.py:603-605 (3DGS: norm over x, y) and gs2dgs/scene/gaussian_model.py:494-495 (2DGS: the whole row): with a
     boolean mask the update runs over all rows - same bits as the two boolean-mask indexings - and an index tensor takes the
