@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _C
-from .rasterizer3d import GaussianRasterizationSettings, PairPolicy, _inputs_struct, _prep, _ptr, _stream
+from .rasterizer3d import _GS3D, GaussianRasterizationSettings, PairPolicy, _preprocess, _ptr, _raw_inputs, _stream
 
 
 class ViewStack:
@@ -51,6 +51,17 @@ class ViewStack:
         return view.contiguous(), proj.contiguous(), campos.contiguous()
 
 
+def _stacked_inputs(pc, stack, bg, view, proj, campos, scaling_modifier, keep):
+    """ScorpGs3dInputs of the model's raw leaves seen from the V cameras of `stack` (num_views = V)."""
+    settings = GaussianRasterizationSettings(
+        image_height=stack.H, image_width=stack.W, tanfovx=stack.tanfovx, tanfovy=stack.tanfovy, bg=bg,
+        scale_modifier=scaling_modifier, viewmatrix=view, projmatrix=proj, sh_degree=pc.active_sh_degree, campos=campos,
+        prefiltered=False, debug=False)
+    _, _, args = _raw_inputs(settings, pc, keep)
+    args.num_views = stack.V
+    return args
+
+
 @torch.no_grad()
 def render_stacked(pc, stack, bg, view=None, proj=None, campos=None, scaling_modifier=1.0):
     """Forward-only render of `pc` from the V cameras of `stack` (optionally with replaced matrices, e.g. from
@@ -63,37 +74,18 @@ def render_stacked(pc, stack, bg, view=None, proj=None, campos=None, scaling_mod
         raise RuntimeError("render_stacked needs GPU tensors (scorp_amd has no CPU path)")
     dev = xyz.device
     V, W, H, N = stack.V, stack.W, stack.H, xyz.shape[0]
-    view = stack.view if view is None else view
-    proj = stack.proj if proj is None else proj
-    campos = stack.campos if campos is None else campos
-    f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw = pc.raw_leaves()
-    t = [_prep(x.detach(), n) for x, n in zip((xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw),
-                                              ("means3D", "features_dc", "features_rest", "opacity", "scaling", "rotation"))]
-    settings = GaussianRasterizationSettings(
-        image_height=H, image_width=W, tanfovx=stack.tanfovx, tanfovy=stack.tanfovy, bg=bg, scale_modifier=scaling_modifier,
-        viewmatrix=view, projmatrix=proj, sh_degree=pc.active_sh_degree, campos=campos, prefiltered=False, debug=False)
     keep = []
-    args = _inputs_struct(settings, t[0], t[1], None, t[3], t[4], t[5], None, keep, t[2], 7)
-    args.num_views = V
+    args = _stacked_inputs(pc, stack, bg, stack.view if view is None else view, stack.proj if proj is None else proj,
+                           stack.campos if campos is None else campos, scaling_modifier, keep)
     Nt, Ht = V * N, V * H
-    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
-    color, depth, alpha, radii = new((3, Ht, W)), new((Ht, W)), new((Ht, W)), new((Nt,), torch.int32)
-    state_bytes = L.scorp_gs3d_state_bytes(Nt, W, Ht)
-    state = new((state_bytes,), torch.uint8)
     stream = _stream()
-    _C.check(L.scorp_gs3d_preprocess(ctypes.byref(args), _ptr(radii), _ptr(state), state_bytes, stream), "scorp_gs3d_preprocess")
-    if PairPolicy.mode == "exact":
-        n = ctypes.c_uint64(0)
-        _C.check(L.scorp_gs3d_num_pairs(_ptr(state), stream, ctypes.byref(n)), "scorp_gs3d_num_pairs")
-        capacity = max(int(n.value), 1)
-        num_pairs = int(n.value)
-    else:
-        capacity = PairPolicy.capacity(Nt, Ht, W)
-        num_pairs = None
-    pairs = new((L.scorp_gs3d_pairs_bytes(capacity),), torch.uint8)
+    exact = PairPolicy.mode == "exact"
+    new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    color, depth, alpha = new((3, Ht, W)), new((Ht, W)), new((Ht, W))   # before _preprocess, which may wait
+    radii, state, pairs, capacity, num_pairs = _preprocess(_GS3D, args, Nt, Ht, W, dev, stream, exact)
     _C.check(L.scorp_gs3d_render_image(ctypes.byref(args), _ptr(state), _ptr(pairs), capacity, _ptr(color), _ptr(depth),
                                        _ptr(alpha), stream), "scorp_gs3d_render_image")
-    if PairPolicy.mode != "exact":
+    if not exact:
         PairPolicy.pend(state, Nt, Ht, W)
     return {"render": color, "render_depth_raw": depth, "render_alpha": alpha, "radii": radii.view(V, N), "num_pairs": num_pairs}
 
@@ -107,27 +99,14 @@ def score_stacked(pc, stack, bg, view, proj, campos, tgt_depth, tgt_alpha, acc, 
     Reserve-mode sizing only (the sweep verifies its launch sets with one PairPolicy.drain())."""
     L = _C.lib()
     xyz = pc.get_xyz
-    dev = xyz.device
     V, W, H, N = stack.V, stack.W, stack.H, xyz.shape[0]
-    f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw = pc.raw_leaves()
-    t = [_prep(x.detach(), n) for x, n in zip((xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw),
-                                              ("means3D", "features_dc", "features_rest", "opacity", "scaling", "rotation"))]
-    settings = GaussianRasterizationSettings(
-        image_height=H, image_width=W, tanfovx=stack.tanfovx, tanfovy=stack.tanfovy, bg=bg, scale_modifier=scaling_modifier,
-        viewmatrix=view, projmatrix=proj, sh_degree=pc.active_sh_degree, campos=campos, prefiltered=False, debug=False)
     keep = []
-    args = _inputs_struct(settings, t[0], t[1], None, t[3], t[4], t[5], None, keep, t[2], 7)
-    args.num_views = V
+    args = _stacked_inputs(pc, stack, bg, view, proj, campos, scaling_modifier, keep)
     Nt, Ht = V * N, V * H
     assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.numel() * rows_per_score == Ht
     assert tgt_depth.is_contiguous() and tgt_alpha.is_contiguous() and tgt_depth.numel() == rows_per_score * W == tgt_alpha.numel()
-    radii = torch.empty((Nt,), dtype=torch.int32, device=dev)
-    state_bytes = L.scorp_gs3d_state_bytes(Nt, W, Ht)
-    state = torch.empty((state_bytes,), dtype=torch.uint8, device=dev)
     stream = _stream()
-    _C.check(L.scorp_gs3d_preprocess(ctypes.byref(args), _ptr(radii), _ptr(state), state_bytes, stream), "scorp_gs3d_preprocess")
-    capacity = PairPolicy.capacity(Nt, Ht, W)
-    pairs = torch.empty((L.scorp_gs3d_pairs_bytes(capacity),), dtype=torch.uint8, device=dev)
+    radii, state, pairs, capacity, _ = _preprocess(_GS3D, args, Nt, Ht, W, xyz.device, stream, exact=False)
     _C.check(L.scorp_gs3d_render_score(ctypes.byref(args), _ptr(state), _ptr(pairs), capacity, _ptr(tgt_depth), _ptr(tgt_alpha),
                                        int(rows_per_score), float(scale), _ptr(acc), stream), "scorp_gs3d_render_score")
     PairPolicy.pend(state, Nt, Ht, W)

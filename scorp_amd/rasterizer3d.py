@@ -9,6 +9,7 @@ stream and autograd bookkeeping; every kernel is in the HIP library, reached thr
 """
 import contextlib
 import ctypes
+import math
 import threading
 from typing import NamedTuple
 
@@ -259,151 +260,201 @@ def _inputs_struct(s, means3D, sh, colors_precomp, opacities, scales, rotations,
     return a
 
 
-class _RasterizeGaussians(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings):
-        dev = means3D.device
-        means3D, sh, colors_precomp = _prep(means3D, "means3D"), _prep(sh, "shs"), _prep(colors_precomp, "colors_precomp")
-        opacities, scales, rotations = _prep(opacities, "opacities"), _prep(scales, "scales"), _prep(rotations, "rotations")
-        cov3Ds_precomp = _prep(cov3Ds_precomp, "cov3D_precomp")
-        color, radii, depth, alpha, state, pairs, keep = _forward_common(
-            ctx, settings, means3D, sh, None, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raw=0)
-        ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
-        none = torch.empty(0, device=dev)
-        ctx.save_for_backward(means3D, none if sh is None else sh, none if colors_precomp is None else colors_precomp,
-                              opacities, none if scales is None else scales, none if rotations is None else rotations,
-                              none if cov3Ds_precomp is None else cov3Ds_precomp, state, pairs, *keep)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
-        L = _C.lib()
-        means3D, sh, colors_precomp, opacities, scales, rotations, cov3D, state, pairs, bg, vm, pm, cp = ctx.saved_tensors
-        has_sh, has_col, has_sr, has_cov = ctx.has
-        sh = sh if has_sh else None
-        colors_precomp = colors_precomp if has_col else None
-        scales, rotations = (scales, rotations) if has_sr else (None, None)
-        cov3D = cov3D if has_cov else None
-        s = ctx.settings._replace(bg=bg, viewmatrix=vm, projmatrix=pm, campos=cp)
-        keep = []
-        args = _inputs_struct(s, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D, keep)
-        N, dev = means3D.shape[0], means3D.device
-        need = ctx.needs_input_grad  # means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, settings
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        g_means3D = new(N, 3) if need[0] else None
-        g_means2D = new(N, 3) if need[1] else None
-        g_sh = torch.empty_like(sh) if (need[2] and has_sh) else None
-        g_col = new(N, 3) if (need[3] and has_col) else None
-        g_op = torch.empty_like(opacities) if need[4] else None
-        g_sc = new(N, 3) if (need[5] and has_sr) else None
-        g_rot = new(N, 4) if (need[6] and has_sr) else None
-        g_cov = new(N, 6) if (need[7] and has_cov) else None
-        grads = _C.ScorpGs3dGrads()
-        grads.means3D, grads.means2D, grads.shs, grads.colors_precomp = _ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col)
-        grads.opacities, grads.scales, grads.rotations, grads.cov3D_precomp = _ptr(g_op), _ptr(g_sc), _ptr(g_rot), _ptr(g_cov)
-        if grad_color is None:
-            grad_color = torch.zeros((3, int(s.image_height), int(s.image_width)), dtype=torch.float32, device=dev)
-        gc = _prep(grad_color, "grad_color")
-        gd = _prep(grad_depth, "grad_depth") if grad_depth is not None else None
-        ga = _prep(grad_alpha, "grad_alpha") if grad_alpha is not None else None
-        scratch_bytes = L.scorp_gs3d_backward_scratch_bytes_ex(N, int(s.image_width), int(s.image_height), ctx.capacity, ctx.backward_flags)
-        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
-        _C.check(L.scorp_gs3d_backward_ex(ctypes.byref(args), _ptr(state), _ptr(pairs), ctx.capacity, _ptr(gc), _ptr(gd),
-                                          _ptr(ga), ctypes.byref(grads), _ptr(scratch), scratch_bytes, ctx.backward_flags,
-                                          _stream()),
-                 "scorp_gs3d_backward_ex")
-        return g_means3D, g_means2D, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None
+class _Kind(NamedTuple):
+    """What the 3DGS and the 2DGS rasterizer do differently; everything else about issuing a view is shared.  The entry
+    points are names in libscorp_gs.so."""
+    state_bytes: str
+    preprocess: str
+    render: str
+    render_image: str               # the render that leaves no state for a backward pass
+    backward_ex: str
+    backward_scratch_bytes_ex: str
+    maps: tuple                     # channels of the [c,H,W] maps after the colour, in the entry points' order
+    grad_widths: dict               # columns of the [N, c] gradients (the others are shaped like their leaf)
+    materialize_grads: bool         # False: outputs nobody used arrive in backward as None (the kernels skip those terms)
+    flags_mask: int                 # backward flags the kind passes on
+    keeps_last_forward: bool        # forwards set LAST_FORWARD under KEEP_LAST_FORWARD
 
 
-def _forward_common(ctx, settings, means3D, sh, sh_rest, colors_precomp, opacities, scales, rotations, cov3D, raw):
-    """Shared by the two autograd Functions: allocate outputs + workspaces, run preprocess / render."""
+def _grad_widths(**kind_widths):
+    return {"means3D": 3, "colors_precomp": 3, "rotations": 4, **kind_widths}
+
+
+_GS3D = _Kind("scorp_gs3d_state_bytes", "scorp_gs3d_preprocess", "scorp_gs3d_render", "scorp_gs3d_render_image",
+              "scorp_gs3d_backward_ex", "scorp_gs3d_backward_scratch_bytes_ex", maps=(1, 1),   # depth, alpha
+              grad_widths=_grad_widths(scales=3, cov3D_precomp=6), materialize_grads=False, flags_mask=~0,
+              keeps_last_forward=True)
+_GS2D = _Kind("scorp_gs2d_state_bytes", "scorp_gs2d_preprocess", "scorp_gs2d_render", "scorp_gs2d_render_image",
+              "scorp_gs2d_backward_ex", "scorp_gs2d_backward_scratch_bytes_ex", maps=(7,),     # allmap
+              grad_widths=_grad_widths(scales=2, cov3D_precomp=9), materialize_grads=True,
+              flags_mask=~_C.BACKWARD_SCRATCH_ZEROED, keeps_last_forward=False)
+
+# The leaves of the two autograd Functions in `apply` order, means2D (a gradient sink only) left out: the ScorpGs3dGrads
+# field each gradient goes to.  The stock leaves are named by their fields, the raw ones by the model's leaves.
+_STOCK_FIELDS = ("means3D", "shs", "colors_precomp", "opacities", "scales", "rotations", "cov3D_precomp")
+_RAW_FIELDS = ("means3D", "shs", "shs_rest", "opacities", "scales", "rotations")
+_RAW_NAMES = ("means3D", "features_dc", "features_rest", "opacity", "scaling", "rotation")
+
+
+def _raw_inputs(settings, pc, keep):
+    """A model's raw leaves as the library reads them: (the leaves xyz + pc.raw_leaves(), their prepped tensors, the
+    ScorpGs3dInputs with raw_params = 7)."""
+    leaves = (pc.get_xyz, *pc.raw_leaves())
+    t = [_prep(x.detach(), n) for x, n in zip(leaves, _RAW_NAMES)]
+    return leaves, t, _inputs_struct(settings, t[0], t[1], None, t[3], t[4], t[5], None, keep, t[2], 7)
+
+
+def _camera_settings(camera, bg, scale_modifier, sh_degree, debug=False):
+    """The rasterizer settings of one camera at its current resolution (gaussian_renderer/__init__.py:45-58)."""
+    w, h = camera.resolution
+    return GaussianRasterizationSettings(
+        image_height=int(h), image_width=int(w), tanfovx=math.tan(camera.FoVx * 0.5),
+        tanfovy=math.tan(camera.FoVy * 0.5), bg=bg, scale_modifier=scale_modifier,
+        viewmatrix=camera.world_view_transform, projmatrix=camera.full_proj_transform, sh_degree=sh_degree,
+        campos=camera.camera_center, prefiltered=False, debug=debug)
+
+
+def _new_grads(kind, fields, t, want):
+    """Gradient buffers of the prepped leaves `t` (ScorpGs3dGrads `fields`), None where not wanted: [N, width] for
+    positions, colours, scales, rotations and covariances, the leaf's own shape for SH and opacity."""
+    widths = kind.grad_widths
+    g = []
+    for f, x, w in zip(fields, t, want):
+        g.append(None if not w or x is None else x.new_empty((x.shape[0], widths[f])) if f in widths else torch.empty_like(x))
+    return g
+
+
+def _grads_struct(fields, g, g_means2D):
+    grads = _C.ScorpGs3dGrads()
+    grads.means2D = _ptr(g_means2D)
+    for f, x in zip(fields, g):
+        setattr(grads, f, _ptr(x))
+    return grads
+
+
+def _preprocess(kind, args, N, H, W, dev, stream, exact, log=False):
+    """Preprocess one launch set and size its pair buffer.  `exact`: from the pair count read back (8 bytes D2H);
+    otherwise from PairPolicy's reservation, and the caller queues the view for drain() once it has rendered.  `log`:
+    note the exact count in LAST_NUM_PAIRS_LOG.  Returns (radii, state, pairs, capacity, exact pair count or None)."""
     L = _C.lib()
-    dev = means3D.device
-    N, H, W = means3D.shape[0], int(settings.image_height), int(settings.image_width)
-    keep = []
-    args = _inputs_struct(settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D, keep, sh_rest, raw)
-    color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-    depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-    alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((N,), dtype=torch.int32, device=dev)
-    state_bytes = L.scorp_gs3d_state_bytes(N, W, H)
+    state_bytes = getattr(L, kind.state_bytes)(N, W, H)
     state = torch.empty(state_bytes, dtype=torch.uint8, device=dev)
-    stream = _stream()
-    _C.check(L.scorp_gs3d_preprocess(ctypes.byref(args), _ptr(radii), _ptr(state), state_bytes, stream), "scorp_gs3d_preprocess")
-    if PairPolicy.mode == "exact":
+    _C.check(getattr(L, kind.preprocess)(ctypes.byref(args), _ptr(radii), _ptr(state), state_bytes, stream), kind.preprocess)
+    num_pairs = None
+    if exact:
         n = ctypes.c_uint64(0)
         _C.check(L.scorp_gs3d_num_pairs(_ptr(state), stream, ctypes.byref(n)), "scorp_gs3d_num_pairs")
-        capacity = max(int(n.value), 1)
-        LAST_NUM_PAIRS_LOG.append(int(n.value))
-        del LAST_NUM_PAIRS_LOG[:-64]
+        num_pairs = int(n.value)
+        capacity = max(num_pairs, 1)
+        if log:
+            LAST_NUM_PAIRS_LOG.append(num_pairs)
+            del LAST_NUM_PAIRS_LOG[:-64]
     else:
         capacity = PairPolicy.capacity(N, H, W)
     pairs = torch.empty(L.scorp_gs3d_pairs_bytes(capacity), dtype=torch.uint8, device=dev)
+    return radii, state, pairs, capacity, num_pairs
+
+
+def _forward(ctx, kind, raw, settings, leaves):
+    """Forward of both autograd Functions: allocate outputs + workspaces, run preprocess / render, save for backward.
+    Returns (color, radii, *maps)."""
+    t = list(map(_prep, leaves, _RAW_NAMES if raw else _STOCK_FIELDS))
+    keep = []
+    if raw:   # activations fused into the kernels
+        args = _inputs_struct(settings, t[0], t[1], None, t[3], t[4], t[5], None, keep, t[2], 7)
+    else:
+        args = _inputs_struct(settings, *t, keep)
+    dev = t[0].device
+    N, H, W = t[0].shape[0], int(settings.image_height), int(settings.image_width)
+    stream = _stream()
+    exact = PairPolicy.mode == "exact"
+    # the outputs first: in "exact" mode _preprocess waits for the pair count, and what is left after it is on the
+    # critical path
+    color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    maps = []
+    for c in kind.maps:
+        maps.append(torch.empty((c, H, W), dtype=torch.float32, device=dev))
+    radii, state, pairs, capacity, _ = _preprocess(kind, args, N, H, W, dev, stream, exact, log=True)
     # nothing to differentiate (the calls the reference makes under torch.no_grad()): the image-only render, which
     # leaves no state for a backward pass
-    fn = L.scorp_gs3d_render if want_backward(ctx) else L.scorp_gs3d_render_image
-    _C.check(fn(ctypes.byref(args), _ptr(state), _ptr(pairs), capacity, _ptr(color), _ptr(depth), _ptr(alpha), stream),
-             "scorp_gs3d_render")
-    if PairPolicy.mode != "exact":
+    fn = kind.render if want_backward(ctx) else kind.render_image
+    _C.check(getattr(_C.lib(), fn)(ctypes.byref(args), _ptr(state), _ptr(pairs), capacity, _ptr(color), *map(_ptr, maps),
+                                   stream), fn)
+    if not exact:
         PairPolicy.pend(state, N, H, W)   # what drain() will look at: a copy of the StateHeader the render just filled in
-    if KEEP_LAST_FORWARD:
+    if kind.keeps_last_forward and KEEP_LAST_FORWARD:
         global LAST_FORWARD
         LAST_FORWARD = (state, N, W, H)
-    ctx.settings, ctx.capacity = settings, capacity
-    ctx.backward_flags = _backward_flags()
-    ctx.set_materialize_grads(False)   # unused outputs arrive as None in backward: the kernels skip those terms
-    return color, radii, depth, alpha, state, pairs, keep
+    # the backward reuses `args`: every tensor it points into is saved below (None leaves stay None)
+    ctx.kind, ctx.raw, ctx.args, ctx.size, ctx.capacity = kind, raw, args, (N, W, H), capacity
+    # backward_precision(...) / SCORP_BACKWARD_DETERMINISTIC: fixed when the forward is issued
+    ctx.backward_flags = _backward_flags() & kind.flags_mask
+    ctx.set_materialize_grads(kind.materialize_grads)
+    ctx.save_for_backward(*t, state, pairs, *keep)
+    ctx.mark_non_differentiable(radii)
+    return (color, radii, *maps)
 
 
-class _RasterizeGaussiansRaw(torch.autograd.Function):
+def _backward(ctx, grad_color, grad_maps):
+    """Backward of both autograd Functions: (the means2D gradient, the leaves' gradients in `apply` order)."""
+    kind, raw, (N, W, H) = ctx.kind, ctx.raw, ctx.size
+    fields = _RAW_FIELDS if raw else _STOCK_FIELDS
+    n = len(fields)
+    saved = ctx.saved_tensors   # (raises if a saved tensor was modified in place since the forward)
+    t, state, pairs = saved[:n], saved[n], saved[n + 1]
+    dev = state.device
+    need = (ctx.needs_input_grad[0],) + ctx.needs_input_grad[2:1 + n]   # (means2D is [1])
+    want = list(need)
+    if raw:
+        want[1] = want[2] = need[1] or need[2]   # the SH gradient is written as a whole
+    g = _new_grads(kind, fields, t, want)
+    g_means2D = torch.empty((N, 3), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+    grads = _grads_struct(fields, g, g_means2D)
+    if grad_color is None:
+        grad_color = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
+    gc = _prep(grad_color, "grad_color")
+    gm = []
+    for x in grad_maps:
+        gm.append(None if x is None else _prep(x, "grad"))
+    L = _C.lib()
+    scratch_bytes = getattr(L, kind.backward_scratch_bytes_ex)(N, W, H, ctx.capacity, ctx.backward_flags)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+    _C.check(getattr(L, kind.backward_ex)(ctypes.byref(ctx.args), _ptr(state), _ptr(pairs), ctx.capacity, _ptr(gc),
+                                          *map(_ptr, gm), ctypes.byref(grads), _ptr(scratch), scratch_bytes,
+                                          ctx.backward_flags, _stream()),
+             kind.backward_ex)
+    if raw:   # only the SH gradients that were asked for
+        g[1], g[2] = g[1] if need[1] else None, g[2] if need[2] else None
+    return g_means2D, g
+
+
+class _Rasterize(torch.autograd.Function):
+    """The rasterizer of `kind` (_GS3D, _GS2D) on the stock inputs: (color, radii, *the kind's maps)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings, kind):
+        return _forward(ctx, kind, False, settings, (means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp))
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, *grad_maps):
+        g_means2D, g = _backward(ctx, grad_color, grad_maps)
+        return (g[0], g_means2D, *g[1:], None, None)
+
+
+class _RasterizeRaw(torch.autograd.Function):
     """Same rasterizer on the GaussianModel's RAW storage (logit opacity, log scale, un-normalised quaternion,
     _features_dc / _features_rest kept apart): the activations of gaussian_model.py:126-146 and the SH concat run
     inside the per-Gaussian kernels, and the gradients come back w.r.t. the raw leaves."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, settings):
-        means3D, f_dc, f_rest = _prep(means3D, "means3D"), _prep(f_dc, "features_dc"), _prep(f_rest, "features_rest")
-        opacity_raw, scaling_raw, rotation_raw = _prep(opacity_raw, "opacity"), _prep(scaling_raw, "scaling"), _prep(rotation_raw, "rotation")
-        color, radii, depth, alpha, state, pairs, keep = _forward_common(
-            ctx, settings, means3D, f_dc, f_rest, None, opacity_raw, scaling_raw, rotation_raw, None, raw=7)
-        ctx.save_for_backward(means3D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, state, pairs, *keep)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, alpha
+    def forward(ctx, means3D, means2D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, settings, kind):
+        return _forward(ctx, kind, True, settings, (means3D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw))
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
-        L = _C.lib()
-        means3D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, state, pairs, bg, vm, pm, cp = ctx.saved_tensors
-        s = ctx.settings._replace(bg=bg, viewmatrix=vm, projmatrix=pm, campos=cp)
-        keep = []
-        args = _inputs_struct(s, means3D, f_dc, None, opacity_raw, scaling_raw, rotation_raw, None, keep, f_rest, 7)
-        N, dev = means3D.shape[0], means3D.device
-        need = ctx.needs_input_grad
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        g_means3D = new(N, 3) if need[0] else None
-        g_means2D = new(N, 3) if need[1] else None
-        want_sh = need[2] or need[3]
-        g_dc = torch.empty_like(f_dc) if want_sh else None
-        g_rest = torch.empty_like(f_rest) if want_sh else None
-        g_op = torch.empty_like(opacity_raw) if need[4] else None
-        g_sc = new(N, 3) if need[5] else None
-        g_rot = new(N, 4) if need[6] else None
-        grads = _C.ScorpGs3dGrads()
-        grads.means3D, grads.means2D, grads.shs, grads.shs_rest = _ptr(g_means3D), _ptr(g_means2D), _ptr(g_dc), _ptr(g_rest)
-        grads.opacities, grads.scales, grads.rotations = _ptr(g_op), _ptr(g_sc), _ptr(g_rot)
-        if grad_color is None:
-            grad_color = torch.zeros((3, int(s.image_height), int(s.image_width)), dtype=torch.float32, device=dev)
-        gc = _prep(grad_color, "grad_color")
-        gd = _prep(grad_depth, "grad_depth") if grad_depth is not None else None
-        ga = _prep(grad_alpha, "grad_alpha") if grad_alpha is not None else None
-        scratch_bytes = L.scorp_gs3d_backward_scratch_bytes_ex(N, int(s.image_width), int(s.image_height), ctx.capacity, ctx.backward_flags)
-        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
-        _C.check(L.scorp_gs3d_backward_ex(ctypes.byref(args), _ptr(state), _ptr(pairs), ctx.capacity, _ptr(gc), _ptr(gd),
-                                          _ptr(ga), ctypes.byref(grads), _ptr(scratch), scratch_bytes, ctx.backward_flags,
-                                          _stream()),
-                 "scorp_gs3d_backward_ex")
-        return (g_means3D, g_means2D, g_dc if need[2] else None, g_rest if need[3] else None, g_op, g_sc, g_rot, None)
+    def backward(ctx, grad_color, grad_radii, *grad_maps):
+        g_means2D, g = _backward(ctx, grad_color, grad_maps)
+        return (g[0], g_means2D, *g[1:], None, None)
 
 
 def want_backward(ctx):
@@ -415,13 +466,13 @@ def want_backward(ctx):
 
 def rasterize_gaussians_raw(means3D, means2D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings):
     _tls.grad_mode = torch.is_grad_enabled()
-    return _RasterizeGaussiansRaw.apply(means3D, means2D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings)
+    return _RasterizeRaw.apply(means3D, means2D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings, _GS3D)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
     _tls.grad_mode = torch.is_grad_enabled()
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings)
+    return _Rasterize.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                            raster_settings, _GS3D)
 
 
 class GaussianRasterizer(nn.Module):

@@ -4,16 +4,15 @@ Same signature, same branches (`pipe.compute_cov3D_python`, `pipe.convert_SHs_py
 six-key result dict, same depth normalisation (`render_depth = depth / alpha`, NaN -> 0).  The only deliberate
 difference: tensors are created on `pc.get_xyz.device` instead of the literal "cuda".
 """
-import math
-
 import torch
 
-from .rasterizer3d import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw, render_tail
+# GaussianRasterizationSettings: kept as a name of this module (re-exported)
+from .rasterizer3d import (GaussianRasterizationSettings, GaussianRasterizer, _camera_settings,  # noqa: F401
+                           rasterize_gaussians_raw, render_tail)
 from .sh import eval_sh
 
 
 _ZEROS = {}
-
 
 
 def _fused_activations(pipe, pc):
@@ -23,6 +22,7 @@ def _fused_activations(pipe, pc):
     if flag is None:
         return hasattr(pc, "raw_leaves") and getattr(pc, "stock_activations", lambda: False)()
     return bool(flag) and hasattr(pc, "raw_leaves")
+
 
 def _grad_sink(xyz, requires_grad=True):
     """A fresh leaf of zeros shaped like xyz (the screen-space gradient sink) over a cached, never-written storage."""
@@ -45,14 +45,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     # densifies then and nobody reads the screen-space gradient (post_refine_gs.py:99,178-180 are commented out), and
     # without it the backward only has colour gradients to produce and takes its colour-only path.
     screenspace_points = _grad_sink(xyz, xyz.requires_grad)
-    tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
-    tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
-    w, h = viewpoint_camera.resolution
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(h), image_width=int(w), tanfovx=tanfovx, tanfovy=tanfovy, bg=bg_color,
-        scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
-        campos=viewpoint_camera.camera_center, prefiltered=False, debug=bool(getattr(pipe, "debug", False)))
+    raster_settings = _camera_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree,
+                                       debug=bool(getattr(pipe, "debug", False)))
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
 
     # Fast path of the build's own harnesses: hand the model's raw leaves to the kernels (activations + SH concat fused

@@ -5,18 +5,16 @@ flavour of `GaussianModel` (gs2dgs/scene/gaussian_model.py: 2-D scales :49,136, 
 Result dict keys as the reference returns them: render, viewspace_points, visibility_filter, radii, render_alpha,
 render_normal (rotated to world space), render_dist, render_depth (= surf_depth), surf_normal.
 """
-import math
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .gaussian_model import GaussianModel, build_rotation, inverse_sigmoid
 from .rasterizer2d import GaussianRasterizer, rasterize_surfels_raw, surfel_maps, surfel_regularizer_losses
-from .rasterizer3d import GaussianRasterizationSettings
-from .renderer import _fused_activations
+# GaussianRasterizationSettings: kept as a name of this module (re-exported)
+from .rasterizer3d import GaussianRasterizationSettings, _camera_settings  # noqa: F401
+from .renderer import _fused_activations, _grad_sink
 from .sh import RGB2SH, eval_sh
-
 
 
 def _camera_rays(view, dev):
@@ -62,34 +60,14 @@ def depth_to_normal(view, depth):
     return output
 
 
-_ZEROS = {}
-
-
-def _grad_sink(xyz):
-    """A fresh leaf of zeros shaped like xyz (the screen-space gradient sink) over a cached, never-written storage."""
-    key = (xyz.shape[0], xyz.dtype, xyz.device)
-    z = _ZEROS.get(key)
-    if z is None:
-        if len(_ZEROS) > 8:
-            _ZEROS.clear()
-        z = _ZEROS[key] = torch.zeros_like(xyz, requires_grad=False)
-    return z.detach().requires_grad_(True)
-
-
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None):
     xyz = pc.get_xyz
     # gradient sink for the screen-space means; the reference builds it as `zeros_like(...) + 0` with retain_grad()
     # (gaussian_renderer/__init__.py:39-43) — a leaf with requires_grad gives the caller the same `.grad` without the
     # extra 12 MB add kernel per view; the zeros themselves are shared between views (nothing ever writes them), so
     # not even a fill kernel runs: every view gets a fresh leaf over the same storage
-    screenspace_points = _grad_sink(xyz)
-    tanfovx, tanfovy = math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5)
-    w, h = viewpoint_camera.resolution
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(h), image_width=int(w), tanfovx=tanfovx, tanfovy=tanfovy, bg=bg_color,
-        scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
-        campos=viewpoint_camera.camera_center, prefiltered=False, debug=False)
+    screenspace_points = _grad_sink(xyz, True)
+    raster_settings = _camera_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree)
 
     fused = (override_color is None and _fused_activations(pipe, pc)
              and not getattr(pipe, "compute_cov3D_python", False))

@@ -14,19 +14,100 @@ resolution, stream), verified by `PairPolicy.drain()`.  The view's overflow word
 densification statistics with it, so a view that overflowed its reservation changes nothing.
 """
 import ctypes
-import math
 
 import torch
 
 from . import _C
-from .rasterizer3d import GaussianRasterizationSettings, PairPolicy, _backward_flags, _inputs_struct, _prep, _ptr, _stream
+# GaussianRasterizationSettings: kept as a name of this module (re-exported)
+from .rasterizer3d import (_GS2D, _GS3D, _RAW_FIELDS, GaussianRasterizationSettings, PairPolicy,  # noqa: F401
+                           _backward_flags, _camera_settings, _grads_struct, _prep, _raw_inputs, _stream)
 
 
-def _accumulate(p, g):
-    if p.grad is None:
-        p.grad = g
-    else:
-        p.grad += g
+class _View:
+    """What train_view and train_view2d share: the model's raw leaves as the library reads them, the rasterizer's
+    buffers (pair buffer sized by PairPolicy's reservation, no host synchronisation), the loss and backward workspaces,
+    the fused optimizer step if it can be taken, and the gradient buffers.  `fill(v)` enters them into the caller's
+    Scorp*TrainView, which the caller completes and issues."""
+
+    def __init__(self, kind, name, camera, pc, bg_color, gt_image, mask, scaling_modifier, optimizer, stats,
+                 grad_out=None, debug=False):
+        L = _C.lib()
+        xyz = pc.get_xyz
+        if not xyz.is_cuda:
+            raise RuntimeError(f"{name} needs GPU tensors (scorp_amd has no CPU path)")
+        settings = _camera_settings(camera, bg_color, scaling_modifier, pc.active_sh_degree, debug)
+        self.keep = []
+        self.leaves, t, self.args = _raw_inputs(settings, pc, self.keep)
+        dev, W, H, N = xyz.device, settings.image_width, settings.image_height, xyz.shape[0]
+        self.dev, self.W, self.H, self.N = dev, W, H, N
+        self.gt = _prep(gt_image, "gt_image")
+        self.mask = None if mask is None else _prep(mask.expand(1, H, W), "mask")
+        new = self.new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+        self.color, self.grad_color = new((3, H, W)), new((3, H, W))
+        self.radii = new((N,), torch.int32)
+        state_bytes = getattr(L, kind.state_bytes)(N, W, H)
+        self.state = new((state_bytes,), torch.uint8)
+        capacity = PairPolicy.capacity(N, H, W)
+        self.pairs = new((L.scorp_gs3d_pairs_bytes(capacity),), torch.uint8)
+        ws_bytes = L.scorp_loss_workspace_bytes(3, H, W)
+        self.ws = new((ws_bytes,), torch.uint8)
+        # rasterizer3d.backward_precision(...) / SCORP_BACKWARD_DETERMINISTIC reach the one-call views too
+        flags = _backward_flags() & kind.flags_mask
+        scratch_bytes = getattr(L, kind.backward_scratch_bytes_ex)(N, W, H, capacity, flags)
+        self.scratch = new((scratch_bytes,), torch.uint8)
+        need = [p.requires_grad for p in self.leaves]   # frozen leaves (post-refine) get no gradient buffer: NULL = not wanted
+        need[1] = need[2] = need[1] or need[2]          # the SH gradient is written as a whole
+        self.pack = None
+        if (optimizer is not None and hasattr(optimizer, "fused_view_pack") and t[2].numel() > 0
+                and all(x.data_ptr() == p.data_ptr() for x, p in zip(t, self.leaves))):
+            st = None
+            if stats is not None and xyz.requires_grad:
+                st = tuple(s_ if (s_.dtype == torch.float32 and s_.is_contiguous()) else None for s_ in stats)
+                st = None if any(s_ is None for s_ in st) else st
+            self.pack = optimizer.fused_view_pack(self.leaves, st)
+            stats = st
+        self.fused_step = self.pack is not None
+        self.stats_accumulated = self.fused_step and stats is not None
+        self.g = [torch.empty_like(x) if (n and not self.fused_step) else None for x, n in zip(t, need)]
+        self.grad_out = None if self.fused_step else grad_out
+        if self.grad_out is not None:
+            for k, (x, n, go) in enumerate(zip(t, need, grad_out)):
+                if n and go is not None:
+                    assert go.shape == x.shape and go.dtype == torch.float32 and go.is_contiguous() and go.device == x.device
+                    self.g[k] = go
+        # the screen-space gradient feeds the densification statistics: not produced when the positions are frozen
+        # (renderer.render does the same), which leaves the backward with colour gradients only -> its colour-only path
+        self.g_means2D = new((N, 3)) if (xyz.requires_grad and not self.stats_accumulated) else None
+        self.grads = _grads_struct(_RAW_FIELDS, self.g, self.g_means2D)
+        self.sizes = (state_bytes, capacity, ws_bytes, scratch_bytes, flags)
+
+    def fill(self, v):
+        """The shared fields of `v` (a ScorpGs3dTrainView or ScorpGs2dTrainView)."""
+        state_bytes, capacity, ws_bytes, scratch_bytes, flags = self.sizes
+        v.inputs = ctypes.addressof(self.args)
+        v.out_radii, v.state, v.state_bytes, v.pairs, v.capacity = (self.radii.data_ptr(), self.state.data_ptr(), state_bytes,
+                                                                    self.pairs.data_ptr(), capacity)
+        v.out_color, v.grad_color = self.color.data_ptr(), self.grad_color.data_ptr()
+        v.gt, v.mask = self.gt.data_ptr(), (None if self.mask is None else self.mask.data_ptr())
+        v.loss_workspace, v.loss_workspace_bytes = self.ws.data_ptr(), ws_bytes
+        v.grads, v.backward_scratch, v.backward_scratch_bytes = ctypes.addressof(self.grads), self.scratch.data_ptr(), scratch_bytes
+        v.backward_flags = flags
+        if self.fused_step:
+            v.adam = ctypes.addressof(self.pack[0])
+
+    def accumulate(self):
+        """The gradients into the leaves' .grad (unless the fused step consumed them): accumulated like backward(), or
+        the grad_out tensors made the .grad."""
+        if self.fused_step:
+            return
+        for k, (p, gp) in enumerate(zip(self.leaves, self.g)):
+            if p.requires_grad:
+                if self.grad_out is not None and self.grad_out[k] is not None:
+                    p.grad = gp.view_as(p)      # written in place of whatever was there: the arena is the gradient
+                elif p.grad is None:
+                    p.grad = gp.view_as(p)
+                else:
+                    p.grad += gp.view_as(p)
 
 
 def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2, mask=None, scaling_modifier=1.0,
@@ -47,88 +128,22 @@ def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2,
     parallel.GradArena.views): the gradients are WRITTEN there (not accumulated) and become the leaves' .grad - the
     data-parallel loop's collective then reads them where the kernel left them."""
     L = _C.lib()
-    xyz = pc.get_xyz
-    if not xyz.is_cuda:
-        raise RuntimeError("train_view needs GPU tensors (scorp_amd has no CPU path)")
-    f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw = pc.raw_leaves()
-    leaves = (xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw)
-    dev = xyz.device
-    w, h = viewpoint_camera.resolution
-    W, H, N = int(w), int(h), xyz.shape[0]
-    settings = GaussianRasterizationSettings(
-        image_height=H, image_width=W, tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
-        tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color, scale_modifier=scaling_modifier,
-        viewmatrix=viewpoint_camera.world_view_transform, projmatrix=viewpoint_camera.full_proj_transform,
-        sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center, prefiltered=False,
-        debug=bool(getattr(pipe, "debug", False)))
-    t = [_prep(x.detach(), n) for x, n in zip(leaves, ("means3D", "features_dc", "features_rest", "opacity", "scaling", "rotation"))]
-    keep = []
-    args = _inputs_struct(settings, t[0], t[1], None, t[3], t[4], t[5], None, keep, t[2], 7)
-    gt = _prep(gt_image, "gt_image")
-    if mask is not None:
-        mask = _prep(mask.expand(1, H, W), "mask")
-    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
-    color, depth_raw, alpha, depth = new((3, H, W)), new((1, H, W)), new((1, H, W)), new((1, H, W))
-    radii, visible = new((N,), torch.int32), new((N,), torch.uint8)
-    loss3, grad_color = new((3,)), new((3, H, W))
-    state_bytes = L.scorp_gs3d_state_bytes(N, W, H)
-    state = new((state_bytes,), torch.uint8)
-    capacity = PairPolicy.capacity(N, H, W)
-    pairs = new((L.scorp_gs3d_pairs_bytes(capacity),), torch.uint8)
-    ws_bytes = L.scorp_loss_workspace_bytes(3, H, W)
-    ws = new((ws_bytes,), torch.uint8)
-    flags = _backward_flags()     # rasterizer3d.backward_precision(...) / SCORP_BACKWARD_DETERMINISTIC reach the one-call view too
-    scratch_bytes = L.scorp_gs3d_backward_scratch_bytes_ex(N, W, H, capacity, flags)
-    scratch = new((scratch_bytes,), torch.uint8)
-    need = [p.requires_grad for p in leaves]          # frozen leaves (post-refine) get no gradient buffer: NULL = not wanted
-    need[1] = need[2] = need[1] or need[2]            # the SH gradient is written as a whole
-    pack = None
-    if (optimizer is not None and hasattr(optimizer, "fused_view_pack") and f_rest.numel() > 0
-            and all(x.data_ptr() == p.data_ptr() for x, p in zip(t, leaves))):
-        st = None
-        if stats is not None and xyz.requires_grad:
-            st = tuple(s_ if (s_.dtype == torch.float32 and s_.is_contiguous()) else None for s_ in stats)
-            st = None if any(s_ is None for s_ in st) else st
-        pack = optimizer.fused_view_pack(leaves, st)
-        stats = st
-    fused_step = pack is not None
-    g = [torch.empty_like(x) if (n and not fused_step) else None for x, n in zip(t, need)]
-    if grad_out is not None and not fused_step:
-        for k, (x, n, go) in enumerate(zip(t, need, grad_out)):
-            if n and go is not None:
-                assert go.shape == x.shape and go.dtype == torch.float32 and go.is_contiguous() and go.device == x.device
-                g[k] = go
-    # the screen-space gradient feeds the densification statistics: not produced when the positions are frozen
-    # (renderer.render does the same), which leaves the backward with colour gradients only -> its colour-only path
-    g_means2D = new((N, 3)) if (xyz.requires_grad and not (fused_step and stats is not None)) else None
-    grads = _C.ScorpGs3dGrads()
-    grads.means3D, grads.means2D, grads.shs, grads.shs_rest = _ptr(g[0]), _ptr(g_means2D), _ptr(g[1]), _ptr(g[2])
-    grads.opacities, grads.scales, grads.rotations = _ptr(g[3]), _ptr(g[4]), _ptr(g[5])
+    c = _View(_GS3D, "train_view", viewpoint_camera, pc, bg_color, gt_image, mask, scaling_modifier, optimizer, stats,
+              grad_out, debug=bool(getattr(pipe, "debug", False)))
+    H, W, N = c.H, c.W, c.N
+    depth_raw, alpha, depth = c.new((1, H, W)), c.new((1, H, W)), c.new((1, H, W))
+    visible, loss3 = c.new((N,), torch.uint8), c.new((3,))
+    header = c.new((64,), torch.uint8)                # {pairs needed, overflow, capacity, 0}: written by the scatter kernel
     v = _C.ScorpGs3dTrainView()
-    v.inputs = ctypes.addressof(args)
-    v.out_radii, v.state, v.state_bytes, v.pairs, v.capacity = radii.data_ptr(), state.data_ptr(), state_bytes, pairs.data_ptr(), capacity
-    v.out_color, v.out_depth_raw, v.out_alpha = color.data_ptr(), depth_raw.data_ptr(), alpha.data_ptr()
-    v.out_depth, v.out_visible = depth.data_ptr(), visible.data_ptr()
-    v.gt, v.mask, v.lambda_dssim = gt.data_ptr(), (None if mask is None else mask.data_ptr()), float(lambda_dssim)
-    v.backward_flags = flags
-    v.out_loss3, v.loss_workspace, v.loss_workspace_bytes = loss3.data_ptr(), ws.data_ptr(), ws_bytes
-    v.grad_color, v.grads = grad_color.data_ptr(), ctypes.addressof(grads)
-    v.backward_scratch, v.backward_scratch_bytes = scratch.data_ptr(), scratch_bytes
-    header = new((64,), torch.uint8)                  # {pairs needed, overflow, capacity, 0}: written by the scatter kernel
-    v.out_header = header.data_ptr()
-    if fused_step:
-        v.adam = ctypes.addressof(pack[0])
+    c.fill(v)
+    v.lambda_dssim = float(lambda_dssim)
+    v.out_depth_raw, v.out_alpha, v.out_depth, v.out_visible = depth_raw.data_ptr(), alpha.data_ptr(), depth.data_ptr(), visible.data_ptr()
+    v.out_loss3, v.out_header = loss3.data_ptr(), header.data_ptr()
     _C.check(L.scorp_gs3d_train_view(ctypes.byref(v), _stream()), "scorp_gs3d_train_view")
-    PairPolicy.pend(state, N, H, W, header=header)    # queued for drain(): no copy launch, the state blob is not pinned
-    if not fused_step:
-        for k, (p, gp) in enumerate(zip(leaves, g)):
-            if p.requires_grad:
-                if grad_out is not None and grad_out[k] is not None:
-                    p.grad = gp.view_as(p)      # written in place of whatever was there: the arena is the gradient
-                else:
-                    _accumulate(p, gp.view_as(p))
-    return {"optimizer_stepped": fused_step, "stats_accumulated": fused_step and stats is not None, "render": color, "viewspace_points": _ViewspaceGrad(g_means2D), "visibility_filter": visible.view(torch.bool),
-            "radii": radii, "render_depth": depth, "render_alpha": alpha, "loss": loss3[0], "l1": loss3[1], "ssim": loss3[2],
+    PairPolicy.pend(c.state, N, H, W, header=header)    # queued for drain(): no copy launch, the state blob is not pinned
+    c.accumulate()
+    return {"optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": visible.view(torch.bool),
+            "radii": c.radii, "render_depth": depth, "render_alpha": alpha, "loss": loss3[0], "l1": loss3[1], "ssim": loss3[2],
             # != 0 if this view needed more pairs than were reserved (its images and gradients then come from truncated
             # tile lists): a device word, so the caller can make the optimizer step conditional without a host sync
             "overflow": header.view(torch.int32)[1:2]}
@@ -152,79 +167,23 @@ def train_view2d(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.
     step and the view's densification statistics inside the view, as for `train_view` (ScorpGs2dTrainView.adam)."""
     from .renderer2d import _camera_rays
     L = _C.lib()
-    xyz = pc.get_xyz
-    if not xyz.is_cuda:
-        raise RuntimeError("train_view2d needs GPU tensors (scorp_amd has no CPU path)")
-    f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw = pc.raw_leaves()
-    leaves = (xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw)
-    dev = xyz.device
-    w, h = viewpoint_camera.resolution
-    W, H, N = int(w), int(h), xyz.shape[0]
-    settings = GaussianRasterizationSettings(
-        image_height=H, image_width=W, tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
-        tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color, scale_modifier=scaling_modifier,
-        viewmatrix=viewpoint_camera.world_view_transform, projmatrix=viewpoint_camera.full_proj_transform,
-        sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center, prefiltered=False, debug=False)
-    t = [_prep(x.detach(), n) for x, n in zip(leaves, ("means3D", "features_dc", "features_rest", "opacity", "scaling", "rotation"))]
-    keep = []
-    args = _inputs_struct(settings, t[0], t[1], None, t[3], t[4], t[5], None, keep, t[2], 7)
-    gt = _prep(gt_image, "gt_image")
-    if mask is not None:
-        mask = _prep(mask.expand(1, H, W), "mask")
-    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
-    color, allmap = new((3, H, W)), new((7, H, W))
-    radii = new((N,), torch.int32)
-    loss5, grad_color, grad_allmap = new((5,)), new((3, H, W)), new((7, H, W))
-    state_bytes = L.scorp_gs2d_state_bytes(N, W, H)
-    state = new((state_bytes,), torch.uint8)
-    capacity = PairPolicy.capacity(N, H, W)
-    pairs = new((L.scorp_gs3d_pairs_bytes(capacity),), torch.uint8)
-    ws_bytes = L.scorp_loss_workspace_bytes(3, H, W)
-    ws = new((ws_bytes,), torch.uint8)
+    c = _View(_GS2D, "train_view2d", viewpoint_camera, pc, bg_color, gt_image, mask, scaling_modifier, optimizer, stats)
+    H, W, N = c.H, c.W, c.N
+    allmap, grad_allmap, loss5 = c.new((7, H, W)), c.new((7, H, W)), c.new((5,))
     rws_bytes = L.scorp_gs2d_regularizers_workspace_bytes(W, H)
-    rws = new((rws_bytes,), torch.uint8)
-    flags = _backward_flags() & ~_C.BACKWARD_SCRATCH_ZEROED   # backward_precision(...) reaches the 2DGS one-call view too
-    scratch_bytes = L.scorp_gs2d_backward_scratch_bytes_ex(N, W, H, capacity, flags)
-    scratch = new((scratch_bytes,), torch.uint8)
-    need = [p.requires_grad for p in leaves]
-    need[1] = need[2] = need[1] or need[2]
-    pack = None
-    if (optimizer is not None and hasattr(optimizer, "fused_view_pack") and f_rest.numel() > 0
-            and all(x.data_ptr() == p.data_ptr() for x, p in zip(t, leaves))):
-        st = None
-        if stats is not None and xyz.requires_grad:
-            st = tuple(s_ if (s_.dtype == torch.float32 and s_.is_contiguous()) else None for s_ in stats)
-            st = None if any(s_ is None for s_ in st) else st
-        pack = optimizer.fused_view_pack(leaves, st)
-        stats = st
-    fused_step = pack is not None
-    g = [torch.empty_like(x) if (n and not fused_step) else None for x, n in zip(t, need)]
-    g_means2D = new((N, 3)) if (xyz.requires_grad and not (fused_step and stats is not None)) else None
-    grads = _C.ScorpGs3dGrads()
-    grads.means3D, grads.means2D, grads.shs, grads.shs_rest = _ptr(g[0]), _ptr(g_means2D), _ptr(g[1]), _ptr(g[2])
-    grads.opacities, grads.scales, grads.rotations = _ptr(g[3]), _ptr(g[4]), _ptr(g[5])
-    rays_d, rays_o = _camera_rays(viewpoint_camera, dev)
+    rws = c.new((rws_bytes,), torch.uint8)
+    rays_d, rays_o = _camera_rays(viewpoint_camera, c.dev)
     v = _C.ScorpGs2dTrainView()
-    v.inputs = ctypes.addressof(args)
-    v.out_radii, v.state, v.state_bytes, v.pairs, v.capacity = radii.data_ptr(), state.data_ptr(), state_bytes, pairs.data_ptr(), capacity
-    v.out_color, v.out_allmap = color.data_ptr(), allmap.data_ptr()
-    v.gt, v.mask = gt.data_ptr(), (None if mask is None else mask.data_ptr())
+    c.fill(v)
+    v.out_allmap, v.grad_allmap = allmap.data_ptr(), grad_allmap.data_ptr()
     v.rays_d, v.rays_o = rays_d.data_ptr(), rays_o.data_ptr()
     v.lambda_dssim, v.depth_ratio = float(lambda_dssim), float(getattr(pipe, "depth_ratio", 1.0))
     v.lambda_normal, v.lambda_dist = float(lambda_normal), float(lambda_dist)
     v.out_loss3, v.out_reg2 = loss5.data_ptr(), loss5[3:].data_ptr()
-    v.loss_workspace, v.loss_workspace_bytes, v.reg_workspace, v.reg_workspace_bytes = ws.data_ptr(), ws_bytes, rws.data_ptr(), rws_bytes
-    v.grad_color, v.grad_allmap, v.grads = grad_color.data_ptr(), grad_allmap.data_ptr(), ctypes.addressof(grads)
-    v.backward_scratch, v.backward_scratch_bytes = scratch.data_ptr(), scratch_bytes
-    v.backward_flags = flags
-    if fused_step:
-        v.adam = ctypes.addressof(pack[0])
+    v.reg_workspace, v.reg_workspace_bytes = rws.data_ptr(), rws_bytes
     _C.check(L.scorp_gs2d_train_view(ctypes.byref(v), _stream()), "scorp_gs2d_train_view")
-    header = PairPolicy.pend(state, N, H, W)
-    if not fused_step:
-        for p, gp in zip(leaves, g):
-            if p.requires_grad:
-                _accumulate(p, gp.view_as(p))
-    return {"optimizer_stepped": fused_step, "stats_accumulated": fused_step and stats is not None, "render": color, "allmap": allmap, "viewspace_points": _ViewspaceGrad(g_means2D), "visibility_filter": radii > 0,
-            "radii": radii, "loss": loss5[0] + loss5[3] + loss5[4], "l1": loss5[1], "ssim": loss5[2],
+    header = PairPolicy.pend(c.state, N, H, W)
+    c.accumulate()
+    return {"optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "allmap": allmap, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": c.radii > 0,
+            "radii": c.radii, "loss": loss5[0] + loss5[3] + loss5[4], "l1": loss5[1], "ssim": loss5[2],
             "normal_loss": loss5[3], "dist_loss": loss5[4], "overflow": header.view(torch.int32)[1:2]}
