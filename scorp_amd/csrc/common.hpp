@@ -266,6 +266,7 @@ struct StateLayout {
   // histogram of view v's tiles only: nb blocks PER VIEW and a block-histogram matrix of nb x tiles counters instead of
   // 256 x tiles (38 MB at the align sweep's 15 x 800x800).  Only nb - and with it the size of the last region - depends
   // on views_, so a state buffer sized by the one-view formula on the totals (scorp_gs3d_state_bytes) always suffices.
+  StateLayout() = default;
   StateLayout(int N, int W, int H, bool mode2d = false, int views_ = 1) {
     views = views_ > 1 ? views_ : 1;
     view_n = N / views;
@@ -311,6 +312,7 @@ struct StateLayout {
 // verdict byte per (quad, entry).
 struct PairLayout {
   size_t keys, keys2, hits, list, total;   // keys2: the tile buckets of the two-level binning (keys: its cell buckets)
+  PairLayout() = default;
   explicit PairLayout(uint64_t capacity) {
     size_t c = capacity > 0 ? (size_t)capacity : 1;
     keys = 0;
@@ -339,8 +341,18 @@ struct DetLayout {
     total = off;
   }
 };
+// backward scratch: the deterministic layout, or the accumulator rows alone (N rows of row_floats floats)
+inline size_t backward_scratch_bytes(int N, uint64_t capacity, uint32_t flags, int row_floats) {
+  if (flags & SCORP_BACKWARD_DETERMINISTIC) return DetLayout(N, capacity, row_floats).total;
+  return align_up((size_t)(N > 0 ? N : 1) * row_floats * sizeof(float), 256);
+}
 int launch_pair_base(int N, const BinRec *bin, const uint64_t *tile_mask, uint32_t *block_sums, uint32_t *pair_base,
                      hipStream_t stream);
+// acc[i] = the flagged partial rows of Gaussian i added in a fixed order (gs3d_backward.hip instantiates <16, 10, 16> for
+// 3DGS and <20, 20, 32> for 2DGS)
+template <int kStride, int kUsed, int kLanes>
+void launch_reduce_pair_rows(int N, const uint32_t *pair_base, uint32_t capacity, const uint8_t *row_flags, const float *partial,
+                             float *acc, hipStream_t stream);
 
 // ---- in-library kernel timing (api.hip) ----
 enum KernelId {
@@ -400,6 +412,9 @@ void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L,
 int backward3d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity, const float *dL_dcolor,
                     const float *dL_ddepth, const float *dL_dalpha, const ScorpGs3dGrads *grads, void *scratch,
                     size_t scratch_bytes, uint32_t flags, scorp_stream_t stream, const AdamEpi *adam);
+int preprocess2d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, void *state, size_t state_bytes, scorp_stream_t stream);
+int render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, float *out_color, float *out_allmap,
+                  scorp_stream_t stream, bool for_backward);
 int backward2d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity, const float *dL_dcolor,
                     const float *dL_dallmap, const ScorpGs3dGrads *grads, void *scratch, size_t scratch_bytes, uint32_t flags,
                     scorp_stream_t stream, const AdamEpi *adam);
@@ -434,8 +449,6 @@ __device__ __forceinline__ void adam_st1(float *p, float x) { __builtin_nontempo
 #endif
 
 // ---- binning shared by the 3DGS and 2DGS paths (gs3d_forward.hip) ----
-int copy_tile_lists_raster(const StateLayout &L, const PairLayout &P, const void *state, const void *pairs, uint64_t capacity,
-                           uint32_t num_pairs, uint32_t *tile_start, uint32_t *point_list, hipStream_t stream);
 int bin_count_and_scan(const StateLayout &L, char *state_base, int N, int debug, hipStream_t stream);
 int bin_scatter_and_sort(const StateLayout &L, const PairLayout &P, char *state_base, char *pairs_base, int N,
                          uint32_t capacity, int debug, hipStream_t stream, uint32_t *header_copy = nullptr);
@@ -469,5 +482,131 @@ void set_error(const char *fmt, ...);
       return SCORP_ERR_HIP;                                                                       \
     }                                                                                             \
   } while (0)
+
+// ---- the host pipeline shared by the 3DGS and 2DGS paths (gs3d_forward.hip, and the templates below) ----
+// What differs between the two kinds, apart from the launches each passes in.
+struct GsKind {
+  bool mode2d;          // StateLayout of the 2DGS records and per-pixel state
+  bool stacked_views;   // reads ScorpGs3dInputs.num_views (3DGS); 2DGS ignores the field: one view
+  bool acc_offsets32;   // the blend backward addresses accumulator and partial rows by 32-bit float offsets (else size_t)
+  int acc_stride;       // floats per accumulator row
+  int prof_preprocess, prof_blend_backward, prof_preprocess_backward;
+  void (*reduce_pair_rows)(int N, const uint32_t *pair_base, uint32_t capacity, const uint8_t *row_flags, const float *partial,
+                           float *acc, hipStream_t stream);
+};
+constexpr GsKind kGs3d = {false, true, true, kAccStride, kKPreprocess, kKBlendBackward, kKPreprocessBackward,
+                          launch_reduce_pair_rows<kAccStride, 10, 16>};
+
+// The input checks of every preprocess and render; *views = the views stacked vertically (1 unless K.stacked_views)
+int validate(const GsKind &K, const ScorpGs3dInputs *in, int *views);
+// The state and pair buffers of a render, backward or debug call: non-NULL, 256-byte aligned, at most 2^32 - 1 pairs
+int check_buffers(const void *state, const void *pairs, uint64_t capacity);
+int read_header(const void *state, hipStream_t stream, StateHeader *h);
+
+// A render after render_frame (validate, layouts, buffer check; nothing launched): the caller checks its own outputs, then
+// runs bin_scatter_and_sort and its blend.  V views stacked vertically: N = V x num_gaussians, H = V x image_height.
+struct RenderFrame {
+  int V, N, W, H;
+  uint32_t capacity;
+  StateLayout L;
+  PairLayout P;
+  char *base, *pb;   // the state and pair buffers
+};
+int render_frame(const GsKind &K, const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, bool for_backward,
+                 RenderFrame *f);
+
+// preprocess: the checks, the kind's per-Gaussian launch(L, state_base) under its timer, then the count and scan of the binning
+template <class Launch>
+int preprocess_pass(const GsKind &K, const ScorpGs3dInputs *in, int32_t *out_radii, void *state, size_t state_bytes,
+                    hipStream_t stream, Launch &&launch) {
+  int V;
+  if (int e = validate(K, in, &V)) return e;
+  const int N = V * in->num_gaussians;
+  const StateLayout L(N, in->image_width, V * in->image_height, K.mode2d, V);
+  if (V > 1 && !L.lds_binning) { set_error("num_views > 1: the stacked image has too many tiles"); return SCORP_ERR_INVALID; }
+  if (!state || state_bytes < L.total || ((uintptr_t)state & 255)) {
+    set_error("state buffer NULL, misaligned or too small (%zu < %zu)", state_bytes, L.total);
+    return SCORP_ERR_INVALID;
+  }
+  if (N > 0 && !out_radii) { set_error("out_radii is NULL"); return SCORP_ERR_INVALID; }
+  char *base = (char *)state;
+  if (!L.lds_binning) SCORP_HIP_CHECK(hipMemsetAsync(base + L.tile_count, 0, ((size_t)L.tiles + 1) * 4, stream));
+  if (N > 0) {
+    ProfScope prof(K.prof_preprocess, stream);
+    launch(L, base);
+    SCORP_KERNEL_CHECK("preprocess", in->debug, stream);
+  }
+  return bin_count_and_scan(L, base, N, in->debug, stream);
+}
+
+// backward: the checks; the accumulator rows - cleared for the float atomics (unless SCORP_BACKWARD_SCRATCH_ZEROED says
+// they are), or with SCORP_BACKWARD_DETERMINISTIC one partial row per (pair, 8x8 block) and their ordered sum; between
+// them the kind's blend(L, P, acc, partial, row_flags, pair_base) (the last three NULL unless deterministic) and then
+// per_gaussian(L, acc), each under its timer
+template <class Blend, class PerGaussian>
+int backward_pass(const GsKind &K, const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
+                  const float *dL_dcolor, const ScorpGs3dGrads *grads, void *scratch, size_t scratch_bytes, uint32_t flags,
+                  hipStream_t stream, Blend &&blend, PerGaussian &&per_gaussian) {
+  if (!in || !state || !pairs || !grads || !scratch || !dL_dcolor) { set_error("NULL argument to the backward"); return SCORP_ERR_INVALID; }
+  if (K.stacked_views && in->num_views > 1) { set_error("num_views > 1 is forward only"); return SCORP_ERR_INVALID; }
+  const int N = in->num_gaussians;
+  if (N <= 0) return SCORP_OK;
+  if (int e = check_buffers(state, pairs, capacity)) return e;
+  if (K.acc_offsets32 && (uint64_t)N * K.acc_stride > 0xFFFFFFFFull) {
+    set_error("num_gaussians %d above the %llu the backward supports", N, 0xFFFFFFFFull / K.acc_stride);
+    return SCORP_ERR_INVALID;
+  }
+  const bool det = (flags & SCORP_BACKWARD_DETERMINISTIC) != 0;
+  // (the reduction indexes the partial rows in 32 bits, a 32-bit float offset also counts their floats)
+  if (det && capacity * 4 * (K.acc_offsets32 ? K.acc_stride : 1) > 0xFFFFFFFFull) {
+    set_error("capacity too large for the deterministic backward"); return SCORP_ERR_INVALID;
+  }
+  const size_t need = backward_scratch_bytes(N, capacity, flags, K.acc_stride);
+  if (scratch_bytes < need || ((uintptr_t)scratch & 15)) {
+    set_error("backward scratch too small or misaligned (%zu < %zu)", scratch_bytes, need);
+    return SCORP_ERR_INVALID;
+  }
+  const StateLayout L(N, in->image_width, in->image_height, K.mode2d);
+  const PairLayout P(capacity);
+  const char *base = (const char *)state;
+  float *acc = (float *)scratch, *partial = nullptr;
+  uint8_t *row_flags = nullptr;
+  uint32_t *pair_base = nullptr;
+  if (det) {
+    const DetLayout DL(N, capacity, K.acc_stride);
+    char *p = (char *)scratch;
+    partial = (float *)(p + DL.partial);
+    row_flags = (uint8_t *)(p + DL.flags);
+    pair_base = (uint32_t *)(p + DL.pair_base);
+    SCORP_HIP_CHECK(hipMemsetAsync(row_flags, 0, (size_t)(capacity > 0 ? capacity : 1) * 4, stream));
+    launch_pair_base(N, (const BinRec *)(base + L.bin), (const uint64_t *)(base + L.tile_mask), (uint32_t *)(p + DL.block_sums),
+                     pair_base, stream);
+    SCORP_KERNEL_CHECK("pair_base", in->debug, stream);
+  } else if (!(flags & SCORP_BACKWARD_SCRATCH_ZEROED)) {
+    SCORP_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)N * K.acc_stride * sizeof(float), stream));
+  }
+  {
+    ProfScope prof(K.prof_blend_backward, stream);
+    blend(L, P, acc, partial, row_flags, pair_base);
+  }
+  SCORP_KERNEL_CHECK("blend_backward", in->debug, stream);
+  if (det) {
+    K.reduce_pair_rows(N, pair_base, (uint32_t)capacity, row_flags, partial, acc, stream);
+    SCORP_KERNEL_CHECK("reduce_pair_rows", in->debug, stream);
+  }
+  {
+    ProfScope prof(K.prof_preprocess_backward, stream);
+    per_gaussian(L, acc);
+  }
+  SCORP_KERNEL_CHECK("preprocess_backward", in->debug, stream);
+  return SCORP_OK;
+}
+
+// debug entry points: the N records (rec_bytes each) and BinRecs of a preprocessed state copied to host memory, one block
+// that *rec points to and the caller frees (NULL when N <= 0); the tile lists in raster order, for both kinds
+int copy_geom_to_host(const void *state, const StateLayout &L, int N, size_t rec_bytes, void **rec, const BinRec **bin,
+                      hipStream_t stream);
+int debug_tiles(bool mode2d, const void *state, const void *pairs, uint64_t capacity, int N, int W, int H, uint32_t *tile_start,
+                uint32_t *point_list, hipStream_t stream);
 
 }  // namespace scorp

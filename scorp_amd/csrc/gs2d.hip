@@ -602,7 +602,7 @@ constexpr int k2BChunk = SCORP_2D_BCHUNK;   // hits staged per chunk: 32 (the st
 //     form pays 8 of them per hit where the split form pays 2 fp16 ones, and saves the split's ~40 instructions.
 //   * kDet (SCORP_BACKWARD_DETERMINISTIC): the twenty sums of a (block, hit) leave as one plain row
 //     partial[4 * pair + block] (pair = the (surfel, tile) pair's ordinal in surfel-major order, gs3d_backward.hip) with a
-//     flag byte; reduce_pair_rows2d_kernel adds a surfel's rows in a fixed order.  No float atomics.
+//     flag byte; reduce_pair_rows_kernel (gs3d_backward.hip) adds a surfel's rows in a fixed order.  No float atomics.
 template <bool kHasMap, bool kExact = false, bool kDet = false>
 __global__ void __launch_bounds__(64, SCORP_2D_BWAVES)
 blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ point_list,
@@ -1219,32 +1219,6 @@ preprocess2d_backward_kernel(Pg2Args a, const Surfel *__restrict__ rec, const Bi
   preprocess2d_backward_body<DEG, SPLIT, false>(a, s_sh, rec, bin, acc, g, ad);
 }
 
-// Deterministic mode: the rows of one surfel are contiguous - partial[4 * pair_base[i] ... 4 * pair_base[i + 1]) - so the
-// ordered per-surfel sum is a streaming read (gs3d_backward.hip has the 3-D twin).  Thirty-two lanes per surfel (lane = float
-// of a row, twenty used) add the flagged rows in the fixed order pair, block - sixteen rows in flight per step.
-__global__ void __launch_bounds__(256)
-reduce_pair_rows2d_kernel(int N, const uint32_t *__restrict__ pair_base, uint32_t capacity, const uint8_t *__restrict__ row_flags,
-                          const float *__restrict__ partial, float *__restrict__ acc) {
-  const int i = blockIdx.x * 8 + (threadIdx.x >> 5), col = threadIdx.x & 31;
-  if (i >= N || col >= kAcc2Stride) return;
-  const uint32_t r0 = min(pair_base[i], capacity) * 4u, r1 = min(pair_base[i + 1], capacity) * 4u;
-  float sum = 0.0f;
-  for (uint32_t r = r0; r < r1; r += 16) {
-    uint32_t f[4];
-#pragma unroll
-    for (int p = 0; p < 4; p++) f[p] = r + 4 * p < r1 ? *reinterpret_cast<const uint32_t *>(row_flags + r + 4 * p) : 0u;
-    float v[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const bool on = (f[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-      v[k] = on ? partial[(size_t)(r + k) * kAcc2Stride + col] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) sum += v[k];   // (an absent row adds an exact zero)
-  }
-  acc[(size_t)i * kAcc2Stride + col] = sum;
-}
-
 Pg2Args make_args2(const ScorpGs3dInputs *in, const StateLayout &L) {
   Pg2Args a;
   a.N = in->num_gaussians; a.K = in->sh_coeffs; a.W = in->image_width; a.H = in->image_height;
@@ -1256,24 +1230,8 @@ Pg2Args make_args2(const ScorpGs3dInputs *in, const StateLayout &L) {
   return a;
 }
 
-int validate2(const ScorpGs3dInputs *in) {
-  if (!in) { set_error("inputs is NULL"); return SCORP_ERR_INVALID; }
-  if (in->num_gaussians < 0 || in->image_width <= 0 || in->image_height <= 0) { set_error("bad sizes"); return SCORP_ERR_INVALID; }
-  if (in->num_gaussians > 0) {
-    if (!in->means3D || !in->opacities) { set_error("means3D / opacities is NULL"); return SCORP_ERR_INVALID; }
-    if ((in->shs == nullptr) == (in->colors_precomp == nullptr)) { set_error("provide exactly one of shs / colors_precomp"); return SCORP_ERR_INVALID; }
-    const bool sr = in->scales != nullptr && in->rotations != nullptr;
-    if (sr == (in->cov3D_precomp != nullptr)) { set_error("provide exactly one of scales+rotations / precomputed transform"); return SCORP_ERR_INVALID; }
-    if (in->shs && (in->sh_degree < 0 || in->sh_degree > 3 || in->sh_coeffs < (in->sh_degree + 1) * (in->sh_degree + 1))) {
-      set_error("bad sh_degree / sh_coeffs"); return SCORP_ERR_INVALID;
-    }
-  }
-  if (!in->bg || !in->viewmatrix || !in->projmatrix || !in->campos) { set_error("bg / matrices / campos is NULL"); return SCORP_ERR_INVALID; }
-  if ((((uintptr_t)in->shs | (uintptr_t)in->shs_rest | (uintptr_t)in->rotations) & 15) != 0) {
-    set_error("shs / shs_rest / rotations must be 16-byte aligned"); return SCORP_ERR_INVALID;
-  }
-  return SCORP_OK;
-}
+constexpr GsKind kGs2d = {true, false, false, kAcc2Stride, kKPreprocess2d, kKBlendBackward2d, kKPreprocessBackward2d,
+                          launch_reduce_pair_rows<kAcc2Stride, kAcc2Stride, 32>};
 
 }  // namespace
 }  // namespace scorp
@@ -1281,60 +1239,44 @@ int validate2(const ScorpGs3dInputs *in) {
 using namespace scorp;
 
 extern "C" size_t scorp_gs2d_state_bytes(int32_t N, int32_t W, int32_t H) { return StateLayout(N, W, H, true).total; }
-extern "C" size_t scorp_gs2d_backward_scratch_bytes(int32_t N) {
-  return align_up((size_t)(N > 0 ? N : 1) * kAcc2Stride * sizeof(float), 256);
-}
+extern "C" size_t scorp_gs2d_backward_scratch_bytes(int32_t N) { return backward_scratch_bytes(N, 0, 0u, kAcc2Stride); }
 extern "C" size_t scorp_gs2d_backward_scratch_bytes_ex(int32_t N, int32_t W, int32_t H, uint64_t capacity, uint32_t flags) {
   (void)W; (void)H;
-  if (flags & SCORP_BACKWARD_DETERMINISTIC) return DetLayout(N, capacity, kAcc2Stride).total;
-  return scorp_gs2d_backward_scratch_bytes(N);
+  return backward_scratch_bytes(N, capacity, flags, kAcc2Stride);
 }
 
 extern "C" int scorp_gs2d_preprocess(const ScorpGs3dInputs *in, int32_t *out_radii, void *state, size_t state_bytes,
-                                     scorp_stream_t stream_) {
-  if (int e = validate2(in)) return e;
-  hipStream_t stream = (hipStream_t)stream_;
-  const int N = in->num_gaussians;
-  const StateLayout L(N, in->image_width, in->image_height, true);
-  if (!state || state_bytes < L.total || ((uintptr_t)state & 255)) { set_error("state buffer NULL, misaligned or too small"); return SCORP_ERR_INVALID; }
-  if (N > 0 && !out_radii) { set_error("out_radii is NULL"); return SCORP_ERR_INVALID; }
-  char *base = (char *)state;
-  uint32_t *tile_count = (uint32_t *)(base + L.tile_count);
-  if (!L.lds_binning) SCORP_HIP_CHECK(hipMemsetAsync(tile_count, 0, ((size_t)L.tiles + 1) * 4, stream));
-  if (N > 0) {
-    ProfScope prof(kKPreprocess2d, stream);
-    const Pg2Args a = make_args2(in, L);
-    const dim3 grid((N + 255) / 256), block(256);
-    const int deg = in->shs ? in->sh_degree : 0;
-    Surfel *rec = (Surfel *)(base + L.rec);
-    BinRec *bin = (BinRec *)(base + L.bin);
-    dispatch_sh_degree(deg, in->shs_rest != nullptr, [&](auto D, auto S) {
-      preprocess2d_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, (uint64_t *)(base + L.tile_mask), out_radii, tile_count);
-    });
-    SCORP_KERNEL_CHECK("preprocess_2d", in->debug, stream);
-  }
-  return bin_count_and_scan(L, base, N, in->debug, stream);
+                                     scorp_stream_t stream) {
+  return preprocess2d_impl(in, out_radii, state, state_bytes, stream);
 }
 
-static int render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, float *out_color,
-                         float *out_allmap, scorp_stream_t stream_, bool for_backward) {
-  if (int e = validate2(in)) return e;
+int scorp::preprocess2d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, void *state, size_t state_bytes, scorp_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const int N = in->num_gaussians, W = in->image_width, H = in->image_height;
-  const StateLayout L(N, W, H, true);
-  const PairLayout P(capacity);
-  if (!state || ((uintptr_t)state & 255) || !pairs || ((uintptr_t)pairs & 255)) { set_error("state / pairs NULL or misaligned"); return SCORP_ERR_INVALID; }
-  if (capacity > 0xFFFFFFFFull) { set_error("capacity above 2^32-1 pairs"); return SCORP_ERR_INVALID; }
+  return preprocess_pass(kGs2d, in, out_radii, state, state_bytes, stream, [&](const StateLayout &L, char *base) {
+    const Pg2Args a = make_args2(in, L);
+    const dim3 grid((in->num_gaussians + 255) / 256), block(256);
+    dispatch_sh_degree(in->shs ? in->sh_degree : 0, in->shs_rest != nullptr, [&](auto D, auto S) {
+      preprocess2d_kernel<D, S><<<grid, block, 0, stream>>>(a, (Surfel *)(base + L.rec), (BinRec *)(base + L.bin),
+                                                            (uint64_t *)(base + L.tile_mask), out_radii, (uint32_t *)(base + L.tile_count));
+    });
+  });
+}
+
+int scorp::render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, float *out_color,
+                         float *out_allmap, scorp_stream_t stream_, bool for_backward) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RenderFrame f;
+  if (int e = render_frame(kGs2d, in, state, pairs, capacity, for_backward, &f)) return e;
   if (!out_color || !out_allmap) { set_error("output image pointer is NULL"); return SCORP_ERR_INVALID; }
-  char *base = (char *)state, *pb = (char *)pairs;
-  if (int e = bin_scatter_and_sort(L, P, base, pb, N, (uint32_t)capacity, in->debug, stream)) return e;
+  const StateLayout &L = f.L;
+  if (int e = bin_scatter_and_sort(L, f.P, f.base, f.pb, f.N, f.capacity, in->debug, stream)) return e;
   {
     ProfScope prof(kKBlendForward2d, stream);
     auto bk = for_backward ? blend2d_forward_wave_kernel<true> : blend2d_forward_wave_kernel<false>;
     bk<<<(L.tiles + 7) / 8 * 32, 64, 0, stream>>>(
-        (const uint32_t *)(base + L.tile_start), (const uint32_t *)(pb + P.list), (const Surfel *)(base + L.rec),
-        (uint32_t)capacity, W, H, L.tiles_x, L.tiles, in->bg, out_color, out_allmap, (float *)(base + L.final_T),
-        (uint32_t *)(base + L.n_contrib), (uint32_t *)(pb + P.hits));
+        (const uint32_t *)(f.base + L.tile_start), (const uint32_t *)(f.pb + f.P.list), (const Surfel *)(f.base + L.rec),
+        f.capacity, f.W, f.H, L.tiles_x, L.tiles, in->bg, out_color, out_allmap, (float *)(f.base + L.final_T),
+        (uint32_t *)(f.base + L.n_contrib), (uint32_t *)(f.pb + f.P.hits));
   }
   SCORP_KERNEL_CHECK("blend_forward_2d", in->debug, stream);
   return SCORP_OK;
@@ -1356,99 +1298,56 @@ extern "C" int scorp_gs2d_backward(const ScorpGs3dInputs *in, const void *state,
   return scorp_gs2d_backward_ex(in, state, pairs, capacity, dL_dcolor, dL_dallmap, grads, scratch, scratch_bytes, 0u, stream_);
 }
 
+// (2DGS ignores SCORP_BACKWARD_SCRATCH_ZEROED: include/scorp_gs.h)
 extern "C" int scorp_gs2d_backward_ex(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                                       const float *dL_dcolor, const float *dL_dallmap, const ScorpGs3dGrads *grads,
                                       void *scratch, size_t scratch_bytes, uint32_t flags, scorp_stream_t stream_) {
-  return backward2d_impl(in, state, pairs, capacity, dL_dcolor, dL_dallmap, grads, scratch, scratch_bytes, flags, stream_, nullptr);
+  return backward2d_impl(in, state, pairs, capacity, dL_dcolor, dL_dallmap, grads, scratch, scratch_bytes,
+                         flags & ~SCORP_BACKWARD_SCRATCH_ZEROED, stream_, nullptr);
 }
 
 // `adam` (scorp_gs2d_train_view): the per-surfel kernel applies the optimizer step and the view's statistics itself
 int scorp::backward2d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                            const float *dL_dcolor, const float *dL_dallmap, const ScorpGs3dGrads *grads, void *scratch,
                            size_t scratch_bytes, uint32_t flags, scorp_stream_t stream_, const AdamEpi *adam) {
-  if (!in || !state || !pairs || !grads || !scratch || !dL_dcolor) { set_error("NULL argument to scorp_gs2d_backward"); return SCORP_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
-  const int N = in->num_gaussians, W = in->image_width, H = in->image_height;
-  if (N <= 0) return SCORP_OK;
-  const StateLayout L(N, W, H, true);
-  const PairLayout P(capacity);
-  const bool det = (flags & SCORP_BACKWARD_DETERMINISTIC) != 0, exact = (flags & SCORP_BACKWARD_EXACT_FP32) != 0;
-  const size_t need = scorp_gs2d_backward_scratch_bytes_ex(N, W, H, capacity, flags);
-  if (scratch_bytes < need || ((uintptr_t)scratch & 15)) {
-    set_error("2D backward scratch too small or misaligned (%zu < %zu)", scratch_bytes, need);
-    return SCORP_ERR_INVALID;
-  }
-  if (det && capacity * 4 > 0xFFFFFFFFull) { set_error("capacity too large for the deterministic backward"); return SCORP_ERR_INVALID; }
   const char *base = (const char *)state, *pb = (const char *)pairs;
-  float *acc = (float *)scratch;
-  float *partial = nullptr;
-  uint8_t *row_flags = nullptr;
-  uint32_t *pair_base = nullptr;
-  const BinRec *bin_arr = (const BinRec *)(base + L.bin);
-  const uint64_t *mask_arr = (const uint64_t *)(base + L.tile_mask);
-  if (det) {
-    const DetLayout DL(N, capacity, kAcc2Stride);
-    char *p = (char *)scratch;
-    partial = (float *)(p + DL.partial);
-    row_flags = (uint8_t *)(p + DL.flags);
-    pair_base = (uint32_t *)(p + DL.pair_base);
-    SCORP_HIP_CHECK(hipMemsetAsync(row_flags, 0, (size_t)(capacity > 0 ? capacity : 1) * 4, stream));
-    launch_pair_base(N, bin_arr, mask_arr, (uint32_t *)(p + DL.block_sums), pair_base, stream);
-    SCORP_KERNEL_CHECK("pair_base", in->debug, stream);
-  } else {
-    SCORP_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)N * kAcc2Stride * sizeof(float), stream));
-  }
-  {
-    ProfScope prof(kKBlendBackward2d, stream);
-    const bool map = dL_dallmap != nullptr;
+  auto blend = [&](const StateLayout &L, const PairLayout &P, float *acc, float *partial, uint8_t *row_flags, uint32_t *pair_base) {
+    const bool det = partial != nullptr, exact = (flags & SCORP_BACKWARD_EXACT_FP32) != 0, map = dL_dallmap != nullptr;
     auto wk = det ? (exact ? (map ? blend2d_backward_wave_kernel<true, true, true> : blend2d_backward_wave_kernel<false, true, true>)
                            : (map ? blend2d_backward_wave_kernel<true, false, true> : blend2d_backward_wave_kernel<false, false, true>))
                   : (exact ? (map ? blend2d_backward_wave_kernel<true, true, false> : blend2d_backward_wave_kernel<false, true, false>)
                            : (map ? blend2d_backward_wave_kernel<true, false, false> : blend2d_backward_wave_kernel<false, false, false>));
     wk<<<(L.tiles + 7) / 8 * 32, 64, 0, stream>>>(
         (const uint32_t *)(base + L.tile_start), (const uint32_t *)(pb + P.list), (const Surfel *)(base + L.rec),
-        (uint32_t)capacity, W, H, L.tiles_x, L.tiles, in->bg, (const float *)(base + L.final_T),
+        (uint32_t)capacity, in->image_width, in->image_height, L.tiles_x, L.tiles, in->bg, (const float *)(base + L.final_T),
         (const uint32_t *)(base + L.n_contrib), dL_dcolor, dL_dallmap, acc, (const uint32_t *)(pb + P.hits), partial, row_flags,
-        pair_base, bin_arr, mask_arr);
-  }
-  SCORP_KERNEL_CHECK("blend_backward_2d", in->debug, stream);
-  if (det) {
-    reduce_pair_rows2d_kernel<<<(N + 7) / 8, 256, 0, stream>>>(N, pair_base, (uint32_t)capacity, row_flags, partial, acc);
-    SCORP_KERNEL_CHECK("reduce_pair_rows_2d", in->debug, stream);
-  }
-  {
-    ProfScope prof(kKPreprocessBackward2d, stream);
+        pair_base, (const BinRec *)(base + L.bin), (const uint64_t *)(base + L.tile_mask));
+  };
+  auto per_gaussian = [&](const StateLayout &L, const float *acc) {
     const Pg2Args a = make_args2(in, L);
-    const dim3 grid((N + 255) / 256), block(256);
-    const int deg = in->shs ? in->sh_degree : 0;
+    const dim3 grid((in->num_gaussians + 255) / 256), block(256);
     const ScorpGs3dGrads g = *grads;
     const Surfel *rec = (const Surfel *)(base + L.rec);
     const BinRec *bin = (const BinRec *)(base + L.bin);
     AdamEpi ad;
     memset(&ad, 0, sizeof(ad));
     if (adam && in->shs_rest) ad = *adam;   // (the fused step is defined for the training layout: dc / rest split leaves)
-    dispatch_sh_degree(deg, in->shs_rest != nullptr, [&](auto D, auto S) {
+    dispatch_sh_degree(in->shs ? in->sh_degree : 0, in->shs_rest != nullptr, [&](auto D, auto S) {
       preprocess2d_backward_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, acc, g, ad);
     });
-  }
-  SCORP_KERNEL_CHECK("preprocess_backward_2d", in->debug, stream);
-  return SCORP_OK;
+  };
+  return backward_pass(kGs2d, in, state, pairs, capacity, dL_dcolor, grads, scratch, scratch_bytes, flags, stream, blend,
+                       per_gaussian);
 }
 
 // xy[N,2], depth[N], T[N,9], normal_opacity[N,4], rgb[N,3], rect[N,4]; any may be NULL (stage-level parity tests)
 extern "C" int scorp_gs2d_debug_geom(const void *state, int32_t N, int32_t W, int32_t H, float *T, float *xy, float *depth,
-                                     float *normal_opacity, float *rgb, int32_t *rect, scorp_stream_t stream_) {
-  if (!state) { set_error("state is NULL"); return SCORP_ERR_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  const StateLayout L(N, W, H, true);
-  if (N <= 0) return SCORP_OK;
-  Surfel *hrec = (Surfel *)malloc((size_t)N * sizeof(Surfel));
-  BinRec *hbin = (BinRec *)malloc((size_t)N * sizeof(BinRec));
-  if (!hrec || !hbin) { free(hrec); free(hbin); set_error("host allocation failed"); return SCORP_ERR_INVALID; }
-  hipError_t e = hipMemcpyAsync(hrec, (const char *)state + L.rec, (size_t)N * sizeof(Surfel), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hbin, (const char *)state + L.bin, (size_t)N * sizeof(BinRec), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) { free(hrec); free(hbin); set_error("debug_geom copy failed: %s", hipGetErrorString(e)); return SCORP_ERR_HIP; }
+                                     float *normal_opacity, float *rgb, int32_t *rect, scorp_stream_t stream) {
+  void *host;
+  const BinRec *hbin;
+  if (int e = copy_geom_to_host(state, StateLayout(N, W, H, true), N, sizeof(Surfel), &host, &hbin, (hipStream_t)stream)) return e;
+  const Surfel *hrec = (const Surfel *)host;
   for (int i = 0; i < N; i++) {
     const bool vis = (hbin[i].radius & kRadiusMask) != 0;
     const Surfel z = {};
@@ -1461,18 +1360,11 @@ extern "C" int scorp_gs2d_debug_geom(const void *state, int32_t N, int32_t W, in
     if (rgb) { rgb[3 * i] = s.r3.w; rgb[3 * i + 1] = s.r4.x; rgb[3 * i + 2] = s.r4.y; }
     if (rect) { rect[4 * i] = vis ? hbin[i].x0 : 0; rect[4 * i + 1] = vis ? hbin[i].y0 : 0; rect[4 * i + 2] = vis ? hbin[i].x1 : 0; rect[4 * i + 3] = vis ? hbin[i].y1 : 0; }
   }
-  free(hrec); free(hbin);
+  free(host);
   return SCORP_OK;
 }
 
 extern "C" int scorp_gs2d_debug_tiles(const void *state, const void *pairs, uint64_t capacity, int32_t N, int32_t W,
-                                      int32_t H, uint32_t *tile_start, uint32_t *point_list, scorp_stream_t stream_) {
-  if (!state || !pairs) { set_error("state / pairs is NULL"); return SCORP_ERR_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  const StateLayout L(N, W, H, true);
-  const PairLayout P(capacity);
-  StateHeader h;
-  SCORP_HIP_CHECK(hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, stream));
-  SCORP_HIP_CHECK(hipStreamSynchronize(stream));
-  return copy_tile_lists_raster(L, P, state, pairs, capacity, h.num_pairs, tile_start, point_list, stream);
+                                      int32_t H, uint32_t *tile_start, uint32_t *point_list, scorp_stream_t stream) {
+  return debug_tiles(true, state, pairs, capacity, N, W, H, tile_start, point_list, (hipStream_t)stream);
 }

@@ -513,8 +513,8 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
 // search: ~190 dependent loads per Gaussian, 2.7 ms of a 3.5 ms view).
 //   pair_count_kernel / pair_base_kernel : pair_base[i] = number of (Gaussian, tile) pairs of the Gaussians before i
 //                                          (a two-level exclusive scan of the tile counts the binning used)
-//   reduce_pair_rows_kernel              : sixteen lanes per Gaussian (lane = float of a row) add the flagged rows in the
-//                                          fixed order tiles of the mask x blocks 0..3
+//   reduce_pair_rows_kernel              : kLanes lanes per Gaussian (lane = float of a row) add the flagged rows in the
+//                                          fixed order tiles of the mask x blocks 0..3 (the 3-D rows and the 2-D ones)
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kScanBlock = kPairScanBlock;   // Gaussians per workgroup of the pair-count scan
 __device__ __forceinline__ uint32_t pairs_of(const BinRec &br, uint64_t mask) {
@@ -574,11 +574,13 @@ pair_base_kernel(int N, const BinRec *__restrict__ bin, const uint64_t *__restri
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) pair_base[N] = run;
 }
 
+// rows of kStride floats, of which the first kUsed are summed (the rest of the accumulator row is written as zeros)
+template <int kStride, int kUsed, int kLanes>
 __global__ void __launch_bounds__(256)
 reduce_pair_rows_kernel(int N, const uint32_t *__restrict__ pair_base, uint32_t capacity, const uint8_t *__restrict__ row_flags,
                         const float *__restrict__ partial, float *__restrict__ acc) {
-  const int i = blockIdx.x * 16 + (threadIdx.x >> 4), col = threadIdx.x & 15;
-  if (i >= N) return;
+  const int i = blockIdx.x * (256 / kLanes) + (threadIdx.x / kLanes), col = threadIdx.x % kLanes;
+  if (i >= N || col >= kStride) return;
   const uint32_t r0 = min(pair_base[i], capacity) * 4u, r1 = min(pair_base[i + 1], capacity) * 4u;
   float sum = 0.0f;
   // four (Gaussian, tile) pairs = sixteen rows per step: the four flag words first, then every flagged row, all loads in
@@ -591,12 +593,12 @@ reduce_pair_rows_kernel(int N, const uint32_t *__restrict__ pair_base, uint32_t 
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const bool on = (f[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-      v[k] = on ? partial[(size_t)(r + k) * kAccStride + col] : 0.0f;
+      v[k] = on ? partial[(size_t)(r + k) * kStride + col] : 0.0f;
     }
 #pragma unroll
     for (int k = 0; k < 16; k++) sum += v[k];   // (an absent row adds an exact zero)
   }
-  acc[(size_t)i * kAccStride + col] = col < 10 ? sum : 0.0f;
+  acc[(size_t)i * kStride + col] = col < kUsed ? sum : 0.0f;
 }
 
 }  // namespace
@@ -613,17 +615,29 @@ int scorp::launch_pair_base(int N, const BinRec *bin, const uint64_t *tile_mask,
   return SCORP_OK;
 }
 
+namespace scorp {
+template <int kStride, int kUsed, int kLanes>
+void launch_reduce_pair_rows(int N, const uint32_t *pair_base, uint32_t capacity, const uint8_t *row_flags,
+                             const float *partial, float *acc, hipStream_t stream) {
+  constexpr int per_block = 256 / kLanes;
+  reduce_pair_rows_kernel<kStride, kUsed, kLanes><<<(N + per_block - 1) / per_block, 256, 0, stream>>>(
+      N, pair_base, capacity, row_flags, partial, acc);
+}
+// 3DGS: ten floats of a 16-float row; 2DGS: the whole 20-float row (kAcc2Stride, gs2d.hip)
+template void launch_reduce_pair_rows<kAccStride, 10, 16>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
+                                                          hipStream_t);
+template void launch_reduce_pair_rows<20, 20, 32>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
+                                                  hipStream_t);
+}  // namespace scorp
+
 using namespace scorp;
 
 extern "C" size_t scorp_gs3d_backward_scratch_bytes_ex(int32_t N, int32_t W, int32_t H, uint64_t capacity, uint32_t flags) {
   (void)W; (void)H;
-  if (flags & SCORP_BACKWARD_DETERMINISTIC) return DetLayout(N, capacity, kAccStride).total;
-  return align_up((size_t)(N > 0 ? N : 1) * kAccStride * sizeof(float), 256);
+  return backward_scratch_bytes(N, capacity, flags, kAccStride);
 }
 
-extern "C" size_t scorp_gs3d_backward_scratch_bytes(int32_t N) {
-  return align_up((size_t)(N > 0 ? N : 1) * kAccStride * sizeof(float), 256);
-}
+extern "C" size_t scorp_gs3d_backward_scratch_bytes(int32_t N) { return backward_scratch_bytes(N, 0, 0u, kAccStride); }
 
 extern "C" int scorp_gs3d_backward(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                                    const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
@@ -646,47 +660,11 @@ int scorp::backward3d_impl(const ScorpGs3dInputs *in, const void *state, const v
                            const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
                            const ScorpGs3dGrads *grads, void *scratch, size_t scratch_bytes, uint32_t flags,
                            scorp_stream_t stream_, const AdamEpi *adam) {
-  if (!in || !state || !pairs || !grads || !scratch) { set_error("NULL argument to scorp_gs3d_backward"); return SCORP_ERR_INVALID; }
-  if (!dL_dcolor) { set_error("dL_dcolor is NULL"); return SCORP_ERR_INVALID; }
-  if (in->num_views > 1) { set_error("num_views > 1 is forward only"); return SCORP_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
-  const int N = in->num_gaussians, W = in->image_width, H = in->image_height;
-  if (N <= 0) return SCORP_OK;
-  if ((uint64_t)N * kAccStride > 0xFFFFFFFFull) {   // the blend kernel addresses accumulators with 32-bit float offsets
-    set_error("num_gaussians %d above the %llu the backward supports", N, 0xFFFFFFFFull / kAccStride);
-    return SCORP_ERR_INVALID;
-  }
-  const StateLayout L(N, W, H);
-  const PairLayout P(capacity);
-  const bool det = (flags & SCORP_BACKWARD_DETERMINISTIC) != 0;
-  const size_t need = scorp_gs3d_backward_scratch_bytes_ex(N, W, H, capacity, flags);
-  if (det && capacity * 4 * kAccStride > 0xFFFFFFFFull) { set_error("capacity too large for the deterministic backward"); return SCORP_ERR_INVALID; }
-  if (scratch_bytes < need || ((uintptr_t)scratch & 15)) {
-    set_error("backward scratch too small or misaligned (%zu < %zu)", scratch_bytes, need);
-    return SCORP_ERR_INVALID;
-  }
   const char *base = (const char *)state, *pb = (const char *)pairs;
-  float *acc = (float *)scratch;
-  float *partial = nullptr;
-  uint8_t *row_flags = nullptr;
-  uint32_t *pair_base = nullptr;
-  const DetLayout DL(N, capacity, kAccStride);
-  if (det) {
-    char *p = (char *)scratch;
-    partial = (float *)(p + DL.partial);
-    row_flags = (uint8_t *)(p + DL.flags);
-    pair_base = (uint32_t *)(p + DL.pair_base);
-    uint32_t *block_sums = (uint32_t *)(p + DL.block_sums);
-    SCORP_HIP_CHECK(hipMemsetAsync(row_flags, 0, (size_t)(capacity > 0 ? capacity : 1) * 4, stream));
-    launch_pair_base(N, (const BinRec *)(base + L.bin), (const uint64_t *)(base + L.tile_mask), block_sums, pair_base, stream);
-    SCORP_KERNEL_CHECK("pair_base", in->debug, stream);
-  } else if (!(flags & SCORP_BACKWARD_SCRATCH_ZEROED)) {
-    SCORP_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)N * kAccStride * sizeof(float), stream));
-  }
-  {
-    ProfScope prof(kKBlendBackward, stream);
+  auto blend = [&](const StateLayout &L, const PairLayout &P, float *acc, float *partial, uint8_t *row_flags, uint32_t *pair_base) {
     const int blocks = ((L.tiles + 7) / 8) * 8 * 4;
-    const bool da = dL_ddepth || dL_dalpha, exact = (flags & SCORP_BACKWARD_EXACT_FP32) != 0;
+    const bool det = partial != nullptr, da = dL_ddepth || dL_dalpha, exact = (flags & SCORP_BACKWARD_EXACT_FP32) != 0;
     // nothing but colour gradients wanted (every geometry / opacity output NULL): the colour-only replay
     const bool adam_geom = adam && adam->on && (adam->m[0] || adam->m[3] || adam->m[4] || adam->m[5] || adam->accum);
     const bool color_only = !exact && !adam_geom && !grads->means3D && !grads->means2D && !grads->opacities && !grads->scales &&
@@ -699,19 +677,13 @@ int scorp::backward3d_impl(const ScorpGs3dInputs *in, const void *state, const v
                       : (da ? blend_backward_wave_kernel<true, false> : blend_backward_wave_kernel<false, false>);
     wk<<<blocks, 64, 0, stream>>>(
         (const uint32_t *)(base + L.tile_start), (const uint32_t *)(pb + P.hits), (const SplatRec *)(base + L.rec),
-        (uint32_t)capacity, W, H, L.tiles_x, L.tiles, in->bg, (const float *)(base + L.final_T),
+        (uint32_t)capacity, in->image_width, in->image_height, L.tiles_x, L.tiles, in->bg, (const float *)(base + L.final_T),
         (const uint32_t *)(base + L.n_contrib), dL_dcolor, dL_ddepth, dL_dalpha, acc, partial, row_flags, pair_base,
         (const BinRec *)(base + L.bin), (const uint64_t *)(base + L.tile_mask));
-  }
-  SCORP_KERNEL_CHECK("blend_backward", in->debug, stream);
-  if (det) {
-    reduce_pair_rows_kernel<<<(N + 15) / 16, 256, 0, stream>>>(N, pair_base, (uint32_t)capacity, row_flags, partial, acc);
-    SCORP_KERNEL_CHECK("reduce_pair_rows", in->debug, stream);
-  }
-  {
-    ProfScope prof(kKPreprocessBackward, stream);
+  };
+  auto per_gaussian = [&](const StateLayout &L, const float *acc) {
     launch_preprocess_backward(in, L, (const BinRec *)(base + L.bin), acc, grads, stream, adam);
-  }
-  SCORP_KERNEL_CHECK("preprocess_backward", in->debug, stream);
-  return SCORP_OK;
+  };
+  return backward_pass(kGs3d, in, state, pairs, capacity, dL_dcolor, grads, scratch, scratch_bytes, flags, stream, blend,
+                       per_gaussian);
 }

@@ -1011,13 +1011,17 @@ score_reduce_kernel(const float *__restrict__ partial, float scale, float *__res
   if (threadIdx.x == 0) acc[blockIdx.x] += scale * tot;
 }
 
-int validate(const ScorpGs3dInputs *in) {
+}  // namespace
+}  // namespace scorp
+
+namespace scorp {
+int validate(const GsKind &K, const ScorpGs3dInputs *in, int *views) {
   if (!in) { set_error("inputs is NULL"); return SCORP_ERR_INVALID; }
   if (in->num_gaussians < 0 || in->image_width <= 0 || in->image_height <= 0) {
     set_error("bad sizes: N=%d W=%d H=%d", in->num_gaussians, in->image_width, in->image_height);
     return SCORP_ERR_INVALID;
   }
-  if (in->image_width > 16 * 65535 || in->image_height > 16 * 65535) {
+  if (in->image_width > 16 * 65535 || in->image_height > 16 * 65535) {   // (BinRec holds tile rectangles as uint16)
     set_error("image larger than 65535 tiles per axis"); return SCORP_ERR_INVALID;
   }
   if (in->num_gaussians > 0) {
@@ -1040,11 +1044,15 @@ int validate(const ScorpGs3dInputs *in) {
   if (!in->bg || !in->viewmatrix || !in->projmatrix || !in->campos) {
     set_error("bg / viewmatrix / projmatrix / campos is NULL"); return SCORP_ERR_INVALID;
   }
-  if (in->num_views < 0) { set_error("num_views %d is negative", in->num_views); return SCORP_ERR_INVALID; }
-  if (in->num_views > 1) {
-    const long long nt = (long long)in->num_views * in->num_gaussians, ht = (long long)in->num_views * in->image_height;
-    if (in->image_height % kTile != 0) { set_error("num_views > 1 needs image_height to be a multiple of %d", kTile); return SCORP_ERR_INVALID; }
-    if (nt > 0x7FFFFFFFll || ht > 16 * 65535ll) { set_error("num_views x N or num_views x H too large"); return SCORP_ERR_INVALID; }
+  *views = 1;
+  if (K.stacked_views) {
+    if (in->num_views < 0) { set_error("num_views %d is negative", in->num_views); return SCORP_ERR_INVALID; }
+    if (in->num_views > 1) {
+      const long long nt = (long long)in->num_views * in->num_gaussians, ht = (long long)in->num_views * in->image_height;
+      if (in->image_height % kTile != 0) { set_error("num_views > 1 needs image_height to be a multiple of %d", kTile); return SCORP_ERR_INVALID; }
+      if (nt > 0x7FFFFFFFll || ht > 16 * 65535ll) { set_error("num_views x N or num_views x H too large"); return SCORP_ERR_INVALID; }
+      *views = in->num_views;
+    }
   }
   // SH rows and quaternions are fetched as 16-byte words (and SH rows by direct global -> LDS loads)
   if ((((uintptr_t)in->shs | (uintptr_t)in->shs_rest | (uintptr_t)in->rotations) & 15) != 0) {
@@ -1053,10 +1061,31 @@ int validate(const ScorpGs3dInputs *in) {
   return SCORP_OK;
 }
 
-}  // namespace
-}  // namespace scorp
+int check_buffers(const void *state, const void *pairs, uint64_t capacity) {
+  if (!state || ((uintptr_t)state & 255) || !pairs || ((uintptr_t)pairs & 255)) {
+    set_error("state / pairs buffer NULL or not 256-byte aligned"); return SCORP_ERR_INVALID;
+  }
+  if (capacity > 0xFFFFFFFFull) { set_error("capacity above 2^32-1 pairs"); return SCORP_ERR_INVALID; }
+  return SCORP_OK;
+}
 
-namespace scorp {
+int read_header(const void *state, hipStream_t stream, StateHeader *h) {
+  SCORP_HIP_CHECK(hipMemcpyAsync(h, state, sizeof(*h), hipMemcpyDeviceToHost, stream));
+  SCORP_HIP_CHECK(hipStreamSynchronize(stream));
+  return SCORP_OK;
+}
+
+int render_frame(const GsKind &K, const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, bool for_backward,
+                 RenderFrame *f) {
+  int V;
+  if (int e = validate(K, in, &V)) return e;
+  if (V > 1 && for_backward) { set_error("num_views > 1 is forward only: use scorp_gs3d_render_image"); return SCORP_ERR_INVALID; }
+  if (int e = check_buffers(state, pairs, capacity)) return e;
+  const int N = V * in->num_gaussians, W = in->image_width, H = V * in->image_height;
+  *f = {V, N, W, H, (uint32_t)capacity, StateLayout(N, W, H, K.mode2d, V), PairLayout(capacity), (char *)state, (char *)pairs};
+  return SCORP_OK;
+}
+
 int bin_count_and_scan(const StateLayout &L, char *base, int N, int debug, hipStream_t stream) {
   uint32_t *tile_count = (uint32_t *)(base + L.tile_count);
   if (L.two_level) {
@@ -1167,9 +1196,14 @@ int bin_scatter_and_sort(const StateLayout &L, const PairLayout &P, char *base, 
 
 // The debug entry points' view of the tile lists: tile_start[tiles + 1] in RASTER tile order with the lists concatenated in
 // that order - whatever order they have in the pair buffer (cell-major under the two-level binning).
-int scorp::copy_tile_lists_raster(const StateLayout &L, const PairLayout &P, const void *state, const void *pairs, uint64_t capacity,
-                                  uint32_t num_pairs, uint32_t *tile_start, uint32_t *point_list, hipStream_t stream) {
-  const size_t n = num_pairs < capacity ? num_pairs : (size_t)capacity;
+int scorp::debug_tiles(bool mode2d, const void *state, const void *pairs, uint64_t capacity, int N, int W, int H,
+                       uint32_t *tile_start, uint32_t *point_list, hipStream_t stream) {
+  if (int e = check_buffers(state, pairs, capacity)) return e;
+  const StateLayout L(N, W, H, mode2d);
+  const PairLayout P(capacity);
+  StateHeader h;
+  if (int e = read_header(state, stream, &h)) return e;
+  const size_t n = h.num_pairs < capacity ? h.num_pairs : (size_t)capacity;
   uint32_t *range = (uint32_t *)malloc(((size_t)L.tiles + 1) * 8), *list = (uint32_t *)malloc((n ? n : 1) * 4);
   if (!range || !list) { free(range); free(list); set_error("out of host memory"); return SCORP_ERR_INVALID; }
   hipError_t e = hipMemcpyAsync(range, (const char *)state + L.tile_start, (size_t)L.tiles * 8, hipMemcpyDeviceToHost, stream);
@@ -1188,6 +1222,23 @@ int scorp::copy_tile_lists_raster(const StateLayout &L, const PairLayout &P, con
   return SCORP_OK;
 }
 
+int scorp::copy_geom_to_host(const void *state, const StateLayout &L, int N, size_t rec_bytes, void **rec, const BinRec **bin,
+                             hipStream_t stream) {
+  if (!state) { set_error("state is NULL"); return SCORP_ERR_INVALID; }
+  *rec = nullptr;
+  *bin = nullptr;
+  if (N <= 0) return SCORP_OK;
+  char *h = (char *)malloc((size_t)N * (rec_bytes + sizeof(BinRec)));
+  if (!h) { set_error("host allocation failed"); return SCORP_ERR_INVALID; }
+  hipError_t e = hipMemcpyAsync(h, (const char *)state + L.rec, (size_t)N * rec_bytes, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h + (size_t)N * rec_bytes, (const char *)state + L.bin, (size_t)N * sizeof(BinRec), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) { free(h); set_error("debug_geom copy failed: %s", hipGetErrorString(e)); return SCORP_ERR_HIP; }
+  *rec = h;
+  *bin = (const BinRec *)(h + (size_t)N * rec_bytes);
+  return SCORP_OK;
+}
+
 using namespace scorp;
 
 extern "C" size_t scorp_gs3d_state_bytes(int32_t N, int32_t W, int32_t H) { return StateLayout(N, W, H).total; }
@@ -1200,46 +1251,25 @@ extern "C" int scorp_gs3d_preprocess(const ScorpGs3dInputs *in, int32_t *out_rad
 
 int scorp::preprocess3d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, uint8_t *out_visible, void *state,
                              size_t state_bytes, scorp_stream_t stream_) {
-  if (int e = validate(in)) return e;
   hipStream_t stream = (hipStream_t)stream_;
-  const int V = in->num_views > 1 ? in->num_views : 1;          // V views stacked vertically: V * N virtual Gaussians
-  const int N = V * in->num_gaussians, W = in->image_width, H = V * in->image_height;
-  const StateLayout L(N, W, H, false, V);
-  if (V > 1 && !L.lds_binning) { set_error("num_views > 1: the stacked image has too many tiles"); return SCORP_ERR_INVALID; }
-  if (!state || state_bytes < L.total || ((uintptr_t)state & 255)) {
-    set_error("state buffer NULL, misaligned or too small (%zu < %zu)", state_bytes, L.total);
-    return SCORP_ERR_INVALID;
-  }
-  if (N > 0 && !out_radii) { set_error("out_radii is NULL"); return SCORP_ERR_INVALID; }
-  char *base = (char *)state;
-  uint32_t *tile_count = (uint32_t *)(base + L.tile_count);
-  if (!L.lds_binning) SCORP_HIP_CHECK(hipMemsetAsync(tile_count, 0, ((size_t)L.tiles + 1) * 4, stream));
-  if (N > 0) {
-    ProfScope prof(kKPreprocess, stream);
+  return preprocess_pass(kGs3d, in, out_radii, state, state_bytes, stream, [&](const StateLayout &L, char *base) {
     launch_preprocess(in, L, (SplatRec *)(base + L.rec), (BinRec *)(base + L.bin), (uint64_t *)(base + L.tile_mask), out_radii,
-                      tile_count, out_visible, stream);
-    SCORP_KERNEL_CHECK("preprocess", in->debug, stream);
-  }
-  if (int e = bin_count_and_scan(L, base, N, in->debug, stream)) return e;
-  return SCORP_OK;
+                      (uint32_t *)(base + L.tile_count), out_visible, stream);
+  });
 }
 
-extern "C" int scorp_gs3d_num_pairs(const void *state, scorp_stream_t stream_, uint64_t *num_pairs) {
+extern "C" int scorp_gs3d_num_pairs(const void *state, scorp_stream_t stream, uint64_t *num_pairs) {
   if (!state || !num_pairs) { set_error("state / num_pairs is NULL"); return SCORP_ERR_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
   StateHeader h;
-  SCORP_HIP_CHECK(hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, stream));
-  SCORP_HIP_CHECK(hipStreamSynchronize(stream));
+  if (int e = read_header(state, (hipStream_t)stream, &h)) return e;
   *num_pairs = h.num_pairs;
   return SCORP_OK;
 }
 
-extern "C" int scorp_gs3d_check_overflow(const void *state, scorp_stream_t stream_, uint64_t *num_pairs) {
+extern "C" int scorp_gs3d_check_overflow(const void *state, scorp_stream_t stream, uint64_t *num_pairs) {
   if (!state) { set_error("state is NULL"); return SCORP_ERR_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
   StateHeader h;
-  SCORP_HIP_CHECK(hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, stream));
-  SCORP_HIP_CHECK(hipStreamSynchronize(stream));
+  if (int e = read_header(state, (hipStream_t)stream, &h)) return e;
   if (num_pairs) *num_pairs = h.num_pairs;
   if (h.overflow) {
     set_error("pair buffer overflow: %u pairs needed, capacity %u", h.num_pairs, h.capacity);
@@ -1251,22 +1281,12 @@ extern "C" int scorp_gs3d_check_overflow(const void *state, scorp_stream_t strea
 int scorp::render3d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, float *out_color,
                          float *out_depth, float *out_alpha, float *out_depth_norm, void *zero_buf, size_t zero_bytes,
                          scorp_stream_t stream_, bool for_backward, uint32_t *header_copy) {
-  if (int e = validate(in)) return e;
   hipStream_t stream = (hipStream_t)stream_;
-  const int V = in->num_views > 1 ? in->num_views : 1;
-  const int N = V * in->num_gaussians, W = in->image_width, H = V * in->image_height;
-  const StateLayout L(N, W, H, false, V);
-  const PairLayout P(capacity);
-  if (V > 1 && for_backward) { set_error("num_views > 1 is forward only: use scorp_gs3d_render_image"); return SCORP_ERR_INVALID; }
-  if (!state || ((uintptr_t)state & 255) || !pairs || ((uintptr_t)pairs & 255)) {
-    set_error("state / pairs buffer NULL or not 256-byte aligned"); return SCORP_ERR_INVALID;
-  }
-  if (capacity > 0xFFFFFFFFull) { set_error("capacity above 2^32-1 pairs"); return SCORP_ERR_INVALID; }
+  RenderFrame f;
+  if (int e = render_frame(kGs3d, in, state, pairs, capacity, for_backward, &f)) return e;
   if (!out_color || !out_depth || !out_alpha) { set_error("output image pointer is NULL"); return SCORP_ERR_INVALID; }
-  char *base = (char *)state, *pb = (char *)pairs;
-  uint32_t *tile_start = (uint32_t *)(base + L.tile_start);
-  uint32_t *point_list = (uint32_t *)(pb + P.list);
-  if (int e = bin_scatter_and_sort(L, P, base, pb, N, (uint32_t)capacity, in->debug, stream, header_copy)) return e;
+  const StateLayout &L = f.L;
+  if (int e = bin_scatter_and_sort(L, f.P, f.base, f.pb, f.N, f.capacity, in->debug, stream, header_copy)) return e;
   {
     ProfScope prof(kKBlendForward, stream);
     const int blocks = ((L.tiles + 7) / 8) * 8 * 4;
@@ -1276,10 +1296,10 @@ int scorp::render3d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, ui
     }
     auto bk = for_backward ? blend_forward_wave_kernel<true> : blend_forward_wave_kernel<false>;
     bk<<<blocks, 64, 0, stream>>>(
-        tile_start, point_list, (const SplatRec *)(base + L.rec), (uint32_t)capacity, W, H, L.tiles_x, L.tiles, in->bg,
-        out_color, out_depth, out_alpha, (float *)(base + L.final_T), (uint32_t *)(base + L.n_contrib),
-        (uint32_t *)(pb + P.hits), (uint32_t *)(base + L.block_hits), out_depth_norm, (float4 *)zero_buf,
-        (uint32_t)zero_per_wave, (uint32_t)zero_total, V > 1 ? in->image_height : 0, nullptr, nullptr, 0);
+        (const uint32_t *)(f.base + L.tile_start), (const uint32_t *)(f.pb + f.P.list), (const SplatRec *)(f.base + L.rec),
+        f.capacity, f.W, f.H, L.tiles_x, L.tiles, in->bg, out_color, out_depth, out_alpha, (float *)(f.base + L.final_T),
+        (uint32_t *)(f.base + L.n_contrib), (uint32_t *)(f.pb + f.P.hits), (uint32_t *)(f.base + L.block_hits), out_depth_norm,
+        (float4 *)zero_buf, (uint32_t)zero_per_wave, (uint32_t)zero_total, f.V > 1 ? in->image_height : 0, nullptr, nullptr, 0);
   }
   SCORP_KERNEL_CHECK("blend_forward", in->debug, stream);
   return SCORP_OK;
@@ -1298,29 +1318,25 @@ extern "C" int scorp_gs3d_render_image(const ScorpGs3dInputs *in, void *state, v
 extern "C" int scorp_gs3d_render_score(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity,
                                        const float *tgt_depth, const float *tgt_alpha, int32_t rows_per_score, float scale,
                                        float *acc, scorp_stream_t stream_) {
-  if (int e = validate(in)) return e;
   hipStream_t stream = (hipStream_t)stream_;
-  const int V = in->num_views > 1 ? in->num_views : 1;
-  const int N = V * in->num_gaussians, W = in->image_width, H = V * in->image_height;
+  RenderFrame f;
+  if (int e = render_frame(kGs3d, in, state, pairs, capacity, false, &f)) return e;
+  const int W = f.W, H = f.H;
   if (!tgt_depth || !tgt_alpha || !acc || rows_per_score <= 0 || rows_per_score % kTile != 0 || H % rows_per_score != 0) {
     set_error("scorp_gs3d_render_score: targets / acc NULL, or rows_per_score (%d) not a multiple of 16 dividing the %d rows", rows_per_score, H);
     return SCORP_ERR_INVALID;
   }
-  const StateLayout L(N, W, H, false, V);
-  const PairLayout P(capacity);
-  if (!state || ((uintptr_t)state & 255) || !pairs || ((uintptr_t)pairs & 255)) { set_error("state / pairs NULL or misaligned"); return SCORP_ERR_INVALID; }
-  if (capacity > 0xFFFFFFFFull) { set_error("capacity above 2^32-1 pairs"); return SCORP_ERR_INVALID; }
-  char *base = (char *)state, *pb = (char *)pairs;
-  if (int e = bin_scatter_and_sort(L, P, base, pb, N, (uint32_t)capacity, in->debug, stream, nullptr)) return e;
-  const uint32_t *tile_start = (const uint32_t *)(base + L.tile_start);
-  const uint32_t *point_list = (const uint32_t *)(pb + P.list);
+  const StateLayout &L = f.L;
+  char *base = f.base;
+  if (int e = bin_scatter_and_sort(L, f.P, base, f.pb, f.N, f.capacity, in->debug, stream, nullptr)) return e;
   {
     ProfScope prof(kKBlendForward, stream);
     const int blocks = ((L.tiles + 7) / 8) * 8 * 4;
     blend_forward_wave_kernel<false, true><<<blocks, 64, 0, stream>>>(
-        tile_start, point_list, (const SplatRec *)(base + L.rec), (uint32_t)capacity, W, H, L.tiles_x, L.tiles, in->bg,
-        nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t *)(pb + P.hits), (uint32_t *)(base + L.block_hits), nullptr, nullptr,
-        0u, 0u, V > 1 ? in->image_height : 0, tgt_depth, tgt_alpha, rows_per_score);
+        (const uint32_t *)(base + L.tile_start), (const uint32_t *)(f.pb + f.P.list), (const SplatRec *)(base + L.rec), f.capacity,
+        W, H, L.tiles_x, L.tiles, in->bg, nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t *)(f.pb + f.P.hits),
+        (uint32_t *)(base + L.block_hits), nullptr, nullptr, 0u, 0u, f.V > 1 ? in->image_height : 0, tgt_depth, tgt_alpha,
+        rows_per_score);
     // the blocks of score j are the tiles of rows [j, j + 1) * rows_per_score: contiguous tile ids, four blocks each
     const int scores = H / rows_per_score, blocks_per_score = (rows_per_score / kTile) * L.tiles_x * 4;
     float *partial = (float *)(base + L.final_T);   // (the per-pixel state of a backward pass: unused by this form)
@@ -1333,18 +1349,11 @@ extern "C" int scorp_gs3d_render_score(const ScorpGs3dInputs *in, void *state, v
 }
 
 extern "C" int scorp_gs3d_debug_geom(const void *state, int32_t N, int32_t W, int32_t H, float *xy, float *depth,
-                                     float *conic_opacity, float *rgb, int32_t *rect, scorp_stream_t stream_) {
-  if (!state) { set_error("state is NULL"); return SCORP_ERR_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  const StateLayout L(N, W, H);
-  if (N <= 0) return SCORP_OK;
-  SplatRec *hrec = (SplatRec *)malloc((size_t)N * sizeof(SplatRec));
-  BinRec *hbin = (BinRec *)malloc((size_t)N * sizeof(BinRec));
-  if (!hrec || !hbin) { free(hrec); free(hbin); set_error("host allocation failed"); return SCORP_ERR_INVALID; }
-  hipError_t e = hipMemcpyAsync(hrec, (const char *)state + L.rec, (size_t)N * sizeof(SplatRec), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hbin, (const char *)state + L.bin, (size_t)N * sizeof(BinRec), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) { free(hrec); free(hbin); set_error("debug_geom copy failed: %s", hipGetErrorString(e)); return SCORP_ERR_HIP; }
+                                     float *conic_opacity, float *rgb, int32_t *rect, scorp_stream_t stream) {
+  void *host;
+  const BinRec *hbin;
+  if (int e = copy_geom_to_host(state, StateLayout(N, W, H), N, sizeof(SplatRec), &host, &hbin, (hipStream_t)stream)) return e;
+  const SplatRec *hrec = (const SplatRec *)host;
   for (int i = 0; i < N; i++) {
     const bool vis = (hbin[i].radius & kRadiusMask) != 0;
     const SplatRec z = {};
@@ -1358,7 +1367,7 @@ extern "C" int scorp_gs3d_debug_geom(const void *state, int32_t N, int32_t W, in
     if (rgb) { rgb[3 * i] = s.r; rgb[3 * i + 1] = s.g; rgb[3 * i + 2] = s.b; }
     if (rect) { rect[4 * i] = vis ? hbin[i].x0 : 0; rect[4 * i + 1] = vis ? hbin[i].y0 : 0; rect[4 * i + 2] = vis ? hbin[i].x1 : 0; rect[4 * i + 3] = vis ? hbin[i].y1 : 0; }
   }
-  free(hrec); free(hbin);
+  free(host);
   return SCORP_OK;
 }
 
@@ -1390,13 +1399,6 @@ extern "C" int scorp_gs3d_debug_work(const void *state, int32_t N, int32_t W, in
 }
 
 extern "C" int scorp_gs3d_debug_tiles(const void *state, const void *pairs, uint64_t capacity, int32_t N, int32_t W,
-                                      int32_t H, uint32_t *tile_start, uint32_t *point_list, scorp_stream_t stream_) {
-  if (!state || !pairs) { set_error("state / pairs is NULL"); return SCORP_ERR_INVALID; }
-  hipStream_t stream = (hipStream_t)stream_;
-  const StateLayout L(N, W, H);
-  const PairLayout P(capacity);
-  StateHeader h;
-  SCORP_HIP_CHECK(hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, stream));
-  SCORP_HIP_CHECK(hipStreamSynchronize(stream));
-  return copy_tile_lists_raster(L, P, state, pairs, capacity, h.num_pairs, tile_start, point_list, stream);
+                                      int32_t H, uint32_t *tile_start, uint32_t *point_list, scorp_stream_t stream) {
+  return debug_tiles(false, state, pairs, capacity, N, W, H, tile_start, point_list, (hipStream_t)stream);
 }

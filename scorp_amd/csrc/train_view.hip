@@ -87,8 +87,8 @@ extern "C" int scorp_gs2d_train_view(const ScorpGs2dTrainView *v, scorp_stream_t
     return SCORP_ERR_INVALID;
   }
   hipStream_t hs = (hipStream_t)stream;
-  if (int e = scorp_gs2d_preprocess(in, v->out_radii, v->state, v->state_bytes, stream)) return e;
-  if (int e = scorp_gs2d_render(in, v->state, v->pairs, v->capacity, v->out_color, v->out_allmap, stream)) return e;
+  if (int e = preprocess2d_impl(in, v->out_radii, v->state, v->state_bytes, stream)) return e;
+  if (int e = render2d_impl(in, v->state, v->pairs, v->capacity, v->out_color, v->out_allmap, stream, true)) return e;
   if (int e = loss_forward_impl(v->out_color, v->gt, v->mask, 3, H, W, v->lambda_dssim, v->out_loss3, v->loss_workspace,
                                 v->loss_workspace_bytes, 1, false, hs)) return e;
   if (reg) {

@@ -80,3 +80,24 @@ def test_shim_packages_expose_reference_names(built_lib):
         r(means3D=None, means2D=None, opacities=None, shs=None, colors_precomp=None, scales=1, rotations=1)
     with pytest.raises(Exception, match="scale/rotation pair or precomputed 3D covariance"):
         r(means3D=None, means2D=None, opacities=None, shs=1, colors_precomp=None, scales=1, rotations=1, cov3D_precomp=1)
+
+
+@pytest.mark.parametrize("case, reason", [("wide", b"65535 tiles"), ("scales_only", b"scales+rotations")])
+def test_gs2d_preprocess_applies_the_3dgs_input_checks(built_lib, case, reason):
+    """2DGS validates its inputs as 3DGS does: an image wider than 65535 tiles (BinRec's tile rectangles are uint16) and
+    scales without rotations beside a precomputed transform are refused.  Validation runs before any HIP call, so the
+    dummy pointers are never dereferenced and no GPU is needed."""
+    from scorp_amd import _C
+    L = _C.lib()
+    dummy = 0x10000   # non-zero, 256-byte aligned
+    inp = _C.ScorpGs3dInputs(num_gaussians=1, sh_degree=0, sh_coeffs=1, image_width=64, image_height=64, tanfovx=1.0,
+                             tanfovy=1.0, scale_modifier=1.0, bg=dummy, viewmatrix=dummy, projmatrix=dummy, campos=dummy,
+                             means3D=dummy, shs=dummy, opacities=dummy, scales=dummy)
+    if case == "wide":
+        inp.image_width = 16 * 65535 + 1
+        inp.rotations = dummy
+    else:
+        inp.cov3D_precomp = dummy
+    rc = L.scorp_gs2d_preprocess(ctypes.byref(inp), dummy, dummy, 0, None)   # (state_bytes 0: never past the state check)
+    assert rc == -1   # SCORP_ERR_INVALID
+    assert reason in L.scorp_last_error()
