@@ -181,6 +181,34 @@ int scorp_gs3d_backward_ex(const ScorpGs3dInputs *in, const void *state, const v
                            const ScorpGs3dGrads *grads, void *scratch, size_t scratch_bytes, uint32_t flags,
                            scorp_stream_t stream);
 
+/* ---- 3-D segmentation by 2-D object masks (utils/mask.py:42-124 get_mask3d, one pass instead of 1 + 2K backwards) ----
+ * With w_i(p) = alpha_i(p) T_i(p) the blend weight the render gave Gaussian i at pixel p (zero where it was not blended) and
+ * masks[k][p] != 0 meaning "p is inside object k":
+ *   S_in[k][i] = sum over the pixels inside mask k of w_i(p),   S_out[k][i] = the same sum over the pixels outside it.
+ * One front-to-back replay of the hit lists scorp_gs3d_render / scorp_gs2d_render left (alpha recomputed with the forward's
+ * own arithmetic), eight objects per pass over the view; no float atomics, so two calls give the same bits.  The result is
+ * ADDED into `out` (views accumulate).  `masks` is [num_masks, H, W] bytes on the device, `out` fp32 on the device:
+ *   SCORP_VOTE_SUMS      out[K, 2, N]: out[k][0][i] += S_in, out[k][1][i] += S_out
+ *   SCORP_VOTE_GRADIENT  out[K, N]:    out[k][i] += scale * (S_in - S_out)   (get_mask3d's "gradient": scale = 1 / (sqrt(3) H W))
+ *   SCORP_VOTE_BINARY    out[K, N]:    out[k][i] += (S_in > 0) - (S_out > 0)
+ * Valid after *_preprocess + *_render (NOT after *_render_image / *_render_score, which leave no hit lists; the state cannot
+ * tell, and the result is then undefined); `capacity` is the one the render ran with.  The state and the pair buffer are
+ * only read: a backward after a vote gives the same bits as one without it.  Synchronises once (reads the state header).
+ * SCORP_ERR_INVALID: num_masks < 1, a NULL pointer, num_views > 1, an unknown method, scratch too small (or not 256-byte
+ * aligned), a capacity other than the render's; SCORP_ERR_OVERFLOW: the render overflowed its pair buffer.  N = 0 or an
+ * empty image: nothing is done. */
+#define SCORP_VOTE_SUMS 0u
+#define SCORP_VOTE_GRADIENT 1u
+#define SCORP_VOTE_BINARY 2u
+size_t scorp_mask_vote_scratch_bytes(int32_t num_gaussians, int32_t image_width, int32_t image_height, uint64_t capacity);
+int scorp_gs3d_mask_vote(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
+                         const uint8_t *masks, int32_t num_masks, uint32_t method, float scale, float *out, void *scratch,
+                         size_t scratch_bytes, scorp_stream_t stream);
+/* The same on a scorp_gs2d_preprocess + scorp_gs2d_render state. */
+int scorp_gs2d_mask_vote(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
+                         const uint8_t *masks, int32_t num_masks, uint32_t method, float scale, float *out, void *scratch,
+                         size_t scratch_bytes, scorp_stream_t stream);
+
 /* ---- introspection for stage-level parity tests (device->host copies; synchronises) ---- */
 /* xy[N,2], depth[N], conic_opacity[N,4], rgb[N,3], rect[N,4] (tile units, max exclusive); any may be NULL. */
 int scorp_gs3d_debug_geom(const void *state, int32_t num_gaussians, int32_t image_width, int32_t image_height,

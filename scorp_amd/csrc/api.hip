@@ -94,7 +94,7 @@ extern "C" int scorp_prof_collect(double *total_ms, uint64_t *launches) {
   return SCORP_OK;
 }
 
-extern "C" int scorp_version(void) { return 100; /* 0.1.0 */ }
+extern "C" int scorp_version(void) { return 101; /* 0.1.1: scorp_gs3d_mask_vote / scorp_gs2d_mask_vote */ }
 
 #ifndef SCORP_SOURCE_SHA
 #define SCORP_SOURCE_SHA "unknown"

@@ -349,7 +349,7 @@ inline size_t backward_scratch_bytes(int N, uint64_t capacity, uint32_t flags, i
 int launch_pair_base(int N, const BinRec *bin, const uint64_t *tile_mask, uint32_t *block_sums, uint32_t *pair_base,
                      hipStream_t stream);
 // acc[i] = the flagged partial rows of Gaussian i added in a fixed order (gs3d_backward.hip instantiates <16, 10, 16> for
-// 3DGS and <20, 20, 32> for 2DGS)
+// 3DGS, <20, 20, 32> for 2DGS and <16, 16, 16> for the mask vote)
 template <int kStride, int kUsed, int kLanes>
 void launch_reduce_pair_rows(int N, const uint32_t *pair_base, uint32_t capacity, const uint8_t *row_flags, const float *partial,
                              float *acc, hipStream_t stream);

@@ -628,6 +628,9 @@ template void launch_reduce_pair_rows<kAccStride, 10, 16>(int, const uint32_t *,
                                                           hipStream_t);
 template void launch_reduce_pair_rows<20, 20, 32>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
                                                   hipStream_t);
+// the mask vote (mask_vote.hip): sixteen sums per row, all of them used
+template void launch_reduce_pair_rows<16, 16, 16>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
+                                                  hipStream_t);
 }  // namespace scorp
 
 using namespace scorp;

@@ -28,8 +28,10 @@ def write_ply(path, xyz, f_dc, f_rest, opacity, scaling, rotation):
         os.makedirs(d, exist_ok=True)
     xyz = np.asarray(xyz, np.float32)
     n = xyz.shape[0]
-    dc = np.asarray(f_dc, np.float32).transpose(0, 2, 1).reshape(n, -1)
-    rest = np.asarray(f_rest, np.float32).transpose(0, 2, 1).reshape(n, -1)
+    f_dc, f_rest = np.asarray(f_dc, np.float32), np.asarray(f_rest, np.float32)
+    # (explicit widths: a model with no rows - an empty selection - still writes a valid header)
+    dc = f_dc.transpose(0, 2, 1).reshape(n, f_dc.shape[1] * f_dc.shape[2])
+    rest = f_rest.transpose(0, 2, 1).reshape(n, f_rest.shape[1] * f_rest.shape[2])
     cols = np.concatenate([xyz, np.zeros_like(xyz), dc, rest, np.asarray(opacity, np.float32).reshape(n, 1),
                            np.asarray(scaling, np.float32), np.asarray(rotation, np.float32)], axis=1)
     names = attribute_names(dc.shape[1], rest.shape[1], np.asarray(scaling).shape[1], np.asarray(rotation).shape[1])
@@ -96,7 +98,7 @@ def read_gaussian_ply(path, max_sh_degree=None):
             rest[:, k] = col(nm)
     else:
         rest = np.stack([col(nm) for nm in rest_names], 1) if rest_names else np.zeros((n, 0), np.float32)
-    rest = rest.reshape(n, 3, -1)
+    rest = rest.reshape(n, 3, rest.shape[1] // 3)
     scaling = np.stack([col(nm) for nm in by_index("scale_")], 1)
     rotation = np.stack([col(nm) for nm in by_index("rot")], 1)
     return dict(xyz=xyz, features_dc=np.ascontiguousarray(dc.transpose(0, 2, 1)),
