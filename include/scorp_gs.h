@@ -209,6 +209,32 @@ int scorp_gs2d_mask_vote(const ScorpGs3dInputs *in, const void *state, const voi
                          const uint8_t *masks, int32_t num_masks, uint32_t method, float scale, float *out, void *scratch,
                          size_t scratch_bytes, scorp_stream_t stream);
 
+/* ---- multi-start point-to-point ICP (align_3dgs_clpe_9dof.py:42-115 get_ICP_fitting_transformation_best: Open3D
+ * registration_icp with TransformationEstimationPointToPoint, no scaling, from every init of a batch) ----
+ * source[n_source, 3], target[n_target, 3] fp32 and inits[n_init, 4, 4] row-major float64 (rigid: last row 0 0 0 1) are
+ * device pointers, as are the outputs: out_transformation[n_init, 4, 4] float64, out_fitness / out_inlier_rmse[n_init]
+ * float64, out_iterations[n_init] int32.  Per init, with r = max_correspondence_distance:
+ *   pass(T):   x = T p for every source point; its pair is the nearest target point q with |x - q|^2 <= r^2 (exact search;
+ *              ties: the lower target index); c pairs, fitness = c / n_source, inlier_rmse = sqrt(sum |x - q|^2 / c)
+ *              (both 0 when c = 0);
+ *   update:    Umeyama / Kabsch without scale on the pairs (R = U D V^T, D = diag(1, 1, -1) iff det U det V < 0,
+ *              t = qm - R xm; the identity when c = 0);
+ *   loop:      result_0 = pass(T_0); for i < max_iteration: T_{i+1} = update(result_i) T_i, result_{i+1} = pass(T_{i+1}),
+ *              stop when |d fitness| < relative_fitness AND |d rmse| < relative_rmse.
+ * The outputs are the last T with its fitness and rmse, and the number of updates made.  The search runs in fp32
+ * relative to the target's bounding-box centre; the pair test, d^2 and the moments are float64, the transforms are
+ * composed in float64 and always applied to the original points.  No float atomics: two calls give the same bits, and an
+ * init run alone gives the bits it gets in a batch.  The inputs are only read.  workspace: scorp_icp_workspace_bytes,
+ * 256-byte aligned.  Synchronises every few iterations (reads the per-init active flags) and returns when every init has
+ * stopped.  SCORP_ERR_INVALID: r <= 0 (or not finite), an empty cloud, max_iteration < 0, n_init outside [1, 65535], a
+ * NULL pointer, a workspace too small or misaligned. */
+size_t scorp_icp_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init);
+int scorp_icp_point_to_point(const float *source, int32_t n_source, const float *target, int32_t n_target,
+                             const double *inits, int32_t n_init, double max_correspondence_distance, int32_t max_iteration,
+                             double relative_fitness, double relative_rmse, double *out_transformation, double *out_fitness,
+                             double *out_inlier_rmse, int32_t *out_iterations, void *workspace, size_t workspace_bytes,
+                             scorp_stream_t stream);
+
 /* ---- introspection for stage-level parity tests (device->host copies; synchronises) ---- */
 /* xy[N,2], depth[N], conic_opacity[N,4], rgb[N,3], rect[N,4] (tile units, max exclusive); any may be NULL. */
 int scorp_gs3d_debug_geom(const void *state, int32_t num_gaussians, int32_t image_width, int32_t image_height,

@@ -86,6 +86,7 @@ EXPORTS = [
     "scorp_gs2d_regularizers_backward", "scorp_gs3d_train_view", "scorp_gs2d_train_view",
     "scorp_prof_enable", "scorp_prof_select", "scorp_prof_num_kernels", "scorp_prof_kernel_name", "scorp_prof_collect",
     "scorp_mask_vote_scratch_bytes", "scorp_gs3d_mask_vote", "scorp_gs2d_mask_vote",
+    "scorp_icp_workspace_bytes", "scorp_icp_point_to_point",
 ]
 
 BACKWARD_EXACT_FP32 = 1   # scorp_gs3d_backward_ex flag (include/scorp_gs.h)
@@ -176,6 +177,10 @@ def lib():
     L.scorp_mask_vote_scratch_bytes.argtypes = [i32, i32, i32, u64]
     for fn in (L.scorp_gs3d_mask_vote, L.scorp_gs2d_mask_vote):
         fn.argtypes = [ctypes.POINTER(ScorpGs3dInputs), vp, vp, u64, vp, i32, ctypes.c_uint32, ctypes.c_float, vp, vp, sz, vp]
+    L.scorp_icp_workspace_bytes.restype = sz
+    L.scorp_icp_workspace_bytes.argtypes = [i32, i32, i32]
+    f64 = ctypes.c_double
+    L.scorp_icp_point_to_point.argtypes = [vp, i32, vp, i32, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
     L.scorp_prof_enable.argtypes = [ctypes.c_int]
     L.scorp_prof_select.argtypes = [u64]
     L.scorp_prof_kernel_name.restype = ctypes.c_char_p

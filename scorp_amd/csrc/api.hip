@@ -94,7 +94,7 @@ extern "C" int scorp_prof_collect(double *total_ms, uint64_t *launches) {
   return SCORP_OK;
 }
 
-extern "C" int scorp_version(void) { return 101; /* 0.1.1: scorp_gs3d_mask_vote / scorp_gs2d_mask_vote */ }
+extern "C" int scorp_version(void) { return 102; /* 0.1.2: scorp_icp_point_to_point */ }
 
 #ifndef SCORP_SOURCE_SHA
 #define SCORP_SOURCE_SHA "unknown"

@@ -1,0 +1,136 @@
+"""Multi-start point-to-point ICP on the GPU: the alignment scripts' get_ICP_fitting_transformation_best
+(align_3dgs_clpe_9dof.py:42-115, align_2dgs_clpe_9dof.py:48-121) without Open3D.
+
+The reference runs Open3D's registration_icp (TransformationEstimationPointToPoint, no scaling, max_iteration=400) once
+per initial pose, 67 poses by default.  Here every init runs in one batch through scorp_icp_point_to_point
+(csrc/icp.hip): one launch per iteration covers all inits still running.  Swap it in with one import:
+
+    from scorp_amd.icp import get_ICP_fitting_transformation_best
+"""
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _C
+
+
+@dataclass
+class ICPResult:
+    """Per init: the final transform [n_init, 4, 4] float64, its fitness and inlier_rmse, and the updates made."""
+    transformation: np.ndarray
+    fitness: np.ndarray
+    inlier_rmse: np.ndarray
+    iterations: np.ndarray
+
+
+def _check_finite(name, a):
+    if isinstance(a, torch.Tensor):
+        bad_nan, bad_inf = bool(torch.isnan(a).any()), bool(torch.isinf(a).any())
+    else:
+        a = np.asarray(a)
+        bad_nan, bad_inf = bool(np.isnan(a).any()), bool(np.isinf(a).any())
+    if bad_nan:
+        raise ValueError(f"{name} contains NaN values")
+    if bad_inf:
+        raise ValueError(f"{name} contains Inf values")
+
+
+def _points(name, a, device):
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be [n, 3]; got {tuple(t.shape)}")
+    if t.shape[0] == 0:
+        raise ValueError(f"{name} is empty")
+    if t.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name} has more than 2^31 - 1 points")
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _device(*arrays):
+    for a in arrays:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def registration_icp(source, target, max_correspondence_distance, inits, max_iteration=30, relative_fitness=1e-6,
+                     relative_rmse=1e-6):
+    """Open3D's registration_icp(source, target, r, init, TransformationEstimationPointToPoint(),
+    ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)) from every init of `inits` ([4, 4] or
+    [n_init, 4, 4]) at once.  source [n, 3] and target [m, 3]: numpy arrays or torch tensors (searched in fp32; pair
+    distances, moments and transforms in float64).  Returns an ICPResult of numpy arrays."""
+    r = float(max_correspondence_distance)
+    if not np.isfinite(r) or r <= 0.0:
+        raise ValueError(f"max_correspondence_distance must be positive and finite; got {max_correspondence_distance}")
+    if int(max_iteration) < 0:
+        raise ValueError(f"max_iteration must be >= 0; got {max_iteration}")
+    _check_finite("source", source)
+    _check_finite("target", target)
+    T0 = np.asarray(inits.detach().cpu() if isinstance(inits, torch.Tensor) else inits, dtype=np.float64)
+    if T0.shape == (4, 4):
+        T0 = T0[None]
+    if T0.ndim != 3 or T0.shape[1:] != (4, 4) or not 1 <= T0.shape[0] <= 65535:
+        raise ValueError(f"inits must be [4, 4] or [n_init, 4, 4] with 1 <= n_init <= 65535; got {T0.shape}")
+    _check_finite("inits", T0)
+    dev = _device(source, target)
+    P = _points("source", source, dev)
+    Q = _points("target", target, dev)
+    ni = T0.shape[0]
+    L = _C.lib()
+    ws = torch.empty(int(L.scorp_icp_workspace_bytes(P.shape[0], Q.shape[0], ni)) + 256, dtype=torch.uint8, device=dev)
+    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+    T_in = torch.as_tensor(np.ascontiguousarray(T0), device=dev)
+    T_out = torch.empty_like(T_in)
+    fit = torch.empty(ni, dtype=torch.float64, device=dev)
+    rmse = torch.empty(ni, dtype=torch.float64, device=dev)
+    iters = torch.empty(ni, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _C.check(L.scorp_icp_point_to_point(
+            P.data_ptr(), P.shape[0], Q.data_ptr(), Q.shape[0], T_in.data_ptr(), ni, ctypes.c_double(r), int(max_iteration),
+            ctypes.c_double(float(relative_fitness)), ctypes.c_double(float(relative_rmse)), T_out.data_ptr(),
+            fit.data_ptr(), rmse.data_ptr(), iters.data_ptr(), ws_ptr, ws.numel() - (ws_ptr - ws.data_ptr()),
+            _C.current_stream_ptr()), "scorp_icp_point_to_point")
+    return ICPResult(T_out.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy())
+
+
+def downsample_indices(num_original, num_refined):
+    """The source indices the reference keeps: Open3D's uniform_down_sample(k) (indices 0, k, 2k, ...) with
+    k = int(n_ref / (4 n_orig)) when n_ref > 4 n_orig, else every point."""
+    if num_refined > 4 * num_original:
+        k = int(num_refined / (4 * num_original))
+        return np.arange(0, num_refined, k)
+    return np.arange(num_refined)
+
+
+def icp_inits(rotations, center_original, center_refined):
+    """The reference's initial poses: [R | c_orig - R c_ref] per rotation, then the centroid translation twice (the
+    reference lists it twice), then the identity."""
+    rotations = np.asarray(rotations, dtype=np.float64)
+    T = np.tile(np.eye(4), (len(rotations) + 3, 1, 1))
+    for i, rot in enumerate(rotations):
+        T[i, :3, :3] = rot
+        T[i, :3, 3] = center_original - rot @ center_refined
+    T[-3, :3, 3] = center_original - center_refined
+    T[-2, :3, 3] = center_original - center_refined
+    return T
+
+
+def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refined: np.ndarray, rotations: np.ndarray,
+                                        threshold: float) -> np.ndarray:
+    """The reference's function of the same name, statement for statement, with every ICP run on the GPU in one batch:
+    the 4x4 float64 transform (refined -> original) of the FIRST init with the highest fitness."""
+    if np.any(np.isnan(pc_xyz_original)) or np.any(np.isnan(pc_xyz_refined)):
+        raise ValueError("Point clouds contain NaN values")
+    if np.any(np.isinf(pc_xyz_original)) or np.any(np.isinf(pc_xyz_refined)):
+        raise ValueError("Point clouds contain Inf values")
+    orig = np.asarray(pc_xyz_original)
+    ref = np.asarray(pc_xyz_refined)
+    center_original = orig.mean(axis=0)   # get_centroid(., method="mean"), in the clouds' own dtype as there
+    center_refined = ref.mean(axis=0)
+    src = ref[downsample_indices(len(orig), len(ref))]
+    inits = icp_inits(rotations, center_original, center_refined)
+    res = registration_icp(src, orig, threshold, inits, max_iteration=400)
+    best = int(np.argmax(res.fitness))   # the first maximum: the reference keeps a pose only on a strictly higher fitness
+    return res.transformation[best].copy()

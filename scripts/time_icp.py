@@ -1,0 +1,66 @@
+"""Time the multi-start ICP (scorp_amd.icp) at the reference's size: a 100 k-point target, a 200 k-point source, the
+67 inits of rotations_64.npz, max_iteration = 400, r = 0.16 x the mean bounding-box edge (the alignment script's
+threshold).  Prints one JSON line: total ms per call (median of --reps after a warm-up call), iterations per init, and
+the 16-thread scipy cKDTree correspondence pass of the yardstick on the same machine.  The per-pass kernel time comes
+from a run under `rocprofv3 --kernel-trace --stats` (icp_pass_kernel / icp_solve_kernel)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--target", type=int, default=100_000)
+    ap.add_argument("--source", type=int, default=200_000)
+    ap.add_argument("--max-iteration", type=int, default=400)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--scipy-passes", type=int, default=5, help="yardstick passes to time (0: skip)")
+    a = ap.parse_args()
+    import torch
+    from scipy.spatial import cKDTree
+    from scorp_amd import icp
+    from tests import icp_reference as ref
+
+    rng = np.random.default_rng(0)
+    tgt = ref.asymmetric_object(a.target, 1).astype(np.float32)
+    R0 = ref.random_rotation(rng)
+    obj = ref.asymmetric_object(a.source, 2)
+    src = ((obj - 0.1) @ R0 + rng.normal(scale=0.002, size=obj.shape)).astype(np.float32)
+    rots = np.load(os.path.join(ROOT, "tests", "golden", "rotations_64.npz"))["rotations"]
+    inits = icp.icp_inits(rots, tgt.mean(axis=0), src.mean(axis=0))
+    r = float(np.ptp(tgt, axis=0).mean() * 0.16)
+    dev = torch.device("cuda:0")
+    S, Q = torch.tensor(src, device=dev), torch.tensor(tgt, device=dev)
+    res = icp.registration_icp(S, Q, r, inits, max_iteration=a.max_iteration)   # warm-up
+    times = []
+    for _ in range(a.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = icp.registration_icp(S, Q, r, inits, max_iteration=a.max_iteration)
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    out = {"target": len(tgt), "source": len(src), "inits": len(inits), "max_iteration": a.max_iteration, "r": r,
+           "total_ms": float(np.median(times)), "total_ms_all": [round(t, 2) for t in times],
+           "passes": int(res.iterations.max()) + 1, "iterations_per_init": res.iterations.tolist(),
+           "best_fitness": float(res.fitness.max())}
+    if a.scipy_passes > 0:
+        tree = cKDTree(tgt.astype(np.float64))
+        src64 = src.astype(np.float64)
+        ts = []
+        for j in range(a.scipy_passes):
+            t0 = time.perf_counter()
+            ref.correspondence_pass(tree, tgt.astype(np.float64), src64, inits[j], r, workers=16)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        out["scipy_pass_ms_16_threads"] = float(np.median(ts))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
