@@ -44,9 +44,14 @@ namespace {
 //     the w slots.  The products are exact and accumulate in fp32.  Range: the pixel's upstream gradients are
 //     pre-scaled by a power of two chosen per wave from the block's largest |dL/dpixel| (so v sits around 2^7 ... and
 //     the conversion saturates, RTZ, instead of overflowing), w by 2^10; the sums are unscaled by exact powers of two.
-//   * EXACT (kExact): v and w stay fp32, 16 + 16 v_mfma_f32_16x16x4_f32 per group (fp32 MFMAs run at the fp32 VALU
-//     rate and their time is paid in full, scripts/mb_mfma_valu.hip: 608 -> 128 matrix cycles per group is what the
-//     split form buys).  The parity tests compare the two forms with each other and each with the oracle.
+//   * EXACT (kExact): v and w stay fp32 and go through v_mfma_f32_4x4x1_16b_f32 (16 independent 4x4 blocks, K = 1, each
+//     with its own A and B; 8 cycles per instruction, scripts/mb_mfma_4x4.hip).  Per half-group of 8 hits, block
+//     (hit quad qb, pixel row rb) and instruction k = pixel column: A = v (w) of hit 4 qb + i at pixel (k, rb), B = column
+//     j at that pixel - {1, x, x^2, y} for v, the four upstream gradients for w - so 8 + 8 instructions per half, 32 per
+//     group (256 matrix cycles; the 16x16x4 form took 32 x 32 = 1 024, two thirds of its MACs unused).  The rows' partial
+//     sums are added across lanes (two permlane swaps, each pairing two registers, and one DPP add), with the y-weighted
+//     sums (y x v, y^2 v) formed on the way.  Products are exact fp32, accumulation fp32 (only the order changes).  The
+//     parity tests compare the two forms with each other and each with the oracle.
 // ---------------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -195,18 +200,17 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   // (1, x, y, x^2, xy, y^2 in the block frame), the following ones the upstream gradients (dL/dr, dL/dg, dL/db,
   // dL/ddepth) of the W half.
   union Frag { f16x8 v; uint4 q; uint32_t d[4]; };
-  float bb[kExact ? 16 : 1];
+  // exact form: lane = 4 b + j of the 16-block 4x4x1 MFMA, block b = (quad qb of the half-group's hits, pixel row rb)
+  const int jb = lane & 3, qb = (lane >> 2) & 1, rb = (lane >> 4) | ((lane >> 1) & 4);
+  const float ylb = (float)rb - 3.5f;
+  float bv[kExact ? 8 : 1], bw[kExact ? 8 : 1];
   Frag bh[kExact ? 1 : 4];
   if constexpr (kExact) {
 #pragma unroll
-    for (int t = 0; t < 16; t++) {   // fp32 MFMA t covers pixels t, t + 16, t + 32, t + 48
-      const int q = t + 16 * bk;
-      const float xl = (float)(q & 7) - 3.5f, yl = (float)(q >> 3) - 3.5f;
-      float v = 0.0f;
-      v = bn == 0 ? 1.0f : v; v = bn == 1 ? xl : v; v = bn == 2 ? yl : v;
-      v = bn == 3 ? xl * xl : v; v = bn == 4 ? xl * yl : v; v = bn == 5 ? yl * yl : v;
-      v = (bn >= 6 && bn <= 9) ? xs[q * 4 + ((bn - 6) & 3)] : v;
-      bb[t] = v;
+    for (int k = 0; k < 8; k++) {   // fp32 MFMA k covers pixel (k, rb) of every block
+      const float xl = (float)k - 3.5f;
+      bv[k] = jb == 0 ? 1.0f : jb == 1 ? xl : jb == 2 ? xl * xl : ylb;
+      bw[k] = xs[(8 * rb + k) * 4 + jb];
     }
   } else {
     // fp16 MFMA m covers pixels 16 bk + 4 m + j, j = 0..3: element 2j = v slot, 2j + 1 = w slot.  V columns (bn < 6) come
@@ -236,8 +240,11 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
     dpix0 *= sq; dpix1 *= sq; dpix2 *= sq; ddep *= sq; dalp *= sq;
   }
   float T = kExact ? T_final : kWScale * T_final, R = 0.0f, s_last = 0.0f, last_alpha = 0.0f;
-  const int abase = (lane & 15) * kXStride + 16 * (lane >> 4);
+  const int abase = kExact ? (4 * qb + jb) * kXStride + 8 * rb : (lane & 15) * kXStride + 16 * (lane >> 4);
   constexpr int kAStep = 4;   // dwords between the lane's four 16-byte reads
+  // exact form, the sums over the block's rows: rows rb and rb ^ 2 meet in a permlane32 swap (lane bit 5), whose two outputs
+  // hold the rows with rb bit 1 clear (y = yl_lo) / set (y = yl_lo + 2)
+  const float yl_lo = (float)(rb & 5) - 3.5f;
   float park_v[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // a group's sums, parked until flush_sums
   uint32_t park_o[4] = {det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u};
                                                 // ... and their float offsets in acc (N * 16 < 2^32, checked at the entry
@@ -277,7 +284,7 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
     const uint4 *ka1 = a_on ? &q_k[1][hv + a_slot] : reinterpret_cast<const uint4 *>(&xm[14 * kXStride + 64]);
     const uint4 *ka2 = a_on ? &q_k[2][hv + a_slot] : reinterpret_cast<const uint4 *>(&xm[15 * kXStride + 64]);
     const f32x16 ev = block_exponents(*ka0, *ka1, *ka2, basis);
-    f32x4 dd[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+    f32x4 dd[kExact ? 1 : 2] = {};
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       if (kFull || h * 8 < nslots) {   // wave-uniform
@@ -339,15 +346,50 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
         // A operands: the lane's 16 pixels are consecutive in its row, fetched as four 16-byte reads issued together
         f32x4 d = {0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (kExact) {
-          float4 av[4];
+          // block (qb, rb), MFMA k: A = v (then w) of hit 4 qb + i at pixel (k, rb), B = column jb at that pixel.  The lane's
+          // eight pixels are its row's two 16-byte runs in the v rows and the same two in the w rows.
+          float av[16];
 #pragma unroll
-          for (int t4 = 0; t4 < 4; t4++) av[t4] = *reinterpret_cast<const float4 *>(&xm[abase + kAStep * t4]);
+          for (int t4 = 0; t4 < 4; t4++)
+            *reinterpret_cast<float4 *>(&av[4 * t4]) =
+                *reinterpret_cast<const float4 *>(&xm[abase + (t4 >> 1) * 8 * kXStride + kAStep * (t4 & 1)]);
+          f32x4 dw = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-          for (int t4 = 0; t4 < 4; t4++) {
-            d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t4].x, bb[4 * t4], d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t4].y, bb[4 * t4 + 1], d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t4].z, bb[4 * t4 + 2], d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t4].w, bb[4 * t4 + 3], d, 0, 0, 0);
+          for (int k = 0; k < 8; k++) d = __builtin_amdgcn_mfma_f32_4x4x1f32(av[k], bv[k], d, 0, 0, 0);
+#pragma unroll
+          for (int k = 0; k < 8; k++) dw = __builtin_amdgcn_mfma_f32_4x4x1f32(av[8 + k], bw[k], dw, 0, 0, 0);
+          // d[i] / dw[i] at lane (jb, qb, rb): row rb's sum of column jb for hit 4 qb + i.  Sum over the eight rows: lane bit 5
+          // (permlane32 swap), bit 4 (permlane16 swap) - each swap pairs two registers, so the register count halves
+          // per step - and bit 3 (DPP).  y-weighted sums (Q) ride along: column 1 gives sum y x v, column 3 (= y) sum y^2 v.
+          // swap32: lo = (a | b) of lanes 0..31 in lanes (0..31 | 32..63), hi = the same of lanes 32..63: the rows with rb
+          // bit 1 clear / set; lo + hi is a's row sum in lanes 0..31 and b's in lanes 32..63
+          auto swap32 = [](float a, float b, float &lo, float &hi) {
+            const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+            lo = __uint_as_float(s[0]); hi = __uint_as_float(s[1]);
+          };
+          auto sum16 = [](float a, float b) {
+            const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+            return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+          };
+          float l0, h0, l1, h1, l2, h2, l3, h3;
+          swap32(d[0], d[1], l0, h0); swap32(d[2], d[3], l1, h1);
+          swap32(dw[0], dw[1], l2, h2); swap32(dw[2], dw[3], l3, h3);
+          const float s0 = l0 + h0, s1 = l1 + h1;
+          float p = sum16(s0, s1);
+          float qy = sum16(__builtin_fmaf(yl_lo, s0, h0 + h0), __builtin_fmaf(yl_lo, s1, h1 + h1));   // y = yl_lo (+ 2 in h)
+          float rw = sum16(l2 + h2, l3 + h3);
+          p += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(p), 0x128, 0xF, 0xF, true));     // row_ror:8
+          qy += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(qy), 0x128, 0xF, 0xF, true));
+          rw += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(rw), 0x128, 0xF, 0xF, true));
+          asm volatile("" : "+v"(p), "+v"(qy), "+v"(rw));   // (the adds stay in front of the branch: one v_add_f32_dpp each)
+          // hit 4 qb + 2 (lane bit 4) + (lane bit 5), column jb.  The slot's three float4 (sum v {1, x, x^2, y}, sum y v {1, x,
+          // x^2, y}, sum w {dL/dr, dL/dg, dL/db, dL/ddepth}) go to q_k[1], q_k[2] and q_col of the slot: the group's exponents
+          // and this half's recurrence are done with them, and the matrix is still needed by the next half
+          if (!(lane & 8)) {
+            const int sl = hv + h * 8 + 4 * qb + 2 * ((lane >> 4) & 1) + (lane >> 5);
+            reinterpret_cast<float *>(&q_k[1][sl])[jb] = p;
+            reinterpret_cast<float *>(&q_k[2][sl])[jb] = qy;
+            reinterpret_cast<float *>(&q_col[sl])[jb] = rw;
           }
         } else {
           Frag af[4];
@@ -356,13 +398,13 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
 #pragma unroll
           for (int m = 0; m < 4; m++) d = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[m].v, bh[m].v, d, 0, 0, 0);
         }
-        dd[h] = d;
+        if constexpr (!kExact) dd[h] = d;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();   // the next half (and the result tile) overwrite the matrix
       }
     }
-    // result tile [term][slot][column] (it reuses the matrix): lane (bn, bk) holds rows 4 bk .. 4 bk + 3 of column bn
-    if (bn < 14) {
+    // split form: result tile [term][slot][column] (it reuses the matrix): lane (bn, bk) holds rows 4 bk .. 4 bk + 3 of column bn
+    if (!kExact && bn < 14) {
 #pragma unroll
       for (int h = 0; h < 2; h++)
 #pragma unroll
@@ -380,21 +422,22 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
       const float cA = a.z * (-1.0f / kConicScale), cB = a.w * (-0.5f / kConicScale), cC = b.x * (-1.0f / kConicScale);
       const float xl = a.x, yl = a.y;
       float mm[10];
-      {
+      if constexpr (kExact) {        // (v, x v, x^2 v, y v), (., y x v, ., y^2 v), w sums
+        const float4 u0 = *reinterpret_cast<const float4 *>(&q_k[1][hv + lane]), u1 = *reinterpret_cast<const float4 *>(&q_k[2][hv + lane]),
+                     u2 = gcol[lane];
+        mm[0] = u0.x; mm[1] = u0.y; mm[2] = u0.w; mm[3] = u0.z; mm[4] = u1.y; mm[5] = u1.w;
+        mm[6] = u2.x; mm[7] = u2.y; mm[8] = u2.z; mm[9] = u2.w;
+      } else {
         const float4 u0 = *reinterpret_cast<const float4 *>(m), u1 = *reinterpret_cast<const float4 *>(m + 4),
                      u2 = *reinterpret_cast<const float4 *>(m + 8), u3 = *reinterpret_cast<const float4 *>(m + 12);
         const float4 w0 = *reinterpret_cast<const float4 *>(m2), w1 = *reinterpret_cast<const float4 *>(m2 + 4),
                      w2 = *reinterpret_cast<const float4 *>(m2 + 8), w3 = *reinterpret_cast<const float4 *>(m2 + 12);
-        if constexpr (kExact) {      // rows 0..7 carried v (columns 0..5), rows 8..15 w (columns 6..9)
-          mm[0] = u0.x; mm[1] = u0.y; mm[2] = u0.z; mm[3] = u0.w; mm[4] = u1.x; mm[5] = u1.y;
-          mm[6] = w1.z; mm[7] = w1.w; mm[8] = w2.x; mm[9] = w2.y;
-        } else {                     // first + second term; W sums = (first-term + remainder columns) of the upstream gradients
-          const float inv_w = inv_sv * (1.0f / kWScale);
-          mm[0] = (u0.x + w0.x) * inv_sv; mm[1] = (u0.y + w0.y) * inv_sv; mm[2] = (u0.z + w0.z) * inv_sv;
-          mm[3] = (u0.w + w0.w) * inv_sv; mm[4] = (u1.x + w1.x) * inv_sv; mm[5] = (u1.y + w1.y) * inv_sv;
-          mm[6] = ((u1.z + w1.z) + (u2.z + w2.z)) * inv_w; mm[7] = ((u1.w + w1.w) + (u2.w + w2.w)) * inv_w;
-          mm[8] = ((u2.x + w2.x) + (u3.x + w3.x)) * inv_w; mm[9] = ((u2.y + w2.y) + (u3.y + w3.y)) * inv_w;
-        }
+        // first + second term; W sums = (first-term + remainder columns) of the upstream gradients
+        const float inv_w = inv_sv * (1.0f / kWScale);
+        mm[0] = (u0.x + w0.x) * inv_sv; mm[1] = (u0.y + w0.y) * inv_sv; mm[2] = (u0.z + w0.z) * inv_sv;
+        mm[3] = (u0.w + w0.w) * inv_sv; mm[4] = (u1.x + w1.x) * inv_sv; mm[5] = (u1.y + w1.y) * inv_sv;
+        mm[6] = ((u1.z + w1.z) + (u2.z + w2.z)) * inv_w; mm[7] = ((u1.w + w1.w) + (u2.w + w2.w)) * inv_w;
+        mm[8] = ((u2.x + w2.x) + (u3.x + w3.x)) * inv_w; mm[9] = ((u2.y + w2.y) + (u3.y + w3.y)) * inv_w;
       }
       if constexpr (kColorOnly) {
         *reinterpret_cast<float4 *>(m) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
