@@ -173,6 +173,56 @@ __device__ __forceinline__ void for_each_tile(int x0, int y0, int x1, int y1, ui
   }
 }
 
+// The (Gaussian, tile) pairs of a binned Gaussian, and the rank of tile (tx, ty) among them.  Both follow for_each_tile's
+// order (the set bits of the mask, or the whole rectangle row by row): a Gaussian's deterministic rows are numbered
+// pair_base[i] + pair_rank, with pair_base the prefix of pairs_of (binning.hip).
+__device__ __forceinline__ uint32_t pairs_of(const BinRec &br, uint64_t mask) {
+  if ((br.radius & kRadiusMask) == 0) return 0u;
+  return mask == kMaskAll ? (uint32_t)((br.x1 - br.x0) * (br.y1 - br.y0)) : (uint32_t)__builtin_popcountll(mask);
+}
+__device__ __forceinline__ uint32_t pair_rank(const BinRec &br, uint64_t mask, int tx, int ty) {
+  return mask == kMaskAll ? (uint32_t)((ty - br.y0) * (br.x1 - br.x0) + (tx - br.x0))
+                          : (uint32_t)__builtin_popcountll(mask & ((1ull << ((ty - br.y0) * 8 + (tx - br.x0))) - 1ull));
+}
+
+// One wave per 8x8 pixel block (the blend kernels and the mask vote).  A tile's four blocks (quad: x = quad & 1,
+// y = quad >> 1) are numbered onto the same XCD: workgroup w takes tile ((w >> 3) >> 2) * 8 + (w & 7) and quad
+// (w >> 3) & 3, so the grid covers the tiles padded to a multiple of eight.
+inline int block_wave_grid(int tiles) { return ((tiles + 7) / 8) * 8 * 4; }
+struct BlockWave {
+  int tile, quad;
+  int bx, by;   // the block's first pixel
+  int tx, ty;   // the tile's column and row
+};
+// false: a padding wave past the last tile
+__device__ __forceinline__ bool block_wave(int tiles, int tiles_x, BlockWave &w) {
+  const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
+  w.tile = (kk >> 2) * 8 + xcd;
+  w.quad = kk & 3;
+  if (w.tile >= tiles) return false;
+  // (the origin before tx / ty: in this order the forward blend kernels compile to the instructions they had when each
+  // decoded its block itself)
+  w.bx =(w.tile % tiles_x) * kTile + (w.quad & 1) * 8;
+  w.by = (w.tile / tiles_x) * kTile + (w.quad >> 1) * 8;
+  w.tx = w.tile % tiles_x;
+  w.ty = w.tile / tiles_x;
+  return true;
+}
+
+// A tile's list in the pair buffer (tile_start holds one (start, end) pair per tile on both binning paths), clamped to
+// the reservation: a view that overflowed it works on what fits
+struct TileRange { uint32_t beg, end; };
+__device__ __forceinline__ TileRange tile_range(const uint32_t *tile_start, int tile, uint32_t capacity) {
+  return {min(tile_start[2 * tile], capacity), min(tile_start[2 * tile + 1], capacity)};
+}
+
+// The block's hit list, left by the blend forward in the pair buffer for the backward and the vote: hits[quad][capacity],
+// the block's entries at its tile's range
+template <typename T>
+__device__ __forceinline__ T *block_hit_list(T *hits, int quad, uint32_t capacity, uint32_t beg) {
+  return hits + (size_t)quad * capacity + beg;
+}
+
 // Host side: calls f(std::integral_constant<int, D>{}, std::bool_constant<S>{}) with D = the SH degree (3 for anything
 // above 2) and S = split SH layout, so that f can launch kernel<D, S>.  The calls are written split first, degrees 0..3,
 // then not split: the order in which the per-Gaussian kernels are instantiated (and emitted).
@@ -221,9 +271,6 @@ inline int bin_blocks(int N, int tiles) {
 constexpr int kCellTiles = 4;
 constexpr int kCellShift = 28;          // level-one keys: tile-in-cell index in bits 28..31 of the low word
 constexpr int kMaxCells = 8192;         // the scatter's prologue scans this many bin totals (8 per thread)
-#ifndef SCORP_TWO_LEVEL_MIN_N
-#define SCORP_TWO_LEVEL_MIN_N 0
-#endif
 // Fewer cells than this: the one-level kernels.  The second level runs ONE workgroup per cell (expand_cells_kernel) and the
 // first level's LDS atomics land on `cells` counters: a 256 x 256 image has 16 cells - sixteen workgroups would move every
 // pair of a 100 k-Gaussian object while 240 CUs idle (the advisor's round-5 finding; profiles/r06_small_image_binning.txt
@@ -292,7 +339,7 @@ struct StateLayout {
     lds_binning = tiles <= 64 * kMaxLdsTiles;   // (beyond: the global-atomic fallback; 150 M pixels)
     // (stacked views too: the V x N virtual Gaussians of the stacked image are binned in ONE pass - a cell that straddles two
     // views' bands is only a bucket - instead of V passes with a tile histogram each and a one-workgroup scan of all tiles)
-    two_level = lds_binning && N < (1 << kCellShift) && N >= SCORP_TWO_LEVEL_MIN_N && cells <= kMaxCells &&
+    two_level = lds_binning && N < (1 << kCellShift) && cells <= kMaxCells &&
                 cells >= two_level_min_cells() && !one_level_binning_forced();
     if (views > 1 && !two_level) {
       // (a view's blocks write only the view's segment of their histogram row, so nb is the number of blocks PER VIEW; more
@@ -325,7 +372,7 @@ struct PairLayout {
 
 // Scratch of the deterministic backward (SCORP_BACKWARD_DETERMINISTIC), 3-D and 2-D:
 // [accumulator rows][pair_base N + 1][block sums of the scan][one flag byte per row][4 x capacity rows of row_floats floats]
-constexpr int kPairScanBlock = 1024;   // Gaussians per workgroup of the pair-count scan (gs3d_backward.hip)
+constexpr int kPairScanBlock = 1024;   // Gaussians per workgroup of the pair-count scan (binning.hip)
 struct DetLayout {
   size_t acc, pair_base, block_sums, flags, partial, total;
   int scan_blocks;
@@ -346,9 +393,17 @@ inline size_t backward_scratch_bytes(int N, uint64_t capacity, uint32_t flags, i
   if (flags & SCORP_BACKWARD_DETERMINISTIC) return DetLayout(N, capacity, row_floats).total;
   return align_up((size_t)(N > 0 ? N : 1) * row_floats * sizeof(float), 256);
 }
-int launch_pair_base(int N, const BinRec *bin, const uint64_t *tile_mask, uint32_t *block_sums, uint32_t *pair_base,
-                     hipStream_t stream);
-// acc[i] = the flagged partial rows of Gaussian i added in a fixed order (gs3d_backward.hip instantiates <16, 10, 16> for
+// The deterministic rows of the backward and the mask vote in a scratch block laid out by DetLayout(N, capacity,
+// row_floats): the row flags cleared and pair_base[N + 1] formed from the binning's tile rectangles and masks (binning.hip).
+// The caller's blend then writes the rows of pair ordinal pair_base[i] + pair_rank and launch_reduce_pair_rows adds them.
+struct PairRows {
+  float *acc, *partial;
+  uint8_t *flags;
+  uint32_t *pair_base;
+};
+int setup_pair_rows(const StateLayout &L, const void *state, int N, uint64_t capacity, int row_floats, void *scratch, int debug,
+                    hipStream_t stream, PairRows *rows);
+// acc[i] = the flagged partial rows of Gaussian i added in a fixed order (binning.hip instantiates <16, 10, 16> for
 // 3DGS, <20, 20, 32> for 2DGS and <16, 16, 16> for the mask vote)
 template <int kStride, int kUsed, int kLanes>
 void launch_reduce_pair_rows(int N, const uint32_t *pair_base, uint32_t capacity, const uint8_t *row_flags, const float *partial,
@@ -448,7 +503,7 @@ __device__ __forceinline__ float adam_ld1(const float *p) { return __builtin_non
 __device__ __forceinline__ void adam_st1(float *p, float x) { __builtin_nontemporal_store(x, p); }
 #endif
 
-// ---- binning shared by the 3DGS and 2DGS paths (gs3d_forward.hip) ----
+// ---- binning shared by the 3DGS and 2DGS paths (binning.hip) ----
 int bin_count_and_scan(const StateLayout &L, char *state_base, int N, int debug, hipStream_t stream);
 int bin_scatter_and_sort(const StateLayout &L, const PairLayout &P, char *state_base, char *pairs_base, int N,
                          uint32_t capacity, int debug, hipStream_t stream, uint32_t *header_copy = nullptr);
@@ -483,7 +538,7 @@ void set_error(const char *fmt, ...);
     }                                                                                             \
   } while (0)
 
-// ---- the host pipeline shared by the 3DGS and 2DGS paths (gs3d_forward.hip, and the templates below) ----
+// ---- the host pipeline shared by the 3DGS and 2DGS paths (api.hip, and the templates below) ----
 // What differs between the two kinds, apart from the launches each passes in.
 struct GsKind {
   bool mode2d;          // StateLayout of the 2DGS records and per-pixel state
@@ -568,42 +623,32 @@ int backward_pass(const GsKind &K, const ScorpGs3dInputs *in, const void *state,
   }
   const StateLayout L(N, in->image_width, in->image_height, K.mode2d);
   const PairLayout P(capacity);
-  const char *base = (const char *)state;
-  float *acc = (float *)scratch, *partial = nullptr;
-  uint8_t *row_flags = nullptr;
-  uint32_t *pair_base = nullptr;
+  PairRows rows = {(float *)scratch, nullptr, nullptr, nullptr};
   if (det) {
-    const DetLayout DL(N, capacity, K.acc_stride);
-    char *p = (char *)scratch;
-    partial = (float *)(p + DL.partial);
-    row_flags = (uint8_t *)(p + DL.flags);
-    pair_base = (uint32_t *)(p + DL.pair_base);
-    SCORP_HIP_CHECK(hipMemsetAsync(row_flags, 0, (size_t)(capacity > 0 ? capacity : 1) * 4, stream));
-    launch_pair_base(N, (const BinRec *)(base + L.bin), (const uint64_t *)(base + L.tile_mask), (uint32_t *)(p + DL.block_sums),
-                     pair_base, stream);
-    SCORP_KERNEL_CHECK("pair_base", in->debug, stream);
+    if (int e = setup_pair_rows(L, state, N, capacity, K.acc_stride, scratch, in->debug, stream, &rows)) return e;
   } else if (!(flags & SCORP_BACKWARD_SCRATCH_ZEROED)) {
-    SCORP_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)N * K.acc_stride * sizeof(float), stream));
+    SCORP_HIP_CHECK(hipMemsetAsync(rows.acc, 0, (size_t)N * K.acc_stride * sizeof(float), stream));
   }
   {
     ProfScope prof(K.prof_blend_backward, stream);
-    blend(L, P, acc, partial, row_flags, pair_base);
+    blend(L, P, rows.acc, rows.partial, rows.flags, rows.pair_base);
   }
   SCORP_KERNEL_CHECK("blend_backward", in->debug, stream);
   if (det) {
-    K.reduce_pair_rows(N, pair_base, (uint32_t)capacity, row_flags, partial, acc, stream);
+    K.reduce_pair_rows(N, rows.pair_base, (uint32_t)capacity, rows.flags, rows.partial, rows.acc, stream);
     SCORP_KERNEL_CHECK("reduce_pair_rows", in->debug, stream);
   }
   {
     ProfScope prof(K.prof_preprocess_backward, stream);
-    per_gaussian(L, acc);
+    per_gaussian(L, rows.acc);
   }
   SCORP_KERNEL_CHECK("preprocess_backward", in->debug, stream);
   return SCORP_OK;
 }
 
 // debug entry points: the N records (rec_bytes each) and BinRecs of a preprocessed state copied to host memory, one block
-// that *rec points to and the caller frees (NULL when N <= 0); the tile lists in raster order, for both kinds
+// that *rec points to and the caller frees (NULL when N <= 0; api.hip); the tile lists in raster order, for both kinds
+// (binning.hip)
 int copy_geom_to_host(const void *state, const StateLayout &L, int N, size_t rec_bytes, void **rec, const BinRec **bin,
                       hipStream_t stream);
 int debug_tiles(bool mode2d, const void *state, const void *pairs, uint64_t capacity, int N, int W, int H, uint32_t *tile_start,

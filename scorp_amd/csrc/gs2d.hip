@@ -4,7 +4,7 @@
 // color[3,H,W], radii[N], allmap[7,H,W]; channel order :131-148).  Arithmetic follows oracle/gs2d_oracle.c: each
 // surfel is a 3x3 matrix T (rows Tu,Tv,Tw) mapping its local (u,v,1) to (x*w, y*w, w) in pixels; a pixel intersects
 // the surfel plane in uv space, alpha = o * exp(-0.5 * min(u^2+v^2, 2*|pixel - centre|^2)).
-// Binning / per-tile depth sort are the 3DGS ones (common.hpp); tiles and 8x8 pixel blocks are culled by the exact
+// Binning / per-tile depth sort are the 3DGS ones (binning.hip); tiles and 8x8 pixel blocks are culled by the exact
 // footprint of {alpha >= 1/255} (an ellipse united with the low-pass disc).
 #include <stdlib.h>
 
@@ -289,24 +289,23 @@ blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint3
   __shared__ float2 q5[k2FRing];                                                          // (g, b)
   __shared__ __attribute__((aligned(16))) uint32_t q_pos[k2FRing];
   const int lane = threadIdx.x;
-  const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
-  const int tile = (kk >> 2) * 8 + xcd, quad = kk & 3;
-  if (tile >= tiles) return;
-  const int bx = (tile % tiles_x) * kTile + (quad & 1) * 8, by = (tile / tiles_x) * kTile + (quad >> 1) * 8;
+  BlockWave blk;
+  if (!block_wave(tiles, tiles_x, blk)) return;
+  const int tile = blk.tile, quad = blk.quad, bx = blk.bx, by = blk.by;
   const int px = bx + (lane & 7), py = by + (lane >> 3);
   const bool inside = px < W && py < H;
   const float pxf = (float)px, pyf = (float)py;
   const float bx0 = (float)bx, bx1 = (float)(bx + 7), by0 = (float)by, by1 = (float)(by + 7);
   const float bxc = (float)bx + 3.5f, byc = (float)by + 3.5f;                    // the linear form's expansion point (surfel_lin)
   const float qxb = (float)(lane & 7) - 3.5f, qyb = (float)(lane >> 3) - 3.5f;   // this pixel about it
-  const uint32_t beg = min(tile_start[2 * tile], capacity), end = min(tile_start[2 * tile + 1], capacity);   // (start, end) per tile
-  const uint32_t n = end - beg;
+  const TileRange tr = tile_range(tile_start, tile, capacity);
+  const uint32_t beg = tr.beg, n = tr.end - tr.beg;
   const float fn = kFarZ / (kFarZ - kNearZ);
   float T = inside ? 1.0f : -1.0f, C0 = 0, C1 = 0, C2 = 0, N0 = 0, N1 = 0, N2 = 0, Dp = 0, M1 = 0, M2 = 0, dist = 0, med = 0;
   uint32_t last = 0, med_c = 0;
   int head = 0, count = 0;
   uint32_t nh = 0;   // hits found so far (wave-uniform): a hit's 1-based position in the block's hit list is its `pos`
-  uint32_t *my_hits = hits + (size_t)quad * capacity + beg;
+  uint32_t *my_hits = block_hit_list(hits, quad, capacity, beg);
   // The chunk's gathers (list entry -> 96-byte record) are dependent loads; software-pipelined: while chunk c is blended
   // the records of chunk c+1 and the list entries of chunk c+2 are in flight.  The entries that pass the footprint test
   // are left for the backward as the block's HIT LIST (ids, compacted, in blend order) in the pair buffer's key region
@@ -525,8 +524,8 @@ constexpr int k2BChunk = SCORP_2D_BCHUNK;   // hits staged per chunk: 32 (the st
 //     reference's arithmetic would carry.  The fp32 MFMA runs at the vector rate (34 cycles each): this
 //     form pays 8 of them per hit where the split form pays 2 fp16 ones, and saves the split's ~40 instructions.
 //   * kDet (SCORP_BACKWARD_DETERMINISTIC): the twenty sums of a (block, hit) leave as one plain row
-//     partial[4 * pair + block] (pair = the (surfel, tile) pair's ordinal in surfel-major order, gs3d_backward.hip) with a
-//     flag byte; reduce_pair_rows_kernel (gs3d_backward.hip) adds a surfel's rows in a fixed order.  No float atomics.
+//     partial[4 * pair + block] (pair = the (surfel, tile) pair's ordinal in surfel-major order, pair_rank in common.hpp)
+//     with a flag byte; reduce_pair_rows_kernel (binning.hip) adds a surfel's rows in a fixed order.  No float atomics.
 template <bool kHasMap, bool kExact = false, bool kDet = false>
 __global__ void __launch_bounds__(64, SCORP_2D_BWAVES)
 blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ point_list,
@@ -549,17 +548,16 @@ blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint
   float *dbuf = reinterpret_cast<float *>(xm2);
   static_assert(16 * k2DStride <= 16 * k2XStride && 64 * 6 <= 16 * k2XStride, "the result tile and the prologue scratch fit the matrix");
   const int lane = threadIdx.x;
-  const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
-  const int tile = (kk >> 2) * 8 + xcd, quad = kk & 3;
-  if (tile >= tiles) return;
-  const int bx = (tile % tiles_x) * kTile + (quad & 1) * 8, by = (tile / tiles_x) * kTile + (quad >> 1) * 8;
+  BlockWave blk;
+  if (!block_wave(tiles, tiles_x, blk)) return;
+  const int tile = blk.tile, quad = blk.quad, bx = blk.bx, by = blk.by;
   const int px = bx + (lane & 7), py = by + (lane >> 3);
   const bool inside = px < W && py < H;
   const float pxf = (float)px, pyf = (float)py;
   const float bxc = (float)bx + 3.5f, byc = (float)by + 3.5f;                    // the linear form's expansion point (surfel_lin)
   const float qxb = (float)(lane & 7) - 3.5f, qyb = (float)(lane >> 3) - 3.5f;   // this pixel about it
-  const uint32_t beg = min(tile_start[2 * tile], capacity), end = min(tile_start[2 * tile + 1], capacity);   // (start, end) per tile
-  if (end == beg) return;
+  const TileRange tr = tile_range(tile_start, tile, capacity);
+  if (tr.end == tr.beg) return;
   const size_t HW = (size_t)H * W, pix = (size_t)py * W + px;
   // all of the pixel's loads are issued together; pixels nothing was blended into drop their upstream gradient
   // afterwards by a select (it may be NaN)
@@ -713,7 +711,7 @@ blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint
   // w * 2^10 <= 2^15.
   // gathers software-pipelined two chunks deep over the block's hit list (left by the forward), back to front: lane l of
   // the chunk that starts dn hits from the end takes the hit at 0-based position todo - 1 - dn - l
-  const uint32_t *my_hits = hits + (size_t)quad * capacity + beg;
+  const uint32_t *my_hits = block_hit_list(hits, quad, capacity, tr.beg);
   auto fetch_idx = [&](uint32_t dn, bool &hit_, uint32_t &id_) {
     hit_ = lane < k2BChunk && dn + lane < todo;
     id_ = hit_ ? my_hits[todo - 1 - dn - lane] : 0u;
@@ -746,15 +744,11 @@ blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint
       q5[qi] = make_float2(r4.x, r4.y);
       float sh_stage = 1.0f, ish_stage = 1.0f;
       if constexpr (kDet) {
-        // the (surfel, tile) pair's ordinal, surfel-major: pair_base[id] + the rank of this tile among the tiles the surfel
-        // reaches (for_each_tile's order: the set bits of its mask, or its whole rectangle row by row)
+        // the (surfel, tile) pair's ordinal, surfel-major (pair_rank)
         const uint4 raw = reinterpret_cast<const uint4 *>(bin)[id];
         const BinRec br = *reinterpret_cast<const BinRec *>(&raw);
         const uint64_t mk = tile_mask[id];
-        const int tx = tile % tiles_x, ty = tile / tiles_x;
-        const uint32_t rank = mk == kMaskAll ? (uint32_t)((ty - br.y0) * (br.x1 - br.x0) + (tx - br.x0))
-                                             : (uint32_t)__builtin_popcountll(mk & ((1ull << ((ty - br.y0) * 8 + (tx - br.x0))) - 1ull));
-        q_id[qi] = pair_base[id] + rank;
+        q_id[qi] = pair_base[id] + pair_rank(br, mk, blk.tx, blk.ty);
       } else {
         q_id[qi] = id;
       }
@@ -1197,7 +1191,7 @@ int scorp::render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, ui
   {
     ProfScope prof(kKBlendForward2d, stream);
     auto bk = for_backward ? blend2d_forward_wave_kernel<true> : blend2d_forward_wave_kernel<false>;
-    bk<<<(L.tiles + 7) / 8 * 32, 64, 0, stream>>>(
+    bk<<<block_wave_grid(L.tiles), 64, 0, stream>>>(
         (const uint32_t *)(f.base + L.tile_start), (const uint32_t *)(f.pb + f.P.list), (const Surfel *)(f.base + L.rec),
         f.capacity, f.W, f.H, L.tiles_x, L.tiles, in->bg, out_color, out_allmap, (float *)(f.base + L.final_T),
         (uint32_t *)(f.base + L.n_contrib), (uint32_t *)(f.pb + f.P.hits));
@@ -1242,7 +1236,7 @@ int scorp::backward2d_impl(const ScorpGs3dInputs *in, const void *state, const v
                            : (map ? blend2d_backward_wave_kernel<true, false, true> : blend2d_backward_wave_kernel<false, false, true>))
                   : (exact ? (map ? blend2d_backward_wave_kernel<true, true, false> : blend2d_backward_wave_kernel<false, true, false>)
                            : (map ? blend2d_backward_wave_kernel<true, false, false> : blend2d_backward_wave_kernel<false, false, false>));
-    wk<<<(L.tiles + 7) / 8 * 32, 64, 0, stream>>>(
+    wk<<<block_wave_grid(L.tiles), 64, 0, stream>>>(
         (const uint32_t *)(base + L.tile_start), (const uint32_t *)(pb + P.list), (const Surfel *)(base + L.rec),
         (uint32_t)capacity, in->image_width, in->image_height, L.tiles_x, L.tiles, in->bg, (const float *)(base + L.final_T),
         (const uint32_t *)(base + L.n_contrib), dL_dcolor, dL_dallmap, acc, (const uint32_t *)(pb + P.hits), partial, row_flags,

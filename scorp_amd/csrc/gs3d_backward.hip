@@ -141,11 +141,9 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
                 sizeof(uint4) * 3 * kChunk + sizeof(float4) * 2 * kChunk + sizeof(float2) * kChunk + 4 * kChunk + 4 * 16 * kXStride == 10240,
                 "10 KiB of LDS per wave: four waves per SIMD fill the CU's 160 KiB exactly");
   const int lane = threadIdx.x;
-  const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
-  const int tile = (kk >> 2) * 8 + xcd, quad = kk & 3;
-  if (tile >= tiles) return;
-  const int tx0 = (tile % tiles_x) * kTile, ty0 = (tile / tiles_x) * kTile;
-  const int bx = tx0 + (quad & 1) * 8, by = ty0 + (quad >> 1) * 8;
+  BlockWave blk;
+  if (!block_wave(tiles, tiles_x, blk)) return;
+  const int quad = blk.quad, bx = blk.bx, by = blk.by;
   const int px = bx + (lane & 7), py = by + (lane >> 3);
   const bool inside = px < W && py < H;
   const float cx = (float)bx + 3.5f, cy = (float)by + 3.5f;  // block-frame origin of the exponent's coefficients and of the moments
@@ -155,11 +153,11 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   const bool a_on = a_operand_active(lane);
   const int a_slot = a_operand_slot(lane);
   if (lane < 3) *reinterpret_cast<uint4 *>(&xm[(13 + lane) * kXStride + 64]) = make_uint4(0u, 0u, 0u, 0u);
-  const uint32_t beg = min(tile_start[2 * tile], capacity), end = min(tile_start[2 * tile + 1], capacity);   // (start, end) per tile
+  const TileRange tr = tile_range(tile_start, blk.tile, capacity);
   // deterministic mode: the sums leave as plain rows partial[4 * pair + quad], pair = the (Gaussian, tile) pair's ordinal
   // in GAUSSIAN-major order (pair_base[id] + the tile's rank in the Gaussian's tile mask), with a flag byte per row
   constexpr bool det = kDet;
-  if (end == beg) return;
+  if (tr.end == tr.beg) return;
   const size_t HW = (size_t)H * W, pix = (size_t)py * W + px;
   // all of the pixel's loads are issued together (no load waits on `last`); pixels nothing was blended into drop
   // their upstream gradient afterwards by a select (it may be NaN: depth / alpha at empty pixels)
@@ -489,7 +487,7 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   // per SIMD nothing hides them, so they are software-pipelined two chunks deep: while chunk c is replayed the records
   // of chunk c+1 and the list entries of chunk c+2 are already in flight.  Chunk c holds the hits at 0-based positions
   // todo - 64 c - 1 (slot 0) down to todo - 64 c - 64 (slot 63): slots ascend back to front.
-  const uint32_t *my_hits = hits + (size_t)quad * capacity + beg;
+  const uint32_t *my_hits = block_hit_list(hits, quad, capacity, tr.beg);
   auto fetch_id = [&](uint32_t c_) {
     const int o = (int)todo - (int)(kChunk * c_) - 1 - lane;
     return o >= 0 ? my_hits[o] : 0xFFFFFFFFu;
@@ -519,15 +517,11 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
       q_t0[lane] = make_float4(a.x - cx, a.y - cy, a.z, a.w);
       q_t1[lane] = make_float2(b.x, c.w);
       if constexpr (det) {
-        // the (Gaussian, tile) pair's ordinal, Gaussian-major: pair_base[id] + the rank of this tile among the tiles the
-        // Gaussian reaches (for_each_tile's order: the set bits of its mask, or its whole rectangle row by row)
+        // the (Gaussian, tile) pair's ordinal, Gaussian-major (pair_rank)
         const uint4 raw = reinterpret_cast<const uint4 *>(bin)[id];
         const BinRec br = *reinterpret_cast<const BinRec *>(&raw);
         const uint64_t mk = tile_mask[id];
-        const int tx = tile % tiles_x, ty = tile / tiles_x;
-        const uint32_t rank = mk == kMaskAll ? (uint32_t)((ty - br.y0) * (br.x1 - br.x0) + (tx - br.x0))
-                                             : (uint32_t)__builtin_popcountll(mk & ((1ull << ((ty - br.y0) * 8 + (tx - br.x0))) - 1ull));
-        q_id[lane] = pair_base[id] + rank;
+        q_id[lane] = pair_base[id] + pair_rank(br, mk, blk.tx, blk.ty);
       } else {
         q_id[lane] = id;
       }
@@ -547,133 +541,7 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   }
   flush_sums();
 }
-
-
-// ---------------------------------------------------------------------------------------------------------
-// Deterministic mode.  The rows are addressed by the (Gaussian, tile) pair's ordinal in Gaussian-major order, so the rows
-// of one Gaussian are CONTIGUOUS - partial[4 * pair_base[i] ... 4 * pair_base[i + 1]) - and the ordered per-Gaussian sum
-// is a streaming read with no search (round 3 found a Gaussian's row in every block's depth-sorted hit list by binary
-// search: ~190 dependent loads per Gaussian, 2.7 ms of a 3.5 ms view).
-//   pair_count_kernel / pair_base_kernel : pair_base[i] = number of (Gaussian, tile) pairs of the Gaussians before i
-//                                          (a two-level exclusive scan of the tile counts the binning used)
-//   reduce_pair_rows_kernel              : kLanes lanes per Gaussian (lane = float of a row) add the flagged rows in the
-//                                          fixed order tiles of the mask x blocks 0..3 (the 3-D rows and the 2-D ones)
-// ---------------------------------------------------------------------------------------------------------
-constexpr int kScanBlock = kPairScanBlock;   // Gaussians per workgroup of the pair-count scan
-__device__ __forceinline__ uint32_t pairs_of(const BinRec &br, uint64_t mask) {
-  if ((br.radius & kRadiusMask) == 0) return 0u;
-  return mask == kMaskAll ? (uint32_t)((br.x1 - br.x0) * (br.y1 - br.y0)) : (uint32_t)__builtin_popcountll(mask);
-}
-__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t *s_red) {   // 256 threads
-  for (int off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
-__global__ void __launch_bounds__(256)
-pair_count_kernel(int N, const BinRec *__restrict__ bin, const uint64_t *__restrict__ tile_mask, uint32_t *__restrict__ block_sums) {
-  __shared__ uint32_t s_red[4];
-  uint32_t v = 0;
-  for (int k = 0; k < kScanBlock / 256; k++) {
-    const int i = blockIdx.x * kScanBlock + k * 256 + threadIdx.x;
-    if (i < N) {
-      const uint4 raw = reinterpret_cast<const uint4 *>(bin)[i];
-      v += pairs_of(*reinterpret_cast<const BinRec *>(&raw), tile_mask[i]);
-    }
-  }
-  v = block_sum_u32(v, s_red);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = v;
-}
-__global__ void __launch_bounds__(256)
-pair_base_kernel(int N, const BinRec *__restrict__ bin, const uint64_t *__restrict__ tile_mask,
-                 const uint32_t *__restrict__ block_sums, uint32_t *__restrict__ pair_base) {
-  __shared__ uint32_t s_red[4], s_wave[4];
-  // the pairs of the workgroups before this one (at most ~1000 words for a million Gaussians: every workgroup adds them itself)
-  uint32_t before = 0;
-  for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) before += block_sums[b];
-  uint32_t run = block_sum_u32(before, s_red);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int k = 0; k < kScanBlock / 256; k++) {
-    const int i = blockIdx.x * kScanBlock + k * 256 + threadIdx.x;
-    uint32_t c = 0;
-    if (i < N) {
-      const uint4 raw = reinterpret_cast<const uint4 *>(bin)[i];
-      c = pairs_of(*reinterpret_cast<const BinRec *>(&raw), tile_mask[i]);
-    }
-    uint32_t inc = c;   // inclusive prefix inside the wave
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)inc, off, 64);
-      if (lane >= off) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < wv; w++) wbase += s_wave[w];
-    if (i < N) pair_base[i] = run + wbase + inc - c;
-    run += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) pair_base[N] = run;
-}
-
-// rows of kStride floats, of which the first kUsed are summed (the rest of the accumulator row is written as zeros)
-template <int kStride, int kUsed, int kLanes>
-__global__ void __launch_bounds__(256)
-reduce_pair_rows_kernel(int N, const uint32_t *__restrict__ pair_base, uint32_t capacity, const uint8_t *__restrict__ row_flags,
-                        const float *__restrict__ partial, float *__restrict__ acc) {
-  const int i = blockIdx.x * (256 / kLanes) + (threadIdx.x / kLanes), col = threadIdx.x % kLanes;
-  if (i >= N || col >= kStride) return;
-  const uint32_t r0 = min(pair_base[i], capacity) * 4u, r1 = min(pair_base[i + 1], capacity) * 4u;
-  float sum = 0.0f;
-  // four (Gaussian, tile) pairs = sixteen rows per step: the four flag words first, then every flagged row, all loads in
-  // flight together (a Gaussian has 2.4 pairs on average: one step); the additions keep the fixed order pair, block
-  for (uint32_t r = r0; r < r1; r += 16) {
-    uint32_t f[4];
-#pragma unroll
-    for (int p = 0; p < 4; p++) f[p] = r + 4 * p < r1 ? *reinterpret_cast<const uint32_t *>(row_flags + r + 4 * p) : 0u;
-    float v[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const bool on = (f[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-      v[k] = on ? partial[(size_t)(r + k) * kStride + col] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) sum += v[k];   // (an absent row adds an exact zero)
-  }
-  acc[(size_t)i * kStride + col] = col < kUsed ? sum : 0.0f;
-}
-
 }  // namespace
-}  // namespace scorp
-
-// pair_base[i] = the number of (Gaussian, tile) pairs of the Gaussians before i (pair_base[N] = all of them), from the tile
-// rectangles / masks the binning used; shared by the 3-D and the 2-D deterministic backward (the 2-D state holds the same
-// BinRec / tile-mask arrays)
-int scorp::launch_pair_base(int N, const BinRec *bin, const uint64_t *tile_mask, uint32_t *block_sums, uint32_t *pair_base,
-                            hipStream_t stream) {
-  const int blocks = (N + kScanBlock - 1) / kScanBlock;
-  pair_count_kernel<<<blocks, 256, 0, stream>>>(N, bin, tile_mask, block_sums);
-  pair_base_kernel<<<blocks, 256, 0, stream>>>(N, bin, tile_mask, block_sums, pair_base);
-  return SCORP_OK;
-}
-
-namespace scorp {
-template <int kStride, int kUsed, int kLanes>
-void launch_reduce_pair_rows(int N, const uint32_t *pair_base, uint32_t capacity, const uint8_t *row_flags,
-                             const float *partial, float *acc, hipStream_t stream) {
-  constexpr int per_block = 256 / kLanes;
-  reduce_pair_rows_kernel<kStride, kUsed, kLanes><<<(N + per_block - 1) / per_block, 256, 0, stream>>>(
-      N, pair_base, capacity, row_flags, partial, acc);
-}
-// 3DGS: ten floats of a 16-float row; 2DGS: the whole 20-float row (kAcc2Stride, gs2d.hip)
-template void launch_reduce_pair_rows<kAccStride, 10, 16>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
-                                                          hipStream_t);
-template void launch_reduce_pair_rows<20, 20, 32>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
-                                                  hipStream_t);
-// the mask vote (mask_vote.hip): sixteen sums per row, all of them used
-template void launch_reduce_pair_rows<16, 16, 16>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
-                                                  hipStream_t);
 }  // namespace scorp
 
 using namespace scorp;
@@ -709,7 +577,7 @@ int scorp::backward3d_impl(const ScorpGs3dInputs *in, const void *state, const v
   hipStream_t stream = (hipStream_t)stream_;
   const char *base = (const char *)state, *pb = (const char *)pairs;
   auto blend = [&](const StateLayout &L, const PairLayout &P, float *acc, float *partial, uint8_t *row_flags, uint32_t *pair_base) {
-    const int blocks = ((L.tiles + 7) / 8) * 8 * 4;
+    const int blocks = block_wave_grid(L.tiles);
     const bool det = partial != nullptr, da = dL_ddepth || dL_dalpha, exact = (flags & SCORP_BACKWARD_EXACT_FP32) != 0;
     // nothing but colour gradients wanted (every geometry / opacity output NULL): the colour-only replay
     const bool adam_geom = adam && adam->on && (adam->m[0] || adam->m[3] || adam->m[4] || adam->m[5] || adam->accum);

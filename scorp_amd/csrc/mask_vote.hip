@@ -54,23 +54,21 @@ mask_vote_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_t *_
   __shared__ __attribute__((aligned(16))) float xm[kVGroup * kVStride];
   __shared__ uint32_t q_mask[64];
   const int lane = threadIdx.x;
-  const int xcd = blockIdx.x & 7, kk = blockIdx.x >> 3;
-  const int tile = (kk >> 2) * 8 + xcd, quad = kk & 3;
-  if (tile >= tiles) return;
-  const int tx = tile % tiles_x, ty = tile / tiles_x;
-  const int bx = tx * kTile + (quad & 1) * 8, by = ty * kTile + (quad >> 1) * 8;
+  BlockWave blk;
+  if (!block_wave(tiles, tiles_x, blk)) return;
+  const int quad = blk.quad, bx = blk.bx, by = blk.by;
   const int px = bx + (lane & 7), py = by + (lane >> 3);
   const bool inside = px < W && py < H;
   const float cx = (float)bx + 3.5f, cy = (float)by + 3.5f;
-  const uint32_t beg = min(tile_start[2 * tile], capacity), end = min(tile_start[2 * tile + 1], capacity);
-  if (end == beg) return;
+  const TileRange tr = tile_range(tile_start, blk.tile, capacity);
+  if (tr.end == tr.beg) return;
   const size_t HW = (size_t)H * W, pix = (size_t)py * W + px;
   uint32_t last = 0u, mbits = 0u;   // mbits: bit j = pixel inside mask k0 + j
   if (inside) {
     last = n_contrib[pix];
     for (int j = 0; j < kVoteObjects && k0 + j < num_masks; j++) mbits |= (masks[(size_t)(k0 + j) * HW + pix] != 0 ? 1u : 0u) << j;
   }
-  const uint32_t todo = min(wave_max_u32(last), end - beg);   // (wave-uniform; a hit list never outgrows its tile's list)
+  const uint32_t todo = min(wave_max_u32(last), tr.end - tr.beg);   // (wave-uniform; a hit list never outgrows its tile's list)
   if (todo == 0) return;
   // B operand.  fp32 MFMA t covers the pixels q = t + 16 bk (K index bk = lane >> 4); lane column bn = lane & 15 is object
   // k0 + bn / 2, inside (even bn) or outside (odd bn) its mask.  Objects beyond num_masks get zero columns.
@@ -93,7 +91,7 @@ mask_vote_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_t *_
   const float qxb = (float)(lane & 7) - 3.5f, qyb = (float)(lane >> 3) - 3.5f, pxf = (float)px, pyf = (float)py;
   float T = 1.0f;
   const int abase = (lane & 15) * kVStride + 16 * bk;
-  const uint32_t *my_hits = hits + (size_t)quad * capacity + beg;
+  const uint32_t *my_hits = block_hit_list(hits, quad, capacity, tr.beg);
   const SplatRec *rec3 = reinterpret_cast<const SplatRec *>(records);
   const Surfel *rec2 = reinterpret_cast<const Surfel *>(records);
 
@@ -195,14 +193,11 @@ mask_vote_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_t *_
         c0.w = guard_limit_pack(r[2].w);   // the forward's bits (exp_mfma.hpp)
         q_s[0][lane] = c0; q_s[1][lane] = c1; q_s[2][lane] = c2;
       }
-      // the (Gaussian, tile) pair's ordinal, Gaussian-major: pair_base[id] + the rank of this tile among the tiles the
-      // Gaussian reaches (for_each_tile's order), as the deterministic backward forms it
+      // the (Gaussian, tile) pair's ordinal, Gaussian-major (pair_rank), as the deterministic backward forms it
       const uint4 raw = reinterpret_cast<const uint4 *>(bin)[id];
       const BinRec br = *reinterpret_cast<const BinRec *>(&raw);
       const uint64_t mk = tile_mask[id];
-      const uint32_t rank = mk == kMaskAll ? (uint32_t)((ty - br.y0) * (br.x1 - br.x0) + (tx - br.x0))
-                                           : (uint32_t)__builtin_popcountll(mk & ((1ull << ((ty - br.y0) * 8 + (tx - br.x0))) - 1ull));
-      q_id[lane] = pair_base[id] + rank;
+      q_id[lane] = pair_base[id] + pair_rank(br, mk, blk.tx, blk.ty);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -263,28 +258,22 @@ int mask_vote_impl(bool mode2d, const ScorpGs3dInputs *in, const void *state, co
   const StateLayout L(N, W, H, mode2d);
   const PairLayout P(capacity);
   const char *base = (const char *)state, *pb = (const char *)pairs;
-  char *p = (char *)scratch;
-  float *acc = (float *)(p + DL.acc), *partial = (float *)(p + DL.partial);
-  uint8_t *row_flags = (uint8_t *)(p + DL.flags);
-  uint32_t *pair_base = (uint32_t *)(p + DL.pair_base);
-  const BinRec *bin = (const BinRec *)(base + L.bin);
-  const uint64_t *tile_mask = (const uint64_t *)(base + L.tile_mask);
-  SCORP_HIP_CHECK(hipMemsetAsync(row_flags, 0, (size_t)(capacity > 0 ? capacity : 1) * 4, stream));
-  launch_pair_base(N, bin, tile_mask, (uint32_t *)(p + DL.block_sums), pair_base, stream);
-  SCORP_KERNEL_CHECK("pair_base", in->debug, stream);
-  const int blocks = ((L.tiles + 7) / 8) * 8 * 4;
+  PairRows rows;
+  if (int e = setup_pair_rows(L, state, N, capacity, kVoteRow, scratch, in->debug, stream, &rows)) return e;
+  const int blocks = block_wave_grid(L.tiles);
   auto vk = mode2d ? mask_vote_wave_kernel<true> : mask_vote_wave_kernel<false>;
   // every pass writes the same rows (they depend on the hits, not on the masks), so the flags of the first pass stand
   for (int k0 = 0; k0 < num_masks; k0 += kVoteObjects) {
     const int kcount = min(kVoteObjects, num_masks - k0);
     vk<<<blocks, 64, 0, stream>>>((const uint32_t *)(base + L.tile_start), (const uint32_t *)(pb + P.hits), base + L.rec,
                                   (uint32_t)capacity, W, H, L.tiles_x, L.tiles, (const uint32_t *)(base + L.n_contrib), masks,
-                                  num_masks, k0, partial, row_flags, pair_base, bin, tile_mask);
+                                  num_masks, k0, rows.partial, rows.flags, rows.pair_base, (const BinRec *)(base + L.bin),
+                                  (const uint64_t *)(base + L.tile_mask));
     SCORP_KERNEL_CHECK("mask_vote", in->debug, stream);
-    launch_reduce_pair_rows<kVoteRow, kVoteRow, 16>(N, pair_base, (uint32_t)capacity, row_flags, partial, acc, stream);
+    launch_reduce_pair_rows<kVoteRow, kVoteRow, 16>(N, rows.pair_base, (uint32_t)capacity, rows.flags, rows.partial, rows.acc, stream);
     SCORP_KERNEL_CHECK("reduce_pair_rows", in->debug, stream);
     const int64_t work = (int64_t)N * kcount;
-    vote_epilogue_kernel<<<(unsigned)((work + 255) / 256), 256, 0, stream>>>(N, acc, k0, kcount, method, scale, out);
+    vote_epilogue_kernel<<<(unsigned)((work + 255) / 256), 256, 0, stream>>>(N, rows.acc, k0, kcount, method, scale, out);
     SCORP_KERNEL_CHECK("vote_epilogue", in->debug, stream);
   }
   return SCORP_OK;
