@@ -43,6 +43,7 @@ typedef void *scorp_stream_t; /* a hipStream_t (NULL = the default stream) */
 #define SCORP_ERR_INVALID (-1)   /* bad argument (NULL, size, shape) */
 #define SCORP_ERR_HIP (-2)       /* a HIP call or kernel failed */
 #define SCORP_ERR_OVERFLOW (-3)  /* the pair buffer was smaller than the number of (tile,splat) pairs */
+#define SCORP_ERR_NO_INLIERS (-4) /* scorp_pose_ransac: the best hypothesis has fewer than 3 inliers */
 
 /* The 12 fields of GaussianRasterizationSettings (gaussian_renderer/__init__.py:51-64) + the 8 call arguments. */
 typedef struct ScorpGs3dInputs {
@@ -234,6 +235,53 @@ int scorp_icp_point_to_point(const float *source, int32_t n_source, const float 
                              double relative_fitness, double relative_rmse, double *out_transformation, double *out_fitness,
                              double *out_inlier_rmse, int32_t *out_iterations, void *workspace, size_t workspace_bytes,
                              scorp_stream_t stream);
+
+/* ---- pose fit from matched 3-D point pairs (utils/solution.py: pc_align_ransac :476-557 and adam_algorithm_3d3d_9dof
+ * :363-446, called once per round and object by the alignment scripts) ----
+ * source[n_pairs, 3] and target[n_pairs, 3] are float64 device pointers, row i of one matched to row i of the other; every
+ * output is a device pointer too.  All arithmetic is float64, no float atomics: two calls give the same bits.  One
+ * workspace size serves both calls: scorp_pose_fit_workspace_bytes(n_pairs, n_hypotheses) (n_hypotheses 1 for the Adam
+ * fit), 256-byte aligned.  The inputs are only read.
+ *
+ * scorp_pose_ransac: samples[n_hypotheses, 3] int32 are the pair indices of every hypothesis, drawn by the caller (the
+ * library holds no random numbers).  Per hypothesis: Umeyama (method SCORP_POSE_UMEYAMA: cov = sum (p - pm)(q - qm)^T
+ * = U S V^T, D = diag(1, 1, det(U V^T) < 0 ? -1 : 1), R = V D U^T, s = sum(S diag D) / sum |p - pm|^2, t = qm - s R pm) or
+ * Kabsch (SCORP_POSE_KABSCH: the same with s = 1) on its three pairs, then the number of pairs with
+ * |R (s p) + t - q| < threshold (strict) into out_counts[n_hypotheses].  The winner is the FIRST hypothesis with the
+ * highest count; with min_inlier_ratio > 0 the first whose count exceeds min_inlier_ratio * n_pairs, if there is one.
+ * out_winner[2] = {its index, its count}, out_inlier_mask[n_pairs] (0 / 1) its inliers, and out_R[3, 3] (row-major),
+ * out_t[3], out_s[1] the same fit over those inliers.  A hypothesis run alone gets the count it gets in a batch.
+ * Synchronises before it returns (reads a status word).  SCORP_ERR_INVALID: n_pairs < 3, n_hypotheses outside
+ * [1, 65535], a sample index outside [0, n_pairs), threshold not finite, an unknown method, a NULL pointer, a workspace
+ * too small or misaligned (none of these launches anything but the index check, which is the fit kernel's);
+ * SCORP_ERR_NO_INLIERS: the winner has fewer than 3 inliers (the reference raises), out_R / out_t / out_s are not written.
+ *
+ * scorp_pose_adam_9dof: `iterations` steps of torch.optim.Adam (lr, betas 0.9 / 0.999, eps 1e-8) in ONE kernel launch on
+ * t[3], q[4], qo[4], l[3] with M = R(q) Ro(qo)^T diag(s) Ro(qo), s = scale_min + (scale_max - scale_min) sigmoid(l),
+ * R(q) = I + 2 B(q) / (q.q), and the loss
+ *   mean |M p + t - q|^2 + lambda_reg_scale (mean (l - 1)^2 + mean (s - mean s)^2)
+ *                        + lambda_reg_rot arccos(clamp((tr R - 1) / 2, -1, 1))^2,
+ * gradients analytic, the data term through the float64 moments of the pairs about their centroids.  Start: t = 0.01,
+ * q = (0.9, 0.01, 0.01, 0.01) (fp32-rounded, as the reference), qo = (1, 0, 0, 0), l = logit of init_scale[3] (a HOST
+ * pointer) inside the bounds; an init_scale outside [scale_min, scale_max] becomes the mid-point for all three axes.
+ * Where the rotation term has no finite derivative (|c| >= 1: R the identity or a half turn; the reference's autograd
+ * gives NaN or an infinity there) its gradient is taken as 0.  out[25] = R (9, row-major), t (3), s (3), Ro (9), the loss
+ * of the last step.  out_loss (may be NULL): the loss of steps loss_every, 2 loss_every, ... (as the reference prints
+ * it, before that step's update), at most loss_capacity values.  Does not synchronise.  SCORP_ERR_INVALID: n_pairs < 3,
+ * iterations outside [0, 1000000] (one wave runs them all: the bound keeps a call to seconds), non-finite
+ * hyper-parameters, scale_max <= scale_min, loss_every < 1 with out_loss, a NULL pointer, a workspace too small or
+ * misaligned. */
+#define SCORP_POSE_UMEYAMA 0
+#define SCORP_POSE_KABSCH 1
+size_t scorp_pose_fit_workspace_bytes(int32_t n_pairs, int32_t n_hypotheses);
+int scorp_pose_ransac(const double *source, const double *target, int32_t n_pairs, const int32_t *samples,
+                      int32_t n_hypotheses, double threshold, double min_inlier_ratio, int32_t method, double *out_R,
+                      double *out_t, double *out_s, int32_t *out_winner, int32_t *out_counts, uint8_t *out_inlier_mask,
+                      void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+int scorp_pose_adam_9dof(const double *source, const double *target, int32_t n_pairs, int32_t iterations, double lr,
+                         double lambda_reg_scale, double lambda_reg_rot, double scale_min, double scale_max,
+                         const double *init_scale, double *out, double *out_loss, int32_t loss_every, int32_t loss_capacity,
+                         void *workspace, size_t workspace_bytes, scorp_stream_t stream);
 
 /* ---- introspection for stage-level parity tests (device->host copies; synchronises) ---- */
 /* xy[N,2], depth[N], conic_opacity[N,4], rgb[N,3], rect[N,4] (tile units, max exclusive); any may be NULL. */

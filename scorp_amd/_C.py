@@ -87,12 +87,15 @@ EXPORTS = [
     "scorp_prof_enable", "scorp_prof_select", "scorp_prof_num_kernels", "scorp_prof_kernel_name", "scorp_prof_collect",
     "scorp_mask_vote_scratch_bytes", "scorp_gs3d_mask_vote", "scorp_gs2d_mask_vote",
     "scorp_icp_workspace_bytes", "scorp_icp_point_to_point",
+    "scorp_pose_fit_workspace_bytes", "scorp_pose_ransac", "scorp_pose_adam_9dof",
 ]
 
 BACKWARD_EXACT_FP32 = 1   # scorp_gs3d_backward_ex flag (include/scorp_gs.h)
 BACKWARD_SCRATCH_ZEROED = 2   # scorp_gs3d_backward_ex flag: the caller cleared the accumulator rows already
 BACKWARD_DETERMINISTIC = 4    # scorp_gs3d_backward_ex flag: no float atomics (plain partial rows + an ordered per-Gaussian sum)
 VOTE_SUMS, VOTE_GRADIENT, VOTE_BINARY = 0, 1, 2   # methods of scorp_gs3d_mask_vote / scorp_gs2d_mask_vote
+POSE_UMEYAMA, POSE_KABSCH = 0, 1   # methods of scorp_pose_ransac
+ERR_INVALID, ERR_NO_INLIERS = -1, -4   # return codes the Python layer tells apart (include/scorp_gs.h)
 
 _lib = None
 
@@ -181,6 +184,10 @@ def lib():
     L.scorp_icp_workspace_bytes.argtypes = [i32, i32, i32]
     f64 = ctypes.c_double
     L.scorp_icp_point_to_point.argtypes = [vp, i32, vp, i32, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
+    L.scorp_pose_fit_workspace_bytes.restype = sz
+    L.scorp_pose_fit_workspace_bytes.argtypes = [i32, i32]
+    L.scorp_pose_ransac.argtypes = [vp, vp, i32, vp, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.scorp_pose_adam_9dof.argtypes = [vp, vp, i32, i32, f64, f64, f64, f64, f64, ctypes.POINTER(f64), vp, vp, i32, i32, vp, sz, vp]
     L.scorp_prof_enable.argtypes = [ctypes.c_int]
     L.scorp_prof_select.argtypes = [u64]
     L.scorp_prof_kernel_name.restype = ctypes.c_char_p
