@@ -469,6 +469,57 @@ typedef struct ScorpGs3dTrainView {
 } ScorpGs3dTrainView;
 int scorp_gs3d_train_view(const ScorpGs3dTrainView *view, scorp_stream_t stream);
 
+/* ---- the loss terms of the late iterations inside the one-call view (train_3dgs.py:109-150, iteration > depth_from_iter) ----
+ * With r = nan_to_num(depth_raw / alpha, 0, 0), the depth render() returns (scorp_gs3d_render_tail's arithmetic):
+ *   sensor term   (train_3dgs.py:112-120)  Ms = (sensor > SCORP_DEPTH_SENSOR_MIN) & (sensor < SCORP_DEPTH_SENSOR_MAX) & (r > 0),
+ *                 Ls = mean over Ms of |r - sensor|;
+ *   estimate term (train_3dgs.py:125-134)  Me = (r > 0) & (est > 0), rn = (r - min r) / (max r - min r) and pn likewise from
+ *                 est, the extrema taken over Me and not differentiated (image_utils.py:87-91), Le = mean over Me of |rn - pn|;
+ *   isotropic     (train_3dgs.py:146-148, loss_utils.py:75-85)  Liso = mean over Gaussians and axes of |s - mean_axes s|,
+ *                 s = the activated scales, of the parameters BEFORE this view's optimizer step.
+ * out_terms4 (device) = {lambda_depth_sensor Ls + weight_depth_est Le + lambda_isotropic Liso, Ls, Le, Liso}; the caller
+ * forms weight_depth_est = 10 * dn_l1_weight(iteration).  A depth term is computed when its map is given; a term that is
+ * not computed reports 0.  The gradients with respect to depth_raw and alpha go to grad_depth_raw / grad_alpha (zeros where
+ * scorp_gs3d_render_tail_backward writes zeros), which the view hands to its backward; the isotropic gradient
+ *   lambda_isotropic / (3 N) * (sgn_j - (sgn_0 + sgn_1 + sgn_2) / 3) * s_j,  sgn = sign(s - mean s),
+ * is added to the scaling gradient of EVERY Gaussian, visible or not, by the per-Gaussian backward kernel, before that
+ * gradient is written or enters the optimizer step.  No float atomics (per-workgroup partial sums in `workspace`, added in
+ * a fixed order): two calls give the same bits.
+ * Degenerate inputs: a term whose mask is empty, or whose rendered or estimated depths over Me are all equal (range 0),
+ * reports the value NaN - and so does out_terms4[0] - and contributes a ZERO gradient, so that no NaN reaches the
+ * parameters or the Adam moments; nothing fails and nothing is written out of bounds.  (The torch formulation raises on an
+ * empty Me and yields NaN gradients for the other cases.) */
+#define SCORP_DEPTH_SENSOR_MIN 0.3f /* train_3dgs.py:113: the sensor's valid range, exclusive on both sides */
+#define SCORP_DEPTH_SENSOR_MAX 7.0f
+typedef struct ScorpGs3dViewTerms {
+  const float *depth_sensor;     /* [H,W] or NULL */
+  const float *depth_est;        /* [H,W] or NULL */
+  float lambda_depth_sensor;     /* != 0 needs depth_sensor */
+  float weight_depth_est;        /* != 0 needs depth_est */
+  float lambda_isotropic;        /* != 0: 3-D scales of the training layout (scales + rotations, shs + shs_rest) */
+  float _pad;
+  float *out_terms4;             /* device: {weighted sum of the three, Ls, Le, Liso} */
+  float *grad_depth_raw;         /* [H,W] scratch, needed with a depth map */
+  float *grad_alpha;             /* [H,W] scratch, needed with a depth map */
+  void *workspace;               /* scorp_gs3d_view_terms_workspace_bytes(W, H, N), 16-byte aligned */
+  size_t workspace_bytes;
+} ScorpGs3dViewTerms;
+size_t scorp_gs3d_view_terms_workspace_bytes(int32_t width, int32_t height, int32_t num_gaussians);
+/* scorp_gs3d_train_view with the terms: between the photometric loss and the backward the view runs the two depth passes
+ * and the isotropic value, its backward gets grad_depth_raw / grad_alpha as dL_ddepth / dL_dalpha, and the per-Gaussian
+ * backward adds the isotropic gradient.  Total loss of the view = out_loss3[0] + out_terms4[0].  With a depth map the
+ * view must produce out_depth.  terms == NULL: scorp_gs3d_train_view, launch for launch.  SCORP_ERR_INVALID before any
+ * launch: out_terms4 NULL, a weight without its map, a map without grad_depth_raw / grad_alpha / out_depth, a workspace
+ * NULL, misaligned or too small, lambda_isotropic without the training layout. */
+int scorp_gs3d_train_view_ex(const ScorpGs3dTrainView *view, const ScorpGs3dViewTerms *terms, scorp_stream_t stream);
+/* The two depth terms alone, on caller-given maps (what an autograd front-end wraps): values into out_terms4 (Liso = 0),
+ * gradients for an upstream gradient of 1 into grad_depth_raw / grad_alpha [H,W].  At least one map; workspace:
+ * scorp_gs3d_view_terms_workspace_bytes(W, H, 0). */
+int scorp_gs3d_depth_terms(int32_t width, int32_t height, const float *depth_raw, const float *alpha, const float *depth_sensor,
+                           const float *depth_est, float lambda_depth_sensor, float weight_depth_est, float *out_terms4,
+                           float *grad_depth_raw, float *grad_alpha, void *workspace, size_t workspace_bytes,
+                           scorp_stream_t stream);
+
 /* The 2DGS twin: one iteration of train_2dgs.py:95-150 for the plain photometric loss plus its two regularisers,
  *   scorp_gs2d_preprocess -> scorp_gs2d_render -> scorp_loss_l1_ssim_forward -> scorp_gs2d_regularizers_forward ->
  *   scorp_loss_l1_ssim_backward -> scorp_gs2d_regularizers_backward -> scorp_gs2d_backward,

@@ -462,11 +462,19 @@ struct AdamEpi {
   uint32_t *skipped_counter;              // ... and this word is incremented once instead (NULL: not counted)
   float *max_radii2D, *accum, *denom;     // per-view densification statistics (all three or none)
 };
+// lambda_isotropic != 0 (scorp_gs3d_train_view_ex; split SH layout, scales given): the isotropic regulariser's gradient is
+// added to every Gaussian's scaling gradient - a separate instantiation, the plain one is the kernel it always was
 void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L, const BinRec *bin, const float *acc,
-                                const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam = nullptr);
+                                const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam = nullptr,
+                                float lambda_isotropic = 0.0f);
 int backward3d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity, const float *dL_dcolor,
                     const float *dL_ddepth, const float *dL_dalpha, const ScorpGs3dGrads *grads, void *scratch,
-                    size_t scratch_bytes, uint32_t flags, scorp_stream_t stream, const AdamEpi *adam);
+                    size_t scratch_bytes, uint32_t flags, scorp_stream_t stream, const AdamEpi *adam,
+                    float lambda_isotropic = 0.0f);
+// ---- the late iterations' loss terms (depth_terms.hip): checked arguments in, launches out; `scales` NULL: no isotropic value
+int view_terms_impl(int W, int H, const float *depth_raw, const float *alpha, const float *sensor, const float *est,
+                    float w_sensor, float w_est, const float *scales, int N, int raw, float lambda_iso, float *out_terms4,
+                    float *g_depth_raw, float *g_alpha, void *workspace, hipStream_t stream);
 int preprocess2d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, void *state, size_t state_bytes, scorp_stream_t stream);
 int render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, float *out_color, float *out_allmap,
                   scorp_stream_t stream, bool for_backward);

@@ -573,7 +573,7 @@ extern "C" int scorp_gs3d_backward_ex(const ScorpGs3dInputs *in, const void *sta
 int scorp::backward3d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                            const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
                            const ScorpGs3dGrads *grads, void *scratch, size_t scratch_bytes, uint32_t flags,
-                           scorp_stream_t stream_, const AdamEpi *adam) {
+                           scorp_stream_t stream_, const AdamEpi *adam, float lambda_isotropic) {
   hipStream_t stream = (hipStream_t)stream_;
   const char *base = (const char *)state, *pb = (const char *)pairs;
   auto blend = [&](const StateLayout &L, const PairLayout &P, float *acc, float *partial, uint8_t *row_flags, uint32_t *pair_base) {
@@ -596,7 +596,7 @@ int scorp::backward3d_impl(const ScorpGs3dInputs *in, const void *state, const v
         (const BinRec *)(base + L.bin), (const uint64_t *)(base + L.tile_mask));
   };
   auto per_gaussian = [&](const StateLayout &L, const float *acc) {
-    launch_preprocess_backward(in, L, (const BinRec *)(base + L.bin), acc, grads, stream, adam);
+    launch_preprocess_backward(in, L, (const BinRec *)(base + L.bin), acc, grads, stream, adam, lambda_isotropic);
   };
   return backward_pass(kGs3d, in, state, pairs, capacity, dL_dcolor, grads, scratch, scratch_bytes, flags, stream, blend,
                        per_gaussian);

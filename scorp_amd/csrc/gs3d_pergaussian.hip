@@ -290,9 +290,12 @@ preprocess_kernel(PgArgs a, SplatRec *__restrict__ rec, BinRec *__restrict__ bin
 // everything a Gaussian needs - radius word, accumulator row, parameters: 22 dwords - with untracked loads AHEAD of
 // the SH stream and pick them up at vmcnt(12); otherwise the chain "radius -> visible? -> accumulators, parameters"
 // would sit behind the 48 KiB stream (the compiler waits with vmcnt(0) while LDS-DMA loads are pending).
-template <int DEG, bool SPLIT, bool LIN>
+// ISO: the isotropic regulariser's gradient (train_3dgs.py:146-148) joins the scaling gradient of EVERY Gaussian of the
+// block, visible or not; iso_k = lambda_isotropic / (9 N).  The plain instantiations do not know it exists.
+template <int DEG, bool SPLIT, bool LIN, bool ISO = false>
 __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float *s_sh, const BinRec *__restrict__ bin,
-                                                         const float *__restrict__ acc, const ScorpGs3dGrads &g, const AdamEpi &ad) {
+                                                         const float *__restrict__ acc, const ScorpGs3dGrads &g, const AdamEpi &ad,
+                                                         float iso_k = 0.0f) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool active = LIN || i < a.N;
   const size_t i0 = (size_t)blockIdx.x * 256;
@@ -520,6 +523,28 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
       }
     }
   }
+  if constexpr (ISO) {
+    // d/d(raw scale j) of lambda * mean_{n,i} |s_ni - m_n| = lambda / (3 N) * (sgn_j - (sgn_0 + sgn_1 + sgn_2) / 3) * ds_j/draw_j.
+    // The mean and the signs are taken in double (three equal scales then have the signs 0, as in exact arithmetic);
+    // 3 sgn_j - sum sgn is a small integer, so the gradient carries three fp32 roundings.  Contraction off where it joins
+    // the rasterizer's gradient: the written-gradient form and the step inside the view give the same bits.
+    if (active && (g.scales != nullptr || (adam_on && ad.m[4] != nullptr))) {
+#pragma clang fp contract(off)
+      float sv[3], sg[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) sv[k] = act_scale(LIN ? pre[7 + k] : a.scales[3 * (size_t)i + k], a.raw);
+      const double m = ((double)sv[0] + (double)sv[1] + (double)sv[2]) / 3.0;
+#pragma unroll
+      for (int k = 0; k < 3; k++) sg[k] = (double)sv[k] > m ? 1.0f : (double)sv[k] < m ? -1.0f : 0.0f;
+      const float sgsum = sg[0] + sg[1] + sg[2];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        float gi = iso_k * (3.0f * sg[k] - sgsum);
+        if (a.raw & 2) gi = gi * sv[k];   // d exp(v) / dv
+        gs[k] = gs[k] + gi;
+      }
+    }
+  }
   if (a.shs && lin) { stage_sh_wait(); __syncthreads(); }
   AdamGeomMoments am;   // asked for here, used in the epilogue: the SH phase in between hides the latency
   const bool adam_pre = SPLIT && adam_on && active;
@@ -609,6 +634,21 @@ preprocess_backward_kernel(PgArgs a, const BinRec *__restrict__ bin, const float
   preprocess_backward_body<DEG, SPLIT, false>(a, s_sh, bin, acc, g, ad);
 }
 
+// The same kernel with the isotropic regulariser's gradient (split SH layout, scales + rotations: the training layout)
+template <int DEG>
+__global__ void __launch_bounds__(256)
+preprocess_backward_iso_kernel(PgArgs a, const BinRec *__restrict__ bin, const float *__restrict__ acc, ScorpGs3dGrads g,
+                               AdamEpi ad, float iso_k) {
+  __shared__ __attribute__((aligned(16))) float s_sh[256 * kShStride];
+  if constexpr (DEG == 3) {
+    if (a.K == 16 && a.N - (int)blockIdx.x * 256 >= 256) {
+      preprocess_backward_body<DEG, true, true, true>(a, s_sh, bin, acc, g, ad, iso_k);
+      return;
+    }
+  }
+  preprocess_backward_body<DEG, true, false, true>(a, s_sh, bin, acc, g, ad, iso_k);
+}
+
 PgArgs make_args(const ScorpGs3dInputs *in, const StateLayout &L) {
   PgArgs a;
   a.N = in->num_gaussians; a.K = in->sh_coeffs; a.W = in->image_width; a.H = in->image_height;
@@ -638,7 +678,7 @@ void launch_preprocess(const ScorpGs3dInputs *in, const StateLayout &L, SplatRec
 }
 
 void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L, const BinRec *bin, const float *acc,
-                                const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam) {
+                                const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam, float lambda_isotropic) {
   const PgArgs a = make_args(in, L);
   const dim3 grid((a.N + 255) / 256), block(256);
   const int deg = in->shs ? in->sh_degree : 0;
@@ -647,6 +687,13 @@ void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L,
   AdamEpi ad;
   memset(&ad, 0, sizeof(ad));
   if (adam && split) ad = *adam;   // (the fused step is defined for the training layout: dc / rest split leaves)
+  if (lambda_isotropic != 0.0f && split && in->shs && in->scales && !in->cov3D_precomp) {   // (the caller checked the layout)
+    const float iso_k = (float)((double)lambda_isotropic / (9.0 * (double)a.N));
+    dispatch_sh_degree(deg, true, [&](auto D, auto) {
+      preprocess_backward_iso_kernel<D><<<grid, block, 0, stream>>>(a, bin, acc, g, ad, iso_k);
+    });
+    return;
+  }
   dispatch_sh_degree(deg, split, [&](auto D, auto S) {
     preprocess_backward_kernel<D, S><<<grid, block, 0, stream>>>(a, bin, acc, g, ad);
   });

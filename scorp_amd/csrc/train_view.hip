@@ -1,6 +1,7 @@
 // train_view.hip — scorp_gs3d_train_view: one training view (render, L1 + SSIM loss, backward) enqueued by ONE call.
 // Host code only: it chains the library's own entry points, so the kernels, their order and their results are those
 // of the separate calls (train_3dgs.py:88-150 minus the optimizer step).  See include/scorp_gs.h for the contract.
+// scorp_gs3d_train_view_ex adds the late iterations' terms (depth_terms.hip) between the loss and the backward.
 #include <math.h>
 
 #include "common.hpp"
@@ -42,6 +43,38 @@ static int make_adam_epi(const ScorpFusedAdam *fa, const ScorpGs3dInputs *in, in
 }
 
 extern "C" int scorp_gs3d_train_view(const ScorpGs3dTrainView *v, scorp_stream_t stream) {
+  return scorp_gs3d_train_view_ex(v, nullptr, stream);
+}
+
+// The arguments of the late iterations' terms, before anything is launched
+static int check_view_terms(const ScorpGs3dTrainView *v, const ScorpGs3dViewTerms *t) {
+  const ScorpGs3dInputs *in = v->in;
+  if (!t->out_terms4) { set_error("scorp_gs3d_train_view_ex: out_terms4 is NULL"); return SCORP_ERR_INVALID; }
+  if (t->lambda_depth_sensor != 0.0f && !t->depth_sensor) {
+    set_error("scorp_gs3d_train_view_ex: lambda_depth_sensor without depth_sensor"); return SCORP_ERR_INVALID;
+  }
+  if (t->weight_depth_est != 0.0f && !t->depth_est) {
+    set_error("scorp_gs3d_train_view_ex: weight_depth_est without depth_est"); return SCORP_ERR_INVALID;
+  }
+  if (t->depth_sensor || t->depth_est) {
+    if (!t->grad_depth_raw || !t->grad_alpha) {
+      set_error("scorp_gs3d_train_view_ex: the depth terms need grad_depth_raw and grad_alpha"); return SCORP_ERR_INVALID;
+    }
+    if (!v->out_depth) { set_error("scorp_gs3d_train_view_ex: the depth terms need the view's out_depth"); return SCORP_ERR_INVALID; }
+  }
+  if (t->lambda_isotropic != 0.0f && (!in->scales || !in->rotations || in->cov3D_precomp || !in->shs || !in->shs_rest)) {
+    set_error("scorp_gs3d_train_view_ex: lambda_isotropic needs the training layout (scales + rotations, shs + shs_rest)");
+    return SCORP_ERR_INVALID;
+  }
+  const size_t need = scorp_gs3d_view_terms_workspace_bytes(in->image_width, in->image_height, in->num_gaussians);
+  if (!t->workspace || t->workspace_bytes < need || ((uintptr_t)t->workspace & 15)) {
+    set_error("scorp_gs3d_train_view_ex: terms workspace NULL, misaligned or too small (%zu < %zu)", t->workspace_bytes, need);
+    return SCORP_ERR_INVALID;
+  }
+  return SCORP_OK;
+}
+
+extern "C" int scorp_gs3d_train_view_ex(const ScorpGs3dTrainView *v, const ScorpGs3dViewTerms *terms, scorp_stream_t stream) {
   if (!v || !v->in || !v->grads) { set_error("NULL argument to scorp_gs3d_train_view"); return SCORP_ERR_INVALID; }
   if (!v->out_color || !v->out_depth_raw || !v->out_alpha || !v->out_radii || !v->gt || !v->out_loss3 || !v->grad_color) {
     set_error("scorp_gs3d_train_view: an output / ground-truth / scratch pointer is NULL");
@@ -49,6 +82,7 @@ extern "C" int scorp_gs3d_train_view(const ScorpGs3dTrainView *v, scorp_stream_t
   }
   const ScorpGs3dInputs *in = v->in;
   const int W = in->image_width, H = in->image_height;
+  if (terms) if (int e = check_view_terms(v, terms)) return e;
   // render()'s tail (normalised depth, visibility filter) comes out of the per-Gaussian kernel and the blend forward's
   // epilogue: same values as scorp_gs3d_render_tail, one launch less per view
   const bool tail = v->out_depth && v->out_visible;
@@ -65,12 +99,21 @@ extern "C" int scorp_gs3d_train_view(const ScorpGs3dTrainView *v, scorp_stream_t
                                 v->loss_workspace_bytes, 1, false, (hipStream_t)stream)) return e;
   if (int e = loss_backward_impl(v->out_color, v->gt, v->mask, 3, H, W, v->lambda_dssim, v->loss_workspace, nullptr,
                                  v->grad_color, v->out_loss3, (hipStream_t)stream)) return e;
+  // the late iterations' terms (train_3dgs.py:109-150): their values, and the gradients the backward takes from here on
+  const bool depth_terms = terms && (terms->depth_sensor || terms->depth_est) && W > 0 && H > 0;
+  const float lambda_iso = terms ? terms->lambda_isotropic : 0.0f;
+  if (terms) {
+    if (int e = view_terms_impl(W, H, v->out_depth_raw, v->out_alpha, terms->depth_sensor, terms->depth_est,
+                                terms->lambda_depth_sensor, terms->weight_depth_est, lambda_iso != 0.0f ? in->scales : nullptr,
+                                in->num_gaussians, in->raw_params, lambda_iso, terms->out_terms4, terms->grad_depth_raw,
+                                terms->grad_alpha, terms->workspace, (hipStream_t)stream)) return e;
+  }
   AdamEpi ad;
   if (int e = make_adam_epi(v->adam, in, 3, v->out_header ? v->out_header + 1 : reinterpret_cast<const uint32_t *>(v->state) + 1, &ad)) return e;
-  return backward3d_impl(in, v->state, v->pairs, v->capacity, v->grad_color, nullptr, nullptr, v->grads,
-                         v->backward_scratch, v->backward_scratch_bytes,
+  return backward3d_impl(in, v->state, v->pairs, v->capacity, v->grad_color, depth_terms ? terms->grad_depth_raw : nullptr,
+                         depth_terms ? terms->grad_alpha : nullptr, v->grads, v->backward_scratch, v->backward_scratch_bytes,
                          (v->backward_flags & ~SCORP_BACKWARD_SCRATCH_ZEROED) | (zero_here ? SCORP_BACKWARD_SCRATCH_ZEROED : 0u),
-                         stream, v->adam ? &ad : nullptr);
+                         stream, v->adam ? &ad : nullptr, lambda_iso);
 }
 
 extern "C" int scorp_gs2d_train_view(const ScorpGs2dTrainView *v, scorp_stream_t stream) {

@@ -3,6 +3,11 @@
 `fused_l1_ssim_loss(image, gt, lambda_dssim, mask)` equals
 `(1-lambda) * l1_loss(image*mask, gt*mask) + lambda * (1 - ssim(image*mask, gt*mask))` of scorp_amd.loss /
 gs3dgs/utils/loss_utils.py, differentiable w.r.t. `image`, in two kernels instead of ~10 convolutions.
+
+`fused_depth_terms(depth_raw, alpha, sensor, est, lambda_depth_sensor, weight_depth_est)` equals
+`loss.depth_losses(nan_to_num(depth_raw / alpha, 0, 0), ...)` of train_3dgs.py:109-134 - the sensor-depth L1 and the min-max
+normalised L1 against an estimated depth - differentiable w.r.t. the rasterizer's two raw maps, without the boolean-mask
+indexings (and their host synchronisations) of the torch formulation (scorp_amd/csrc/depth_terms.hip).
 """
 import ctypes
 
@@ -57,3 +62,46 @@ class _FusedL1SSIM(torch.autograd.Function):
 
 def fused_l1_ssim_loss(image, gt, lambda_dssim=0.2, mask=None):
     return _FusedL1SSIM.apply(image, gt, lambda_dssim, mask)
+
+
+def depth_terms(depth_raw, alpha, sensor=None, est=None, lambda_depth_sensor=0.0, weight_depth_est=0.0):
+    """scorp_gs3d_depth_terms, no autograd: (out4, g_depth_raw, g_alpha) with out4 = {weighted sum, sensor term, estimate
+    term, 0} on the device and the two gradient maps (upstream gradient 1) shaped like their inputs."""
+    L = _C.lib()
+    if not depth_raw.is_cuda:
+        raise RuntimeError("depth_terms needs GPU tensors (scorp_amd has no CPU path)")
+    H, W = depth_raw.shape[-2:]
+    prep = lambda t: None if t is None else t.detach().contiguous().float()
+    d, a, s_, e = prep(depth_raw), prep(alpha), prep(sensor), prep(est)
+    for t in (d, a, s_, e):
+        if t is not None and t.numel() != H * W:
+            raise ValueError(f"depth_terms: maps of {H} x {W} expected, got {tuple(t.shape)}")
+    ws_bytes = L.scorp_gs3d_view_terms_workspace_bytes(W, H, 0)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d.device)
+    out = torch.empty(4, dtype=torch.float32, device=d.device)
+    g_depth, g_alpha = torch.empty_like(d), torch.empty_like(a)
+    _C.check(L.scorp_gs3d_depth_terms(W, H, _p(d), _p(a), _p(s_), _p(e), float(lambda_depth_sensor), float(weight_depth_est),
+                                      _p(out), _p(g_depth), _p(g_alpha), _p(ws), ws_bytes, _stream()), "scorp_gs3d_depth_terms")
+    return out, g_depth, g_alpha
+
+
+class _FusedDepthTerms(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth_raw, alpha, sensor, est, lambda_depth_sensor, weight_depth_est):
+        out, g_depth, g_alpha = depth_terms(depth_raw, alpha, sensor, est, lambda_depth_sensor, weight_depth_est)
+        ctx.save_for_backward(g_depth, g_alpha)
+        ctx.parts = out      # {weighted sum, sensor term, estimate term, 0}
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_depth, g_alpha = ctx.saved_tensors
+        return (g_depth * grad_out if ctx.needs_input_grad[0] else None,
+                g_alpha * grad_out if ctx.needs_input_grad[1] else None, None, None, None, None)
+
+
+def fused_depth_terms(depth_raw, alpha, sensor=None, est=None, lambda_depth_sensor=0.0, weight_depth_est=0.0):
+    """lambda_depth_sensor * Ls + weight_depth_est * Le on the rasterizer's raw depth and alpha maps (see the module
+    docstring; weight_depth_est = 10 * dn_l1_weight(iteration)).  A term whose mask is empty or whose range is zero reads NaN
+    and has a zero gradient (include/scorp_gs.h, ScorpGs3dViewTerms)."""
+    return _FusedDepthTerms.apply(depth_raw, alpha, sensor, est, lambda_depth_sensor, weight_depth_est)

@@ -94,10 +94,12 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
         if hasattr(gaussians.optimizer, "skip_flag") and not stepped_in_view:
             gaussians.optimizer.skip_flag = ovf
         pkg["visibility_filter"] = pkg["visibility_filter"] & (ovf == 0)
-    elif (fused_view and not surfels and not extra_terms and render_fn is render and loss_fn is fused_l1_ssim_loss
+    elif (fused_view and not surfels and render_fn is render and loss_fn is fused_l1_ssim_loss
             and getattr(pipe, "fused_activations", False)):
-        # plain photometric iteration: render + loss + backward enqueued by ONE library call (train_view.py); same
-        # kernels and results, no autograd graph.  The pair buffer is reserved, the caller drains (see train()).
+        # render + loss + backward enqueued by ONE library call (train_view.py); same kernels and results, no autograd
+        # graph.  The pair buffer is reserved, the caller drains (see train()).  After depth_from_iter the view carries the
+        # depth terms and the isotropic regulariser too (the conditions of the `else:` branch below), so the three quarters
+        # of a default run that have them stay on this path.
         view_fn = view_fn or _default_view_fn()
         # The optimizer step itself inside the view (ScorpFusedAdam: the per-Gaussian backward kernel applies Adam and the
         # view's statistics while it holds the gradient row) on the iterations where the reference's optimizer.step() sees
@@ -115,6 +117,8 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
             kw_view["optimizer"] = gaussians.optimizer
             if densify and iteration < opt.densify_until_iter and _stats_components(gaussians) == 2:
                 kw_view["stats"] = (gaussians.max_radii2D, gaussians.xyz_gradient_accum, gaussians.denom)
+        if extra_terms:
+            kw_view.update(_view_terms_kw(opt, iteration, gt_depth, gt_depth_est))
         pkg = view_fn(cam, gaussians, pipe, bg, gt_image, opt.lambda_dssim, **kw_view)
         loss = pkg["loss"]
         stepped_in_view = bool(pkg.get("optimizer_stepped"))
@@ -181,6 +185,21 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
     return loss, pkg
 
 
+def _view_terms_kw(opt, iteration, gt_depth, gt_depth_est):
+    """The terms of train_3dgs.py:109-150 that apply at this iteration (> depth_from_iter), as train_view takes them: the
+    conditions and weights of loss.depth_losses and of the isotropic line of the autograd branch."""
+    from .gaussian_model import get_expon_lr_func
+    kw = {}
+    if gt_depth is not None:
+        kw["depth_sensor"], kw["lambda_depth_sensor"] = gt_depth, opt.lambda_depth_sensor
+    if gt_depth_est is not None:
+        w = get_expon_lr_func(opt.dn_l1_weight_init, opt.dn_l1_weight_final, max_steps=opt.iterations)(iteration)
+        kw["depth_est"], kw["weight_depth_est"] = gt_depth_est, 10 * w
+    if getattr(opt, "lambda_isotropic", 0.0) > 0:
+        kw["lambda_isotropic"] = opt.lambda_isotropic
+    return kw
+
+
 def _stats_components(gaussians):
     """Over how many components of a means2D-gradient row the model's add_densification_stats norms - declared next to the
     method by the class that DEFINES it (GaussianModel.accumulate_view_stats uses the same rule); None: an override the fused
@@ -219,10 +238,12 @@ def _default_view_fn():
 
 
 def train(gaussians, cameras, gt_images, opt, pipe=None, iterations=None, background=None, seed=0, data_parallel=False,
-          **kw):
+          gt_depths=None, gt_depth_ests=None, **kw):
     """Runs `iterations` training iterations over shuffled cameras; returns the list of per-iteration losses.
     `data_parallel`: every rank runs this with the same arguments and the same initial model; one iteration then
-    consumes world_size views (rank r takes the r-th of each group), i.e. a batch of views per optimizer step."""
+    consumes world_size views (rank r takes the r-th of each group), i.e. a batch of views per optimizer step.
+    `gt_depths` / `gt_depth_ests`: optional per-camera sensor / estimated depth maps, indexed like `gt_images` (an entry
+    may be None); they reach the iteration as `gt_depth` / `gt_depth_est` (used after opt.depth_from_iter)."""
     pipe = pipe or PipelineParams()
     dev = gaussians.get_xyz.device
     background = torch.zeros(3, device=dev) if background is None else background
@@ -241,6 +262,10 @@ def train(gaussians, cameras, gt_images, opt, pipe=None, iterations=None, backgr
                 rng.shuffle(stack)
             ks.append(stack.pop())
         k = ks[rank]
+        if gt_depths is not None:
+            kw["gt_depth"] = gt_depths[k]
+        if gt_depth_ests is not None:
+            kw["gt_depth_est"] = gt_depth_ests[k]
         loss, _ = training_iteration(gaussians, cameras[k], gt_images[k], opt, pipe, background, it,
                                      data_parallel=data_parallel and collective(), **kw)
         if kw.get("fused_view") and not first_checked:

@@ -111,7 +111,8 @@ class _View:
 
 
 def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2, mask=None, scaling_modifier=1.0,
-               optimizer=None, stats=None, grad_out=None):
+               optimizer=None, stats=None, grad_out=None, depth_sensor=None, depth_est=None, lambda_depth_sensor=0.0,
+               weight_depth_est=0.0, lambda_isotropic=0.0):
     """Returns the dict of `renderer.render` plus "loss", "l1", "ssim" (0-d views of one device tensor); parameter
     gradients are accumulated into `pc`'s leaves.  Needs the model's raw leaves (fused activations).
 
@@ -126,7 +127,15 @@ def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2,
 
     `grad_out` (six tensors or None entries, the leaves' order xyz, features_dc, features_rest, opacity, scaling, rotation; e.g.
     parallel.GradArena.views): the gradients are WRITTEN there (not accumulated) and become the leaves' .grad - the
-    data-parallel loop's collective then reads them where the kernel left them."""
+    data-parallel loop's collective then reads them where the kernel left them.
+
+    `depth_sensor` / `depth_est` ([1,H,W] or [H,W]), `lambda_depth_sensor`, `weight_depth_est` (= 10 * dn_l1_weight(iteration),
+    formed by the caller as loss.depth_losses forms it) and `lambda_isotropic`: the terms train_3dgs.py:109-150 adds after
+    depth_from_iter, inside the same call (scorp_gs3d_train_view_ex, ScorpGs3dViewTerms in include/scorp_gs.h: the two depth
+    passes between the loss and the backward, the isotropic gradient in the per-Gaussian backward kernel - with `optimizer`
+    the invisible Gaussians then take the step with that gradient alone).  The result gains "depth_sensor_loss",
+    "depth_est_loss", "isotropic_loss" (unweighted, 0-d views of one device tensor) and "loss" is the total.  A term whose mask
+    is empty or whose range is zero reads NaN and moves nothing.  With all five at their defaults nothing changes."""
     L = _C.lib()
     c = _View(_GS3D, "train_view", viewpoint_camera, pc, bg_color, gt_image, mask, scaling_modifier, optimizer, stats,
               grad_out, debug=bool(getattr(pipe, "debug", False)))
@@ -139,14 +148,47 @@ def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2,
     v.lambda_dssim = float(lambda_dssim)
     v.out_depth_raw, v.out_alpha, v.out_depth, v.out_visible = depth_raw.data_ptr(), alpha.data_ptr(), depth.data_ptr(), visible.data_ptr()
     v.out_loss3, v.out_header = loss3.data_ptr(), header.data_ptr()
-    _C.check(L.scorp_gs3d_train_view(ctypes.byref(v), _stream()), "scorp_gs3d_train_view")
+    terms = None
+    if depth_sensor is not None or depth_est is not None or lambda_depth_sensor or weight_depth_est or lambda_isotropic:
+        terms, keep = _view_terms(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, lambda_isotropic)
+        _C.check(L.scorp_gs3d_train_view_ex(ctypes.byref(v), ctypes.byref(terms), _stream()), "scorp_gs3d_train_view_ex")
+    else:
+        _C.check(L.scorp_gs3d_train_view(ctypes.byref(v), _stream()), "scorp_gs3d_train_view")
     PairPolicy.pend(c.state, N, H, W, header=header)    # queued for drain(): no copy launch, the state blob is not pinned
     c.accumulate()
-    return {"optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": visible.view(torch.bool),
-            "radii": c.radii, "render_depth": depth, "render_alpha": alpha, "loss": loss3[0], "l1": loss3[1], "ssim": loss3[2],
+    extra, total = {}, loss3[0]
+    if terms is not None:
+        terms4 = keep[0]
+        extra = {"photometric_loss": loss3[0], "depth_sensor_loss": terms4[1], "depth_est_loss": terms4[2], "isotropic_loss": terms4[3]}
+        total = loss3[0] + terms4[0]      # the convention of the 2DGS twin: out_loss3[0] + out_terms4[0]
+    return {**extra, "optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": visible.view(torch.bool),
+            "radii": c.radii, "render_depth": depth, "render_alpha": alpha, "loss": total, "l1": loss3[1], "ssim": loss3[2],
             # != 0 if this view needed more pairs than were reserved (its images and gradients then come from truncated
             # tile lists): a device word, so the caller can make the optimizer step conditional without a host sync
             "overflow": header.view(torch.int32)[1:2]}
+
+
+def _view_terms(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, lambda_isotropic):
+    """The ScorpGs3dViewTerms of one view and the tensors it points to (out_terms4 first)."""
+    H, W, N = c.H, c.W, c.N
+    maps = []
+    for t, name in ((depth_sensor, "depth_sensor"), (depth_est, "depth_est")):
+        if t is not None:
+            if t.numel() != H * W:
+                raise ValueError(f"{name}: {tuple(t.shape)} is not a depth map of the view ({H} x {W})")
+            t = _prep(t, name)
+        maps.append(t)
+    ws_bytes = L.scorp_gs3d_view_terms_workspace_bytes(W, H, N)
+    keep = [c.new((4,)), c.new((ws_bytes,), torch.uint8), *maps]
+    t = _C.ScorpGs3dViewTerms()
+    t.depth_sensor, t.depth_est = (None if m is None else m.data_ptr() for m in maps)
+    t.lambda_depth_sensor, t.weight_depth_est = float(lambda_depth_sensor), float(weight_depth_est)
+    t.lambda_isotropic = float(lambda_isotropic)
+    t.out_terms4, t.workspace, t.workspace_bytes = keep[0].data_ptr(), keep[1].data_ptr(), ws_bytes
+    if maps[0] is not None or maps[1] is not None:
+        keep += [c.new((H, W)), c.new((H, W))]
+        t.grad_depth_raw, t.grad_alpha = keep[-2].data_ptr(), keep[-1].data_ptr()
+    return t, keep
 
 
 class _ViewspaceGrad:
