@@ -557,6 +557,66 @@ typedef struct ScorpGs2dTrainView {
 } ScorpGs2dTrainView;
 int scorp_gs2d_train_view(const ScorpGs2dTrainView *view, scorp_stream_t stream);
 
+/* ---- the loss terms of the late iterations inside the one-call 2DGS view (train_2dgs.py:100-139, iteration > depth_from_iter) ----
+ * With d = the surface depth of a pixel as scorp_gs2d_maps_forward forms it (nan_to_num(allmap[0] / allmap[1], 0, 0) and
+ * nan_to_num(allmap[5], 0, 0) mixed by depth_ratio: the render_depth of the 2DGS render()):
+ *   sensor term   (train_2dgs.py:101-109)  Ls, and
+ *   estimate term (train_2dgs.py:114-124)  Le: the definitions, masks, constants and double-precision uniforms of
+ *                 ScorpGs3dViewTerms above, with d in place of r;
+ *   depth-normal  (train_2dgs.py:126-134)  pred_normal[3,H,W] = the normal of the ESTIMATED depth map through the camera's ray
+ *                 table (gs2dgs/utils/point_utils.py:9-37: central differences of the back-projected points, cross product,
+ *                 normalised with the epsilon handling of surf_normal, zero on the one-pixel border; not alpha-weighted, no
+ *                 gradient),  Ldn = mean over ALL H*W pixels of (1 - surf_normal . pred_normal),  Lrn = the same mean with the
+ *                 world-space render_normal; pixels where the estimate is 0 are not masked out;
+ *   isotropic     (train_2dgs.py:136-139)  Liso = mean over surfels and both axes of |s - mean_axes s|, s = the activated
+ *                 [N,2] scales, of the parameters BEFORE this view's optimizer step.
+ * out_terms6 (device) = {lambda_depth_sensor Ls + weight_depth_est Le + weight_depth_normal (Ldn + Lrn) + lambda_isotropic Liso,
+ * Ls, Le, Ldn, Lrn, Liso}; the caller forms weight_depth_est = 10 * dn_l1_weight(iteration) and weight_depth_normal =
+ * dn_l1_weight(iteration) (0 until depth_from_iter + 1000).  A depth term is computed when its map is given, the depth-normal
+ * terms when weight_depth_normal != 0; a term that is not computed reports 0.  Gradients: d loss / d d of the two depth terms
+ * goes to grad_depth[H,W], -(weight_depth_normal / HW) pred_normal - the gradient with respect to BOTH surf_normal (its alpha
+ * factor stays detached) and render_normal - to grad_normal[3,H,W]; the view's maps backward adds them to the regularisers'
+ * gradients and writes all seven channels of grad_allmap once, in one kernel.  The isotropic gradient
+ *   lambda_isotropic / (2 N) * (sgn_j - (sgn_0 + sgn_1) / 2) * s_j,  sgn = sign(s - mean s),
+ * is added to the scaling gradient of EVERY surfel, visible or not, by the per-surfel backward kernel, before that gradient
+ * is written or enters the optimizer step.  No float atomics (per-workgroup partial sums in `workspace`, added in a fixed
+ * order): two calls give the same bits.
+ * Degenerate inputs: a depth term whose mask is empty, or whose depths over Me are all equal (range 0), reports NaN - and
+ * so does out_terms6[0] - and contributes a ZERO gradient; no NaN reaches the parameters or the Adam moments, nothing fails.
+ * Ldn and Lrn are plain means over H*W and cannot be empty. */
+typedef struct ScorpGs2dViewTerms {
+  const float *depth_sensor;     /* [H,W] or NULL */
+  const float *depth_est;        /* [H,W] or NULL */
+  float lambda_depth_sensor;     /* != 0 needs depth_sensor */
+  float weight_depth_est;        /* != 0 needs depth_est */
+  float weight_depth_normal;     /* != 0 needs depth_est */
+  float lambda_isotropic;        /* != 0: [N,2] scales of the training layout (scales + rotations, shs + shs_rest) */
+  float *out_terms6;             /* device: {weighted total, Ls, Le, Ldn, Lrn, Liso} */
+  float *out_depth;              /* [H,W]: the surface depth d; needed (and written) with a depth map */
+  float *grad_depth;             /* [H,W] scratch, needed with a depth map */
+  float *grad_normal;            /* [3,H,W] scratch, needed with weight_depth_normal != 0 */
+  void *workspace;               /* scorp_gs2d_view_terms_workspace_bytes(W, H, N), 16-byte aligned */
+  size_t workspace_bytes;
+} ScorpGs2dViewTerms;
+size_t scorp_gs2d_view_terms_workspace_bytes(int32_t width, int32_t height, int32_t num_gaussians);
+/* scorp_gs2d_train_view with the terms: between the photometric loss and the backward the view runs the two pixel passes
+ * and the isotropic value, its maps backward takes grad_depth / grad_normal next to the regularisers, and the per-surfel
+ * backward adds the isotropic gradient.  Total loss of the view = out_loss3[0] + out_reg2[0] + out_reg2[1] + out_terms6[0].
+ * With a depth map the view needs rays_d, rays_o and grad_allmap whatever the regularisers' weights.  terms == NULL:
+ * scorp_gs2d_train_view, launch for launch.  SCORP_ERR_INVALID before any launch: out_terms6 NULL, a weight without its map,
+ * weight_depth_normal without depth_est, a map without out_depth / grad_depth (/ grad_normal) / rays / grad_allmap, a
+ * workspace NULL, misaligned or too small, lambda_isotropic without the training layout. */
+int scorp_gs2d_train_view_ex(const ScorpGs2dTrainView *view, const ScorpGs2dViewTerms *terms, scorp_stream_t stream);
+/* The depth and depth-normal terms alone, on a caller-given allmap (what an autograd front-end wraps): values into
+ * out_terms6 (Liso = 0), grad_allmap[7,H,W] for an upstream gradient of 1 (every channel written).  At least one map;
+ * out_depth / grad_depth [H,W] and grad_normal [3,H,W] (with weight_depth_normal != 0) are the caller's scratch, as in the
+ * struct; workspace: scorp_gs2d_view_terms_workspace_bytes(W, H, 0). */
+int scorp_gs2d_surfel_terms(int32_t width, int32_t height, const float *allmap, const float *viewmatrix, const float *rays_d,
+                            const float *rays_o, float depth_ratio, const float *depth_sensor, const float *depth_est,
+                            float lambda_depth_sensor, float weight_depth_est, float weight_depth_normal, float *out_terms6,
+                            float *out_depth, float *grad_depth, float *grad_normal, float *grad_allmap, void *workspace,
+                            size_t workspace_bytes, scorp_stream_t stream);
+
 /* ---- rigid / scale transform of a whole model incl. its SH coefficients (utils/gaussians.py:12-108) ----
  * In place, one launch:  xyz <- ((xyz - c) R^T) * s + c + t;  rotation <- q (x) normalize(rotation) (w,x,y,z; q = the
  * quaternion of R);  scaling <- scaling + log(s) (log-space, `scale_dims` = 3, or 2 for surfels);  features_rest

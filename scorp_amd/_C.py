@@ -48,6 +48,13 @@ class ScorpGs3dViewTerms(ctypes.Structure):
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
+class ScorpGs2dViewTerms(ctypes.Structure):
+    _fields_ = [("depth_sensor", ctypes.c_void_p), ("depth_est", ctypes.c_void_p), ("lambda_depth_sensor", ctypes.c_float),
+                ("weight_depth_est", ctypes.c_float), ("weight_depth_normal", ctypes.c_float), ("lambda_isotropic", ctypes.c_float),
+                ("out_terms6", ctypes.c_void_p), ("out_depth", ctypes.c_void_p), ("grad_depth", ctypes.c_void_p),
+                ("grad_normal", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
 class ScorpFusedAdam(ctypes.Structure):
     _fields_ = [("exp_avg", ctypes.c_void_p * 6), ("exp_avg_sq", ctypes.c_void_p * 6), ("lr", ctypes.c_float * 6),
                 ("_pad", ctypes.c_float * 2), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
@@ -92,6 +99,7 @@ EXPORTS = [
     "scorp_gs2d_maps_backward", "scorp_gs2d_regularizers_workspace_bytes", "scorp_gs2d_regularizers_forward",
     "scorp_gs2d_regularizers_backward", "scorp_gs3d_train_view", "scorp_gs2d_train_view",
     "scorp_gs3d_view_terms_workspace_bytes", "scorp_gs3d_train_view_ex", "scorp_gs3d_depth_terms",
+    "scorp_gs2d_view_terms_workspace_bytes", "scorp_gs2d_train_view_ex", "scorp_gs2d_surfel_terms",
     "scorp_prof_enable", "scorp_prof_select", "scorp_prof_num_kernels", "scorp_prof_kernel_name", "scorp_prof_collect",
     "scorp_mask_vote_scratch_bytes", "scorp_gs3d_mask_vote", "scorp_gs2d_mask_vote",
     "scorp_icp_workspace_bytes", "scorp_icp_point_to_point",
@@ -178,6 +186,11 @@ def lib():
     L.scorp_gs3d_view_terms_workspace_bytes.argtypes = [i32, i32, i32]
     L.scorp_gs3d_train_view_ex.argtypes = [ctypes.POINTER(ScorpGs3dTrainView), ctypes.POINTER(ScorpGs3dViewTerms), vp]
     L.scorp_gs3d_depth_terms.argtypes = [i32, i32, vp, vp, vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, sz, vp]
+    L.scorp_gs2d_view_terms_workspace_bytes.restype = sz
+    L.scorp_gs2d_view_terms_workspace_bytes.argtypes = [i32, i32, i32]
+    L.scorp_gs2d_train_view_ex.argtypes = [ctypes.POINTER(ScorpGs2dTrainView), ctypes.POINTER(ScorpGs2dViewTerms), vp]
+    L.scorp_gs2d_surfel_terms.argtypes = [i32, i32, vp, vp, vp, vp, ctypes.c_float, vp, vp, ctypes.c_float, ctypes.c_float,
+                                          ctypes.c_float, vp, vp, vp, vp, vp, vp, sz, vp]
     L.scorp_knn_dist2.argtypes = [vp, i32, vp, vp]
     L.scorp_gaussians_transform.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.scorp_adam_step.argtypes = [ctypes.POINTER(ScorpAdamTensor), i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, vp]

@@ -480,7 +480,18 @@ int render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t 
                   scorp_stream_t stream, bool for_backward);
 int backward2d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity, const float *dL_dcolor,
                     const float *dL_dallmap, const ScorpGs3dGrads *grads, void *scratch, size_t scratch_bytes, uint32_t flags,
-                    scorp_stream_t stream, const AdamEpi *adam);
+                    scorp_stream_t stream, const AdamEpi *adam, float lambda_isotropic = 0.0f);
+// ---- the late iterations' loss terms of the 2DGS view (surfel_terms.hip): checked arguments in, launches out.  out_depth
+// [H,W] (the surface depth), g_depth [H,W] and g_normal [3,H,W] are written when a depth map / the depth-normal weight is
+// given; `scales` NULL: no isotropic value.
+int surfel_terms_impl(int W, int H, const float *allmap, const float *viewmatrix, const float *rays_d, const float *rays_o,
+                      float depth_ratio, const float *sensor, const float *est, float w_sensor, float w_est, float w_normal,
+                      const float *scales, int N, int raw, float lambda_iso, float *out_terms6, float *out_depth, float *g_depth,
+                      float *g_normal, void *workspace, hipStream_t stream);
+// the regularisers' maps backward with g_depth / g_surf_normal / g_render_normal (any may be NULL) added, one pass (gs2d_maps.hip)
+int maps_backward_terms_impl(int W, int H, const float *allmap, const float *viewmatrix, const float *rays_d, const float *rays_o,
+                             float depth_ratio, float lambda_normal, float lambda_dist, const float *g_depth,
+                             const float *g_surf_normal, const float *g_render_normal, float *g_allmap, hipStream_t stream);
 // one Adam update, the operation order of torch.optim.Adam (single-tensor, non-capturable): exp_avg.lerp_, addcmul_,
 // sqrt / div / add, addcdiv_; (1 - beta) is formed in double on the host, as torch does.  Shared by adam_kernel
 // (aux_kernels.hip) and the fused epilogue of preprocess_backward_kernel so that the two give the same bits.

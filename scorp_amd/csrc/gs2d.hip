@@ -869,10 +869,12 @@ blend2d_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint
 // issued, so that one memory latency covers it all instead of the chain radius -> visible? -> rows -> parameters behind
 // the stream.  Plain 16-byte loads here: the 44 dwords as untracked one-dword loads (the forward's way, which would also
 // let the maths start before the stream has landed) cost more in the texture pipe than they gain (121 vs 118 us).
-template <int DEG, bool SPLIT, bool LIN>
+// ISO: the isotropic regulariser's gradient (train_2dgs.py:136-139 over the [N,2] scales) joins the scaling gradient of EVERY
+// surfel of the block, visible or not; iso_k = lambda_isotropic / (4 N).  The plain instantiations do not know it exists.
+template <int DEG, bool SPLIT, bool LIN, bool ISO = false>
 __device__ __forceinline__ void preprocess2d_backward_body(const Pg2Args &a, float *s_sh, const Surfel *__restrict__ rec,
                                                            const BinRec *__restrict__ bin, const float *__restrict__ acc,
-                                                           const ScorpGs3dGrads &g, const AdamEpi &ad) {
+                                                           const ScorpGs3dGrads &g, const AdamEpi &ad, float iso_k = 0.0f) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool active = LIN || i < a.N;
   const size_t i0 = (size_t)blockIdx.x * 256;
@@ -1052,6 +1054,28 @@ __device__ __forceinline__ void preprocess2d_backward_body(const Pg2Args &a, flo
       for (int ch = 0; ch < 3; ch++) gr3[ch] = ((rad_bits >> (kClampShift + ch)) & 1) ? 0.0f : grgb[ch];
     }
   }
+  if constexpr (ISO) {
+    // d/d(raw scale j) of lambda * mean_{n,i} |s_ni - m_n| = lambda / (2 N) * (sgn_j - (sgn_0 + sgn_1) / 2) * ds_j/draw_j.
+    // The mean and the signs are taken in double (two equal scales then have the signs 0, as in exact arithmetic);
+    // 2 sgn_j - sum sgn is a small integer, so the gradient carries three fp32 roundings.  Contraction off where it joins
+    // the rasterizer's gradient: the written-gradient form and the step inside the view give the same bits.
+    if (active && (g.scales != nullptr || (adam_on && ad.m[4] != nullptr))) {
+#pragma clang fp contract(off)
+      float sv[2], sg[2];
+#pragma unroll
+      for (int k = 0; k < 2; k++) sv[k] = act_scale(LIN ? pre[7 + k] : a.scales[2 * (size_t)i + k], a.raw);
+      const double m = ((double)sv[0] + (double)sv[1]) / 2.0;
+#pragma unroll
+      for (int k = 0; k < 2; k++) sg[k] = (double)sv[k] > m ? 1.0f : (double)sv[k] < m ? -1.0f : 0.0f;
+      const float sgsum = sg[0] + sg[1];
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        float gi = iso_k * (2.0f * sg[k] - sgsum);
+        if (a.raw & 2) gi = gi * sv[k];   // d exp(v) / dv
+        gs[k] = gs[k] + gi;
+      }
+    }
+  }
   if (a.shs && lin) { stage_sh_wait(); __syncthreads(); }
   AdamGeomMoments am;   // asked for here, used in the epilogue: the SH phase in between hides the latency
   if (adam_on && active && !a.transmat) {
@@ -1135,6 +1159,21 @@ preprocess2d_backward_kernel(Pg2Args a, const Surfel *__restrict__ rec, const Bi
     }
   }
   preprocess2d_backward_body<DEG, SPLIT, false>(a, s_sh, rec, bin, acc, g, ad);
+}
+
+// The same kernel with the isotropic regulariser's gradient (split SH layout, scales + rotations: the training layout)
+template <int DEG>
+__global__ void __launch_bounds__(256)
+preprocess2d_backward_iso_kernel(Pg2Args a, const Surfel *__restrict__ rec, const BinRec *__restrict__ bin,
+                                 const float *__restrict__ acc, ScorpGs3dGrads g, AdamEpi ad, float iso_k) {
+  __shared__ __attribute__((aligned(16))) float s_sh[256 * kShStride];
+  if constexpr (DEG == 3) {
+    if (a.K == 16 && a.N - (int)blockIdx.x * 256 >= 256) {
+      preprocess2d_backward_body<DEG, true, true, true>(a, s_sh, rec, bin, acc, g, ad, iso_k);
+      return;
+    }
+  }
+  preprocess2d_backward_body<DEG, true, false, true>(a, s_sh, rec, bin, acc, g, ad, iso_k);
 }
 
 Pg2Args make_args2(const ScorpGs3dInputs *in, const StateLayout &L) {
@@ -1227,7 +1266,8 @@ extern "C" int scorp_gs2d_backward_ex(const ScorpGs3dInputs *in, const void *sta
 // `adam` (scorp_gs2d_train_view): the per-surfel kernel applies the optimizer step and the view's statistics itself
 int scorp::backward2d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                            const float *dL_dcolor, const float *dL_dallmap, const ScorpGs3dGrads *grads, void *scratch,
-                           size_t scratch_bytes, uint32_t flags, scorp_stream_t stream_, const AdamEpi *adam) {
+                           size_t scratch_bytes, uint32_t flags, scorp_stream_t stream_, const AdamEpi *adam,
+                           float lambda_isotropic) {
   hipStream_t stream = (hipStream_t)stream_;
   const char *base = (const char *)state, *pb = (const char *)pairs;
   auto blend = [&](const StateLayout &L, const PairLayout &P, float *acc, float *partial, uint8_t *row_flags, uint32_t *pair_base) {
@@ -1251,6 +1291,13 @@ int scorp::backward2d_impl(const ScorpGs3dInputs *in, const void *state, const v
     AdamEpi ad;
     memset(&ad, 0, sizeof(ad));
     if (adam && in->shs_rest) ad = *adam;   // (the fused step is defined for the training layout: dc / rest split leaves)
+    if (lambda_isotropic != 0.0f && a.N > 0 && in->shs && in->shs_rest && in->scales && !in->cov3D_precomp) {   // (the caller checked the layout; an empty model has no isotropic term)
+      const float iso_k = (float)((double)lambda_isotropic / (4.0 * (double)a.N));
+      dispatch_sh_degree(in->sh_degree, true, [&](auto D, auto) {
+        preprocess2d_backward_iso_kernel<D><<<grid, block, 0, stream>>>(a, rec, bin, acc, g, ad, iso_k);
+      });
+      return;
+    }
     dispatch_sh_degree(in->shs ? in->sh_degree : 0, in->shs_rest != nullptr, [&](auto D, auto S) {
       preprocess2d_backward_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, acc, g, ad);
     });

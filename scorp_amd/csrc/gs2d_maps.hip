@@ -8,57 +8,12 @@
 // read allmap once.  The backward is a gather: a pixel's depth enters the normals of its four 4-neighbours, so each
 // thread re-derives those four centres' normal gradients instead of scattering with atomics.
 #include "common.hpp"
+#include "gs2d_maps.hpp"
 
 namespace scorp {
 namespace {
 
-constexpr float kNormEps = 1e-12f;  // torch.nn.functional.normalize default eps
-
-struct MapsDev {
-  int W, H;
-  float depth_ratio;
-  const float *view;    // world_view_transform, 4x4 row-major as torch stores it (device)
-  const float *rays_o;  // [3] (device)
-};
-struct MapsArgs {
-  int W, H;
-  float depth_ratio;
-  float V[9];   // world_view_transform[:3,:3]
-  float ro[3];
-  __device__ explicit MapsArgs(const MapsDev &d) : W(d.W), H(d.H), depth_ratio(d.depth_ratio) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-#pragma unroll
-      for (int i = 0; i < 3; i++) V[j * 3 + i] = d.view[j * 4 + i];
-      ro[j] = d.rays_o[j];
-    }
-  }
-};
-
-// torch.nan_to_num(x, 0, 0): nan -> 0, +inf -> 0, -inf -> lowest finite
-__device__ __forceinline__ float nan_to_num00(float x) {
-  if (x != x) return 0.0f;
-  if (x == __builtin_inff()) return 0.0f;
-  if (x == -__builtin_inff()) return -3.402823466e+38f;
-  return x;
-}
-__device__ __forceinline__ bool passes_grad(float x) { return x == x && fabsf(x) != __builtin_inff(); }
-
-__device__ __forceinline__ float surf_depth_of(const float *__restrict__ allmap, size_t HW, size_t p, float r) {
-  const float e = nan_to_num00(allmap[p] / allmap[HW + p]);
-  const float m = nan_to_num00(allmap[5 * HW + p]);
-  return e * (1.0f - r) + r * m;
-}
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 cross3(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-__device__ __forceinline__ V3 point_of(float d, const float *__restrict__ rays_d, size_t p, const float *ro) {
-#pragma clang fp contract(off)
-  return {d * rays_d[3 * p] + ro[0], d * rays_d[3 * p + 1] + ro[1], d * rays_d[3 * p + 2] + ro[2]};
-}
+// (camera arguments, surface depth, points and normal frames: gs2d_maps.hpp)
 
 __global__ void __launch_bounds__(256)
 maps_forward_kernel(MapsDev dev, const float *__restrict__ allmap, const float *__restrict__ rays_d,
@@ -89,38 +44,6 @@ maps_forward_kernel(MapsDev dev, const float *__restrict__ allmap, const float *
   surf_normal[p] = n.x; surf_normal[HW + p] = n.y; surf_normal[2 * HW + p] = n.z;
 }
 
-// Where the backward takes its upstream gradients from.  kReg = false: the five gradient maps of an arbitrary loss
-// (scorp_gs2d_maps_backward).  kReg = true: the two regularisers of train_2dgs.py:142-150 fused in —
-// normal_loss = lambda_n * mean(1 - rend_normal . surf_normal), dist_loss = lambda_d * mean(render_dist) — whose
-// gradient maps are scaled copies of the OTHER map (d/d rend_normal = -k surf_normal, d/d surf_normal = -k rend_normal,
-// d/d dist = k_d) and are re-derived from allmap on the fly; the surface depth is recomputed instead of stored.
-struct MapsGrads {
-  const float *sd, *g_alpha, *g_rn, *g_dist, *g_sd, *g_sn;   // kReg = false
-  float kn, kd;                                               // kReg = true: lambda_n * g0 / HW, lambda_d * g1 / HW
-};
-
-template <bool kReg>
-__device__ __forceinline__ float depth_at(const MapsArgs &a, const MapsGrads &G, const float *__restrict__ allmap, size_t HW, size_t q) {
-  return kReg ? surf_depth_of(allmap, HW, q, a.depth_ratio) : G.sd[q];
-}
-
-// world-space rendered normal at pixel q (what render() returns as render_normal)
-__device__ __forceinline__ V3 world_normal(const MapsArgs &a, const float *__restrict__ allmap, size_t HW, size_t q) {
-  const float n0 = allmap[2 * HW + q], n1 = allmap[3 * HW + q], n2 = allmap[4 * HW + q];
-  return {n0 * a.V[0] + n1 * a.V[1] + n2 * a.V[2], n0 * a.V[3] + n1 * a.V[4] + n2 * a.V[5], n0 * a.V[6] + n1 * a.V[7] + n2 * a.V[8]};
-}
-
-// the two difference vectors of the normal centred at pixel c (must be interior), their cross product and its length
-template <bool kReg>
-__device__ __forceinline__ void centre_frame(const MapsArgs &a, const MapsGrads &G, const float *__restrict__ rays_d,
-                                             const float *__restrict__ allmap, size_t HW, size_t c, V3 &dv, V3 &dh, V3 &cr,
-                                             float &len) {
-  const size_t pu = c - a.W, pd = c + a.W, pl = c - 1, pr = c + 1;
-  dv = point_of(depth_at<kReg>(a, G, allmap, HW, pd), rays_d, pd, a.ro) - point_of(depth_at<kReg>(a, G, allmap, HW, pu), rays_d, pu, a.ro);
-  dh = point_of(depth_at<kReg>(a, G, allmap, HW, pr), rays_d, pr, a.ro) - point_of(depth_at<kReg>(a, G, allmap, HW, pl), rays_d, pl, a.ro);
-  cr = cross3(dv, dh);
-  len = sqrtf(dot3(cr, cr));
-}
 
 // Gradient of the loss with respect to the two difference vectors dv, dh of a normal, given the gradient G with respect to the
 // (alpha-weighted) unit normal: through normalize(dv x dh) and the cross product.
@@ -145,10 +68,15 @@ __device__ __forceinline__ void frame_grads(const V3 dv, const V3 dh, const V3 c
 // 2.1 depths and 1.5 frames per pixel.  Same expressions in the same order per value.
 constexpr int kRT_W = 64, kRT_H = 4, kRT_PW = kRT_W + 4, kRT_PH = kRT_H + 4, kRT_CW = kRT_W + 2, kRT_CH = kRT_H + 2;
 // (tiles of 8 rows: the same 40 us; of 16: 50)
-template <bool kReg>
-__global__ void __launch_bounds__(256)
-maps_backward_tiled_kernel(MapsDev dev, const float *__restrict__ allmap, const float *__restrict__ rays_d, MapsGrads Gr,
-                           const float *__restrict__ g_out2, float lambda_normal, float lambda_dist, float *__restrict__ g_allmap) {
+// kTerms (with kReg): the late iterations' terms (surfel_terms.hip) join the regularisers in the same pass - Gr.g_sd [H,W] is
+// d loss / d surface depth of the two depth terms (or NULL), Gr.g_sn and Gr.g_rn [3,H,W] are the depth-normal terms'
+// gradients with respect to surf_normal and the world-space render_normal (both NULL: no such term).
+template <bool kReg, bool kTerms>
+__device__ __forceinline__ void maps_backward_tiled_body(const MapsDev &dev, const float *__restrict__ allmap,
+                                                         const float *__restrict__ rays_d, MapsGrads Gr,
+                                                         const float *__restrict__ g_out2, float lambda_normal, float lambda_dist,
+                                                         float *__restrict__ g_allmap) {
+  static_assert(kReg || !kTerms, "the terms join the regularisers' instantiation");
   const MapsArgs a(dev);
   __shared__ float sP[3][kRT_PW * kRT_PH];        // surface points
   __shared__ float sG[kReg ? 9 : 6][kRT_CW * kRT_CH];   // per centre: g_dv (3), g_dh (3); kReg: -k alpha normalize(dv x dh) (3)
@@ -187,6 +115,12 @@ maps_backward_tiled_kernel(MapsDev dev, const float *__restrict__ allmap, const 
           G = {-Gr.kn * rn.x * al, -Gr.kn * rn.y * al, -Gr.kn * rn.z * al};
           const float sc = -Gr.kn * al / fmaxf(len, kNormEps);
           grn = {cr.x * sc, cr.y * sc, cr.z * sc};
+          if constexpr (kTerms) {
+            if (Gr.g_sn) {
+              G = {G.x + Gr.g_sn[c] * al, G.y + Gr.g_sn[HW + c] * al, G.z + Gr.g_sn[2 * HW + c] * al};
+              grn = {grn.x + Gr.g_rn[c], grn.y + Gr.g_rn[HW + c], grn.z + Gr.g_rn[2 * HW + c]};
+            }
+          }
         } else {
           G = {Gr.g_sn[c] * al, Gr.g_sn[HW + c] * al, Gr.g_sn[2 * HW + c] * al};
         }
@@ -202,7 +136,7 @@ maps_backward_tiled_kernel(MapsDev dev, const float *__restrict__ allmap, const 
   const size_t p = (size_t)y * a.W + x;
   const bool xin = x >= 1 && x < a.W - 1, yin = y >= 1 && y < a.H - 1;
   const int ci = (ty + 1) * kRT_CW + (tx + 1);   // this pixel in the centre tile
-  float gd = (!kReg && Gr.g_sd) ? Gr.g_sd[p] : 0.0f;
+  float gd = ((!kReg || kTerms) && Gr.g_sd) ? Gr.g_sd[p] : 0.0f;
   if (want_frames) {
     V3 gp = {0.0f, 0.0f, 0.0f};
     if (xin && y >= 2) { const int j = ci - kRT_CW; gp.x += sG[0][j]; gp.y += sG[1][j]; gp.z += sG[2][j]; }         // the lower end of dv there
@@ -227,6 +161,20 @@ maps_backward_tiled_kernel(MapsDev dev, const float *__restrict__ allmap, const 
   for (int i = 0; i < 3; i++) g_allmap[(2 + i) * HW + p] = grn.x * a.V[i] + grn.y * a.V[3 + i] + grn.z * a.V[6 + i];
   g_allmap[5 * HW + p] = passes_grad(med) ? gd * a.depth_ratio : 0.0f;
   g_allmap[6 * HW + p] = kReg ? Gr.kd : (Gr.g_dist ? Gr.g_dist[p] : 0.0f);
+}
+
+template <bool kReg>
+__global__ void __launch_bounds__(256)
+maps_backward_tiled_kernel(MapsDev dev, const float *__restrict__ allmap, const float *__restrict__ rays_d, MapsGrads Gr,
+                           const float *__restrict__ g_out2, float lambda_normal, float lambda_dist, float *__restrict__ g_allmap) {
+  maps_backward_tiled_body<kReg, false>(dev, allmap, rays_d, Gr, g_out2, lambda_normal, lambda_dist, g_allmap);
+}
+
+// the regularisers' instantiation with the late iterations' terms: grad_allmap is still written once, by one kernel
+__global__ void __launch_bounds__(256)
+maps_backward_terms_kernel(MapsDev dev, const float *__restrict__ allmap, const float *__restrict__ rays_d, MapsGrads Gr,
+                           float lambda_normal, float lambda_dist, float *__restrict__ g_allmap) {
+  maps_backward_tiled_body<true, true>(dev, allmap, rays_d, Gr, nullptr, lambda_normal, lambda_dist, g_allmap);
 }
 
 // ---- the regularisers' forward: per-block partial sums of (1 - rend_normal . surf_normal) and render_dist ----
@@ -279,12 +227,6 @@ reg_finalize_kernel(const float *__restrict__ partials, int nblocks, double inv_
   }
 }
 
-int fill_args(MapsDev &a, int W, int H, const float *viewmatrix, const float *rays_o, float depth_ratio) {
-  if (W <= 0 || H <= 0) { set_error("bad image size %dx%d", W, H); return SCORP_ERR_INVALID; }
-  if (!viewmatrix || !rays_o) { set_error("viewmatrix / rays_o is NULL"); return SCORP_ERR_INVALID; }
-  a.W = W; a.H = H; a.depth_ratio = depth_ratio; a.view = viewmatrix; a.rays_o = rays_o;
-  return SCORP_OK;
-}
 
 }  // namespace
 }  // namespace scorp
@@ -328,6 +270,24 @@ extern "C" int scorp_gs2d_maps_backward(int32_t W, int32_t H, const float *allma
         a, allmap, rays_d, Gr, nullptr, 0.0f, 0.0f, g_allmap);
   }
   SCORP_KERNEL_CHECK("surfel_maps_backward", 0, stream);
+  return SCORP_OK;
+}
+
+// The view's maps backward with the terms (scorp_gs2d_train_view_ex, scorp_gs2d_surfel_terms); arguments checked by the caller
+int scorp::maps_backward_terms_impl(int W, int H, const float *allmap, const float *viewmatrix, const float *rays_d,
+                                    const float *rays_o, float depth_ratio, float lambda_normal, float lambda_dist,
+                                    const float *g_depth, const float *g_surf_normal, const float *g_render_normal,
+                                    float *g_allmap, hipStream_t stream) {
+  MapsDev a;
+  if (int e = fill_args(a, W, H, viewmatrix, rays_o, depth_ratio)) return e;
+  {
+    ProfScope prof(kKMapsBackward2d, stream);
+    MapsGrads Gr = {};
+    Gr.g_sd = g_depth; Gr.g_sn = g_surf_normal; Gr.g_rn = g_render_normal;
+    maps_backward_terms_kernel<<<dim3((W + kRT_W - 1) / kRT_W, (H + kRT_H - 1) / kRT_H), 256, 0, stream>>>(
+        a, allmap, rays_d, Gr, lambda_normal, lambda_dist, g_allmap);
+  }
+  SCORP_KERNEL_CHECK("surfel_terms_maps_backward", 0, stream);
   return SCORP_OK;
 }
 

@@ -1,7 +1,8 @@
 // train_view.hip — scorp_gs3d_train_view: one training view (render, L1 + SSIM loss, backward) enqueued by ONE call.
 // Host code only: it chains the library's own entry points, so the kernels, their order and their results are those
 // of the separate calls (train_3dgs.py:88-150 minus the optimizer step).  See include/scorp_gs.h for the contract.
-// scorp_gs3d_train_view_ex adds the late iterations' terms (depth_terms.hip) between the loss and the backward.
+// scorp_gs3d_train_view_ex adds the late iterations' terms (depth_terms.hip) between the loss and the backward;
+// scorp_gs2d_train_view_ex is its 2DGS twin (surfel_terms.hip).
 #include <math.h>
 
 #include "common.hpp"
@@ -117,6 +118,46 @@ extern "C" int scorp_gs3d_train_view_ex(const ScorpGs3dTrainView *v, const Scorp
 }
 
 extern "C" int scorp_gs2d_train_view(const ScorpGs2dTrainView *v, scorp_stream_t stream) {
+  return scorp_gs2d_train_view_ex(v, nullptr, stream);
+}
+
+// The arguments of the 2DGS view's late-iteration terms, before anything is launched
+static int check_view_terms2d(const ScorpGs2dTrainView *v, const ScorpGs2dViewTerms *t) {
+  const ScorpGs3dInputs *in = v->in;
+  if (!t->out_terms6) { set_error("scorp_gs2d_train_view_ex: out_terms6 is NULL"); return SCORP_ERR_INVALID; }
+  if (t->lambda_depth_sensor != 0.0f && !t->depth_sensor) {
+    set_error("scorp_gs2d_train_view_ex: lambda_depth_sensor without depth_sensor"); return SCORP_ERR_INVALID;
+  }
+  if (t->weight_depth_est != 0.0f && !t->depth_est) {
+    set_error("scorp_gs2d_train_view_ex: weight_depth_est without depth_est"); return SCORP_ERR_INVALID;
+  }
+  if (t->weight_depth_normal != 0.0f && !t->depth_est) {
+    set_error("scorp_gs2d_train_view_ex: weight_depth_normal without depth_est"); return SCORP_ERR_INVALID;
+  }
+  if (t->depth_sensor || t->depth_est) {
+    if (!t->out_depth || !t->grad_depth) {
+      set_error("scorp_gs2d_train_view_ex: the depth terms need out_depth and grad_depth"); return SCORP_ERR_INVALID;
+    }
+    if (t->weight_depth_normal != 0.0f && !t->grad_normal) {
+      set_error("scorp_gs2d_train_view_ex: weight_depth_normal needs grad_normal"); return SCORP_ERR_INVALID;
+    }
+    if (!v->rays_d || !v->rays_o || !v->grad_allmap) {
+      set_error("scorp_gs2d_train_view_ex: the depth terms need rays_d, rays_o and grad_allmap"); return SCORP_ERR_INVALID;
+    }
+  }
+  if (t->lambda_isotropic != 0.0f && (!in->scales || !in->rotations || in->cov3D_precomp || !in->shs || !in->shs_rest)) {
+    set_error("scorp_gs2d_train_view_ex: lambda_isotropic needs the training layout (scales + rotations, shs + shs_rest)");
+    return SCORP_ERR_INVALID;
+  }
+  const size_t need = scorp_gs2d_view_terms_workspace_bytes(in->image_width, in->image_height, in->num_gaussians);
+  if (!t->workspace || t->workspace_bytes < need || ((uintptr_t)t->workspace & 15)) {
+    set_error("scorp_gs2d_train_view_ex: terms workspace NULL, misaligned or too small (%zu < %zu)", t->workspace_bytes, need);
+    return SCORP_ERR_INVALID;
+  }
+  return SCORP_OK;
+}
+
+extern "C" int scorp_gs2d_train_view_ex(const ScorpGs2dTrainView *v, const ScorpGs2dViewTerms *terms, scorp_stream_t stream) {
   if (!v || !v->in || !v->grads) { set_error("NULL argument to scorp_gs2d_train_view"); return SCORP_ERR_INVALID; }
   if (!v->out_color || !v->out_allmap || !v->out_radii || !v->gt || !v->out_loss3 || !v->out_reg2 || !v->grad_color) {
     set_error("scorp_gs2d_train_view: an output / ground-truth / scratch pointer is NULL");
@@ -129,6 +170,7 @@ extern "C" int scorp_gs2d_train_view(const ScorpGs2dTrainView *v, scorp_stream_t
     set_error("scorp_gs2d_train_view: the regularisers need rays_d, rays_o, grad_allmap and reg_workspace");
     return SCORP_ERR_INVALID;
   }
+  if (terms) if (int e = check_view_terms2d(v, terms)) return e;
   hipStream_t hs = (hipStream_t)stream;
   if (int e = preprocess2d_impl(in, v->out_radii, v->state, v->state_bytes, stream)) return e;
   if (int e = render2d_impl(in, v->state, v->pairs, v->capacity, v->out_color, v->out_allmap, stream, true)) return e;
@@ -143,13 +185,27 @@ extern "C" int scorp_gs2d_train_view(const ScorpGs2dTrainView *v, scorp_stream_t
   }
   if (int e = loss_backward_impl(v->out_color, v->gt, v->mask, 3, H, W, v->lambda_dssim, v->loss_workspace, nullptr,
                                  v->grad_color, v->out_loss3, hs)) return e;
-  if (reg) {
+  // the late iterations' terms (train_2dgs.py:100-139): their values, and the gradient maps that join the regularisers'
+  // gradients in ONE pass over grad_allmap (maps_backward_terms_kernel)
+  const bool depth_terms = terms && (terms->depth_sensor || terms->depth_est) && W > 0 && H > 0;
+  const float lambda_iso = terms ? terms->lambda_isotropic : 0.0f;
+  if (terms) {
+    if (int e = surfel_terms_impl(W, H, v->out_allmap, in->viewmatrix, v->rays_d, v->rays_o, v->depth_ratio, terms->depth_sensor,
+                                  terms->depth_est, terms->lambda_depth_sensor, terms->weight_depth_est, terms->weight_depth_normal,
+                                  lambda_iso != 0.0f ? in->scales : nullptr, in->num_gaussians, in->raw_params, lambda_iso,
+                                  terms->out_terms6, terms->out_depth, terms->grad_depth, terms->grad_normal, terms->workspace, hs)) return e;
+  }
+  if (depth_terms) {
+    const float *gn = terms->weight_depth_normal != 0.0f ? terms->grad_normal : nullptr;
+    if (int e = maps_backward_terms_impl(W, H, v->out_allmap, in->viewmatrix, v->rays_d, v->rays_o, v->depth_ratio,
+                                         v->lambda_normal, v->lambda_dist, terms->grad_depth, gn, gn, v->grad_allmap, hs)) return e;
+  } else if (reg) {
     if (int e = scorp_gs2d_regularizers_backward(W, H, v->out_allmap, in->viewmatrix, v->rays_d, v->rays_o, v->depth_ratio,
                                                  v->lambda_normal, v->lambda_dist, nullptr, v->grad_allmap, stream)) return e;
   }
   AdamEpi ad;
   if (int e = make_adam_epi(v->adam, in, 2, reinterpret_cast<const uint32_t *>(v->state) + 1, &ad)) return e;
-  return backward2d_impl(in, v->state, v->pairs, v->capacity, v->grad_color, reg ? v->grad_allmap : nullptr, v->grads,
+  return backward2d_impl(in, v->state, v->pairs, v->capacity, v->grad_color, (reg || depth_terms) ? v->grad_allmap : nullptr, v->grads,
                          v->backward_scratch, v->backward_scratch_bytes, v->backward_flags & ~SCORP_BACKWARD_SCRATCH_ZEROED,
-                         stream, v->adam ? &ad : nullptr);
+                         stream, v->adam ? &ad : nullptr, lambda_iso);
 }

@@ -111,3 +111,15 @@ def depth_losses(rend_depth, iteration, opt, gt_depth=None, gt_depth_est=None):
         mask = (rend_depth > 0.0) & (gt_depth_est > 0.0)
         loss = loss + 10 * w * l1_loss(depth_normalize_(rend_depth[mask]), depth_normalize_(gt_depth_est[mask]))
     return loss
+
+
+def depth_normal_losses(pkg, viewpoint_camera, depth_est):
+    """The two depth-normal terms of train_2dgs.py:126-134, unweighted: (mean(1 - surf_normal . pred_normal),
+    mean(1 - render_normal . pred_normal)) with pred_normal = depth_to_normal(camera, depth_est) under no_grad.  `pkg`: what
+    the 2DGS render() returns.  The caller weights their sum by dn_l1_weight(iteration) after depth_from_iter + 1000."""
+    from .renderer2d import depth_to_normal
+    with torch.no_grad():
+        pred_normal = depth_to_normal(viewpoint_camera, depth_est.reshape(1, *depth_est.shape[-2:])).permute(2, 0, 1)
+    depth_normal_loss = (1 - (pkg["surf_normal"] * pred_normal).sum(dim=0)).mean()
+    render_normal_loss = (1 - (pkg["render_normal"] * pred_normal).sum(dim=0)).mean()
+    return depth_normal_loss, render_normal_loss

@@ -23,7 +23,7 @@ import torch.distributed as dist
 
 from .fused_loss import fused_l1_ssim_loss
 from .rasterizer3d import PairPolicy
-from .loss import depth_losses, isotropic_loss, psnr
+from .loss import depth_losses, depth_normal_losses, isotropic_loss, psnr
 from .parallel import average_gradients, average_gradients_sparse, collective, world
 from .renderer import render
 
@@ -67,8 +67,8 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
     caller hands each rank a different camera; gradients are averaged over ranks before the optimizer step and the
     densification statistics are reduced before they are used, so the replicas stay bit-identical.
     `fused_step` (with `fused_view`): let the view apply the optimizer step itself where that is the same computation (see
-    below).  `view_fn`: the one-call view (default train_view.train_view; the CPU tests of the loop's bookkeeping pass a
-    stand-in)."""
+    below).  `view_fn`: the one-call view (default train_view.train_view, train_view.train_view2d for surfels; the CPU tests of
+    the loop's bookkeeping pass a stand-in)."""
     stepped_in_view = False
     gaussians.update_learning_rate(iteration)
     if iteration % 1000 == 0:
@@ -76,10 +76,12 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
     bg = torch.rand(3, device=background.device) if opt.random_background else background
     extra_terms = iteration > getattr(opt, "depth_from_iter", 1 << 30) and (
         gt_depth is not None or gt_depth_est is not None or getattr(opt, "lambda_isotropic", 0.0) > 0)
-    if (fused_view and surfels and not extra_terms and loss_fn is fused_l1_ssim_loss and getattr(pipe, "fused_activations", False)
+    if (fused_view and surfels and loss_fn is fused_l1_ssim_loss and getattr(pipe, "fused_activations", False)
             and hasattr(gaussians, "raw_leaves")):
-        # the 2DGS iteration (train_2dgs.py:95-150) by ONE library call: render + loss + regularisers + backward
-        from .train_view import train_view2d
+        # the 2DGS iteration (train_2dgs.py:95-150) by ONE library call: render + loss + regularisers + backward.  After
+        # depth_from_iter the view carries the depth, depth-normal and isotropic terms too (the conditions of the `else:`
+        # branch below), so the three quarters of a default run that have them stay on this path.
+        view_fn = view_fn or _default_view2d_fn()
         lambda_normal = opt.lambda_normal if iteration > 7000 else 0.0
         lambda_dist = opt.lambda_dist if iteration > 3000 else 0.0
         kw_view = {}
@@ -87,7 +89,9 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
             kw_view["optimizer"] = gaussians.optimizer
             if densify and iteration < opt.densify_until_iter and _stats_components(gaussians) == 3:
                 kw_view["stats"] = (gaussians.max_radii2D, gaussians.xyz_gradient_accum, gaussians.denom)
-        pkg = train_view2d(cam, gaussians, pipe, bg, gt_image, opt.lambda_dssim, lambda_normal, lambda_dist, **kw_view)
+        if extra_terms:
+            kw_view.update(_view_terms_kw(opt, iteration, gt_depth, gt_depth_est, surfels=True))
+        pkg = view_fn(cam, gaussians, pipe, bg, gt_image, opt.lambda_dssim, lambda_normal, lambda_dist, **kw_view)
         loss = pkg["loss"]
         stepped_in_view = bool(pkg.get("optimizer_stepped"))
         ovf = _shared_overflow(pkg, data_parallel)
@@ -136,6 +140,10 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
         if iteration > getattr(opt, "depth_from_iter", 1 << 30):
             if gt_depth is not None or gt_depth_est is not None:
                 loss = loss + depth_losses(pkg["render_depth"], iteration, opt, gt_depth, gt_depth_est)
+            if surfels and gt_depth_est is not None and iteration > opt.depth_from_iter + 1000:   # train_2dgs.py:126-134
+                loss = loss + _dn_l1_weight(opt, iteration) * sum(depth_normal_losses(pkg, cam, gt_depth_est))
+            # (the reference's 2DGS script nests the isotropic line under the estimate, train_2dgs.py:136-139; this loop keeps
+            # one condition for both kinds: DESIGN.md 4.6)
             if getattr(opt, "lambda_isotropic", 0.0) > 0:
                 loss = loss + opt.lambda_isotropic * isotropic_loss(gaussians.get_scaling)
         if surfels:   # train_2dgs.py:142-150: normal consistency after 7000 iterations, depth distortion after 3000
@@ -185,16 +193,23 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
     return loss, pkg
 
 
-def _view_terms_kw(opt, iteration, gt_depth, gt_depth_est):
-    """The terms of train_3dgs.py:109-150 that apply at this iteration (> depth_from_iter), as train_view takes them: the
-    conditions and weights of loss.depth_losses and of the isotropic line of the autograd branch."""
+def _dn_l1_weight(opt, iteration):
     from .gaussian_model import get_expon_lr_func
+    return get_expon_lr_func(opt.dn_l1_weight_init, opt.dn_l1_weight_final, max_steps=opt.iterations)(iteration)
+
+
+def _view_terms_kw(opt, iteration, gt_depth, gt_depth_est, surfels=False):
+    """The terms of train_3dgs.py:109-150 / train_2dgs.py:100-139 that apply at this iteration (> depth_from_iter), as
+    train_view / train_view2d take them: the conditions and weights of loss.depth_losses, of the depth-normal lines (surfels,
+    after depth_from_iter + 1000) and of the isotropic line of the autograd branch."""
     kw = {}
     if gt_depth is not None:
         kw["depth_sensor"], kw["lambda_depth_sensor"] = gt_depth, opt.lambda_depth_sensor
     if gt_depth_est is not None:
-        w = get_expon_lr_func(opt.dn_l1_weight_init, opt.dn_l1_weight_final, max_steps=opt.iterations)(iteration)
+        w = _dn_l1_weight(opt, iteration)
         kw["depth_est"], kw["weight_depth_est"] = gt_depth_est, 10 * w
+        if surfels:
+            kw["weight_depth_normal"] = w if iteration > opt.depth_from_iter + 1000 else 0.0
     if getattr(opt, "lambda_isotropic", 0.0) > 0:
         kw["lambda_isotropic"] = opt.lambda_isotropic
     return kw
@@ -235,6 +250,11 @@ def _grad_arena(gaussians):
 def _default_view_fn():
     from .train_view import train_view
     return train_view
+
+
+def _default_view2d_fn():
+    from .train_view import train_view2d
+    return train_view2d
 
 
 def train(gaussians, cameras, gt_images, opt, pipe=None, iterations=None, background=None, seed=0, data_parallel=False,

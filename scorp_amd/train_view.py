@@ -200,13 +200,25 @@ class _ViewspaceGrad:
 
 
 def train_view2d(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2, lambda_normal=0.0, lambda_dist=0.0,
-                 mask=None, scaling_modifier=1.0, optimizer=None, stats=None):
+                 mask=None, scaling_modifier=1.0, optimizer=None, stats=None, depth_sensor=None, depth_est=None,
+                 lambda_depth_sensor=0.0, weight_depth_est=0.0, weight_depth_normal=0.0, lambda_isotropic=0.0):
     """The 2DGS twin of `train_view`: one iteration of train_2dgs.py:95-150 for the plain photometric loss plus the
     normal-consistency / depth-distortion regularisers (train_2dgs.py:142-150), enqueued by ONE library call
     (`scorp_gs2d_train_view`).  Returns "render", "allmap", "radii", "visibility_filter", "viewspace_points",
     "loss" (= photometric + normal + distortion, a 0-d device tensor), "l1", "ssim", "normal_loss", "dist_loss",
     "overflow"; parameter gradients are accumulated into the surfel model's leaves.  `optimizer` / `stats`: the optimizer
-    step and the view's densification statistics inside the view, as for `train_view` (ScorpGs2dTrainView.adam)."""
+    step and the view's densification statistics inside the view, as for `train_view` (ScorpGs2dTrainView.adam).
+
+    `depth_sensor` / `depth_est` ([1,H,W] or [H,W]), `lambda_depth_sensor`, `weight_depth_est` (= 10 * dn_l1_weight(iteration)),
+    `weight_depth_normal` (= dn_l1_weight(iteration) once iteration > depth_from_iter + 1000; needs `depth_est`) and
+    `lambda_isotropic`: the terms train_2dgs.py:100-139 adds after depth_from_iter, inside the same call
+    (scorp_gs2d_train_view_ex, ScorpGs2dViewTerms in include/scorp_gs.h: two pixel passes between the loss and the backward, their
+    gradient maps folded into the one maps backward, the isotropic gradient in the per-surfel backward kernel - with `optimizer`
+    the invisible surfels then take the step with that gradient alone).  The result gains "photometric_loss",
+    "depth_sensor_loss", "depth_est_loss", "depth_normal_loss", "render_normal_loss", "isotropic_loss" (unweighted, 0-d views of
+    one device tensor) and "render_depth" ([1,H,W], the surface depth the terms were taken on; None when no depth map was
+    given); "loss" is the total.  A depth term whose mask is empty or whose range is zero reads NaN and moves nothing.  With
+    all six at their defaults the call is the one it always was."""
     from .renderer2d import _camera_rays
     L = _C.lib()
     c = _View(_GS2D, "train_view2d", viewpoint_camera, pc, bg_color, gt_image, mask, scaling_modifier, optimizer, stats)
@@ -223,9 +235,50 @@ def train_view2d(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.
     v.lambda_normal, v.lambda_dist = float(lambda_normal), float(lambda_dist)
     v.out_loss3, v.out_reg2 = loss5.data_ptr(), loss5[3:].data_ptr()
     v.reg_workspace, v.reg_workspace_bytes = rws.data_ptr(), rws_bytes
-    _C.check(L.scorp_gs2d_train_view(ctypes.byref(v), _stream()), "scorp_gs2d_train_view")
+    terms = None
+    if (depth_sensor is not None or depth_est is not None or lambda_depth_sensor or weight_depth_est or weight_depth_normal
+            or lambda_isotropic):
+        terms, keep, depth = _view_terms2d(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est,
+                                           weight_depth_normal, lambda_isotropic)
+        _C.check(L.scorp_gs2d_train_view_ex(ctypes.byref(v), ctypes.byref(terms), _stream()), "scorp_gs2d_train_view_ex")
+    else:
+        _C.check(L.scorp_gs2d_train_view(ctypes.byref(v), _stream()), "scorp_gs2d_train_view")
     header = PairPolicy.pend(c.state, N, H, W)
     c.accumulate()
-    return {"optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "allmap": allmap, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": c.radii > 0,
-            "radii": c.radii, "loss": loss5[0] + loss5[3] + loss5[4], "l1": loss5[1], "ssim": loss5[2],
+    extra, total = {}, loss5[0] + loss5[3] + loss5[4]
+    if terms is not None:
+        t6 = keep[0]
+        extra = {"photometric_loss": loss5[0], "depth_sensor_loss": t6[1], "depth_est_loss": t6[2], "depth_normal_loss": t6[3],
+                 "render_normal_loss": t6[4], "isotropic_loss": t6[5], "render_depth": depth}
+        total = total + t6[0]
+    return {**extra, "optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "allmap": allmap, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": c.radii > 0,
+            "radii": c.radii, "loss": total, "l1": loss5[1], "ssim": loss5[2],
             "normal_loss": loss5[3], "dist_loss": loss5[4], "overflow": header.view(torch.int32)[1:2]}
+
+
+def _view_terms2d(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, weight_depth_normal, lambda_isotropic):
+    """The ScorpGs2dViewTerms of one view, the tensors it points to (out_terms6 first) and the surface-depth map (or None)."""
+    H, W, N = c.H, c.W, c.N
+    maps = []
+    for t, name in ((depth_sensor, "depth_sensor"), (depth_est, "depth_est")):
+        if t is not None:
+            if t.numel() != H * W:
+                raise ValueError(f"{name}: {tuple(t.shape)} is not a depth map of the view ({H} x {W})")
+            t = _prep(t, name)
+        maps.append(t)
+    ws_bytes = L.scorp_gs2d_view_terms_workspace_bytes(W, H, N)
+    keep = [c.new((6,)), c.new((ws_bytes,), torch.uint8), *maps]
+    t = _C.ScorpGs2dViewTerms()
+    t.depth_sensor, t.depth_est = (None if m is None else m.data_ptr() for m in maps)
+    t.lambda_depth_sensor, t.weight_depth_est = float(lambda_depth_sensor), float(weight_depth_est)
+    t.weight_depth_normal, t.lambda_isotropic = float(weight_depth_normal), float(lambda_isotropic)
+    t.out_terms6, t.workspace, t.workspace_bytes = keep[0].data_ptr(), keep[1].data_ptr(), ws_bytes
+    depth = None
+    if maps[0] is not None or maps[1] is not None:
+        depth = c.new((1, H, W))
+        keep += [depth, c.new((H, W))]
+        t.out_depth, t.grad_depth = depth.data_ptr(), keep[-1].data_ptr()
+        if weight_depth_normal:
+            keep.append(c.new((3, H, W)))
+            t.grad_normal = keep[-1].data_ptr()
+    return t, keep, depth
