@@ -283,6 +283,75 @@ int scorp_pose_adam_9dof(const double *source, const double *target, int32_t n_p
                          const double *init_scale, double *out, double *out_loss, int32_t loss_every, int32_t loss_capacity,
                          void *workspace, size_t workspace_bytes, scorp_stream_t stream);
 
+/* ---- multi-view TSDF fusion (gs2dgs/utils/mesh_utils.py:196-247 compute_sdf_perframe / compute_unbounded_tsdf) ----
+ * Every sample runs over all views in ONE launch with its running state in registers.  All pointers are device pointers.
+ * views:   depth[V, H, W], rgb[V, 3, H, W] (NULL: no colour), full_proj[V, 16] = each view's full_proj_transform as
+ *          stored (row-vector convention: p_h = [x y z 1] @ M, M row-major); every view has the same resolution.
+ * samples: the points xyz[*, 3], or (xyz NULL) the lattice x[nx], y[ny], z[nz] whose sample g = (ix ny + iy) nz + iz
+ *          (C order, z fastest).  The call handles the samples g in [first, first + count) and writes out_tsdf[g] and
+ *          out_rgb[3 g ..] - the arrays are addressed by the global index, so a caller splits a large M into calls by
+ *          moving `first` alone.  count <= (2^31 - 1) 256.
+ * params:  contracted != 0: the sample s lies in the contracted space, n = |s|, trunc = 5 voxel_size, times
+ *          1 / (2 - min(n, 1.9)) where n > 1, and the world point is uncontract(s) radius + center (uncontract(y) = y for
+ *          n < 1, y / n / (2 - n) otherwise); else trunc = 5 voxel_size and s is the world point.
+ * Per sample: tsdf = 1, w = 1, rgb = 0; then for view i = 0 .. V-1 in order: p = [s 1] @ M_i, zc = p.w, pix = p.xy / p.w,
+ * inside = all(pix > -1) & all(pix < 1) & zc > 0 (a NaN compares false), d = the bilinear sample of depth_i at pix
+ * (align_corners, border padding; a corner of weight 0 past the last row / column is not read), sdf = d - zc, and where
+ * inside & sdf > -trunc:  tsdf = (tsdf w + clamp(sdf / trunc, -1, 1)) / (w + 1), rgb likewise with the bilinear colour,
+ * w += 1.  out_rgb may be NULL (then views->rgb is not read).  Does not synchronise.  SCORP_ERR_INVALID: a NULL pointer,
+ * num_views < 1, width or height < 2, count < 1 (or above the bound, or past the lattice), voxel_size <= 0, radius <= 0
+ * with contracted, out_rgb without views->rgb. */
+typedef struct ScorpTsdfViews {
+  const float *depth;
+  const float *rgb;
+  const float *full_proj;
+  int32_t num_views, width, height, _pad;
+} ScorpTsdfViews;
+typedef struct ScorpTsdfSamples {
+  const float *xyz;
+  const float *x, *y, *z;
+  int32_t nx, ny, nz, _pad;
+  uint64_t first, count;
+} ScorpTsdfSamples;
+typedef struct ScorpTsdfParams {
+  double voxel_size; /* trunc = (float)(5 voxel_size): the reference forms the product in double */
+  float center[3];
+  float radius;
+  int32_t contracted, _pad;
+} ScorpTsdfParams;
+int scorp_tsdf_fuse(const ScorpTsdfViews *views, const ScorpTsdfSamples *samples, const ScorpTsdfParams *params,
+                    float *out_tsdf, float *out_rgb, scorp_stream_t stream);
+
+/* ---- surface extraction from a dense grid: naive surface nets, no tables ----
+ * f[nx, ny, nz] fp32 in C order with the coordinate arrays x[nx], y[ny], z[nz]; a lattice point is INSIDE when
+ * f < level.  Cell (i, j, k), 0 <= i < nx - 1 (likewise j, k), linear index (i (ny - 1) + j)(nz - 1) + k, is ACTIVE when
+ * its 8 corners are neither all inside nor all outside.  An active cell owns one vertex: the mean over its sign-changing
+ * edges (x-edges, then y-edges, then z-edges, each by ascending first corner, corner index = 4 di + 2 dj + dk) of the
+ * crossing at t = (level - f0) / (f1 - f0), in the cell's own coordinates, then mapped through the coordinate arrays
+ * (x[i] + frac (x[i + 1] - x[i])).  A lattice edge q -> q + e_a whose ends differ in inside-ness, with the other two
+ * indices of q in 1 .. n - 2, gives the quad of the four cells round it, (b, c) = the axes after a in cyclic order:
+ * c00 = cell(q), c10 = cell(q - e_b), c11 = cell(q - e_b - e_c), c01 = cell(q - e_c), as the triangles (c00, c10, c11),
+ * (c00, c11, c01) when q is inside and reversed, (c00, c11, c10), (c00, c01, c11), otherwise: the normal points from
+ * inside to outside.  Vertices follow the ascending cell index, quads the ascending linear index of q, then a: two
+ * passes with a scan (the caller's) between them, no atomics.
+ *   count_cells:   out_flags[cells] = 1 for an active cell, else 0
+ *   emit_vertices: cell_scan[cells] = the INCLUSIVE int32 prefix sum of the flags; vertex cell_scan[c] - 1 of every active
+ *                  cell c into out_vertices[num_vertices, 3]
+ *   count_faces:   out_counts[nx ny nz] = quads of lattice point q (0 .. 3)
+ *   emit_faces:    edge_scan[nx ny nz] = the inclusive int32 prefix sum of the counts; the two triangles of quad r into
+ *                  out_faces[2 r .. 2 r + 1, 3] (int32 vertex indices), num_quads in all
+ * None synchronises.  SCORP_ERR_INVALID: a NULL pointer, a dimension < 2, more than (2^31 - 1) 256 lattice points, more
+ * than 2^31 - 1 vertices or quads. */
+int scorp_isosurface_count_cells(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, uint8_t *out_flags,
+                                 scorp_stream_t stream);
+int scorp_isosurface_emit_vertices(const float *f, const float *x, const float *y, const float *z, int32_t nx, int32_t ny,
+                                   int32_t nz, float level, const int32_t *cell_scan, int64_t num_vertices,
+                                   float *out_vertices, scorp_stream_t stream);
+int scorp_isosurface_count_faces(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, uint8_t *out_counts,
+                                 scorp_stream_t stream);
+int scorp_isosurface_emit_faces(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, const int32_t *cell_scan,
+                                const int32_t *edge_scan, int64_t num_quads, int32_t *out_faces, scorp_stream_t stream);
+
 /* ---- introspection for stage-level parity tests (device->host copies; synchronises) ---- */
 /* xy[N,2], depth[N], conic_opacity[N,4], rgb[N,3], rect[N,4] (tile units, max exclusive); any may be NULL. */
 int scorp_gs3d_debug_geom(const void *state, int32_t num_gaussians, int32_t image_width, int32_t image_height,

@@ -76,6 +76,22 @@ class ScorpGs2dTrainView(ctypes.Structure):
                 ("backward_flags", ctypes.c_uint32), ("adam", ctypes.c_void_p)]
 
 
+class ScorpTsdfViews(ctypes.Structure):
+    _fields_ = [("depth", c_float_p), ("rgb", c_float_p), ("full_proj", c_float_p), ("num_views", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class ScorpTsdfSamples(ctypes.Structure):
+    _fields_ = [("xyz", c_float_p), ("x", c_float_p), ("y", c_float_p), ("z", c_float_p), ("nx", ctypes.c_int32),
+                ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("_pad", ctypes.c_int32), ("first", ctypes.c_uint64),
+                ("count", ctypes.c_uint64)]
+
+
+class ScorpTsdfParams(ctypes.Structure):
+    _fields_ = [("voxel_size", ctypes.c_double), ("center", ctypes.c_float * 3), ("radius", ctypes.c_float),
+                ("contracted", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
 class ScorpRowTensor(ctypes.Structure):
     _fields_ = [("src", c_float_p), ("dst", c_float_p), ("row_floats", ctypes.c_uint32), ("zero_if_fresh", ctypes.c_uint32)]
 
@@ -104,6 +120,8 @@ EXPORTS = [
     "scorp_mask_vote_scratch_bytes", "scorp_gs3d_mask_vote", "scorp_gs2d_mask_vote",
     "scorp_icp_workspace_bytes", "scorp_icp_point_to_point",
     "scorp_pose_fit_workspace_bytes", "scorp_pose_ransac", "scorp_pose_adam_9dof",
+    "scorp_tsdf_fuse", "scorp_isosurface_count_cells", "scorp_isosurface_emit_vertices", "scorp_isosurface_count_faces",
+    "scorp_isosurface_emit_faces",
 ]
 
 BACKWARD_EXACT_FP32 = 1   # scorp_gs3d_backward_ex flag (include/scorp_gs.h)
@@ -213,6 +231,13 @@ def lib():
     L.scorp_pose_fit_workspace_bytes.argtypes = [i32, i32]
     L.scorp_pose_ransac.argtypes = [vp, vp, i32, vp, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.scorp_pose_adam_9dof.argtypes = [vp, vp, i32, i32, f64, f64, f64, f64, f64, ctypes.POINTER(f64), vp, vp, i32, i32, vp, sz, vp]
+    L.scorp_tsdf_fuse.argtypes = [ctypes.POINTER(ScorpTsdfViews), ctypes.POINTER(ScorpTsdfSamples), ctypes.POINTER(ScorpTsdfParams),
+                                  vp, vp, vp]
+    i64 = ctypes.c_int64
+    L.scorp_isosurface_count_cells.argtypes = [vp, i32, i32, i32, ctypes.c_float, vp, vp]
+    L.scorp_isosurface_emit_vertices.argtypes = [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, i64, vp, vp]
+    L.scorp_isosurface_count_faces.argtypes = [vp, i32, i32, i32, ctypes.c_float, vp, vp]
+    L.scorp_isosurface_emit_faces.argtypes = [vp, i32, i32, i32, ctypes.c_float, vp, vp, i64, vp, vp]
     L.scorp_prof_enable.argtypes = [ctypes.c_int]
     L.scorp_prof_select.argtypes = [u64]
     L.scorp_prof_kernel_name.restype = ctypes.c_char_p

@@ -1,0 +1,418 @@
+"""From a trained surfel model to a coloured triangle mesh: gs2dgs/utils/mesh_utils.py's GaussianExtractor
+(reconstruction, estimate_bounding_sphere, extract_mesh_unbounded / compute_unbounded_tsdf) and the lattice of
+gs2dgs/utils/mcube_utils.py, on the GPU.
+
+    ex = GaussianExtractor(gaussians, render, pipe)
+    ex.reconstruction(cameras)
+    write_mesh_ply("mesh.ply", ex.extract_mesh_unbounded(resolution=512))
+
+The depth and colour maps stay on the device as two stacked tensors.  The TSDF of every sample is fused over all views by
+one launch (csrc/tsdf.hip: scorp_tsdf_fuse), the volume is ONE dense grid (no 512^3 crops, so no crop seams and no
+restriction of `resolution` to multiples of 512), and the surface is extracted by surface nets (csrc/isosurface.hip) -
+not marching cubes: one vertex per cell the surface crosses, which lies in the same cell as the marching-cubes vertices
+of that cell.  `extract_mesh_bounded` (Open3D's ScalableTSDFVolume), mesh simplification and `post_process_mesh`
+(Open3D clustering) are not built.
+
+CUDA tensors run the HIP kernels; CPU tensors run a torch / numpy form of the same statements.
+"""
+import ctypes
+import os
+from dataclasses import dataclass
+from functools import partial
+
+import numpy as np
+import torch
+
+from . import _C
+
+MAX_RANGE = 32.0            # mcube_utils.py:26,93: the un-contracted vertices are clipped to +-max_range
+LAUNCH_SAMPLES = 1 << 30    # samples per scorp_tsdf_fuse call (the C ABI takes up to (2^31 - 1) * 256)
+
+
+@dataclass
+class Mesh:
+    """vertices [Nv, 3] float32, faces [Nf, 3] int32 (vertex indices), colors [Nv, 3] float32 in [0, 1]."""
+    vertices: torch.Tensor
+    faces: torch.Tensor
+    colors: torch.Tensor
+
+
+def uncontract(y):
+    """Contracted space back to the normalised one: a point of norm n >= 1 goes to norm 1 / (2 - n) on its ray, the unit
+    ball stays (the inverse of the contraction n -> 2 - 1 / n that the reference's unbounded route works in)."""
+    n = torch.linalg.vector_norm(y, dim=-1, keepdim=True)
+    return y * torch.where(n < 1, torch.ones_like(n), 1 / ((2 - n) * n))
+
+
+# ---- TSDF fusion ----
+
+def _maps(depth, rgb, full_proj):
+    if not isinstance(depth, torch.Tensor) or not isinstance(full_proj, torch.Tensor):
+        raise ValueError("depth and full_proj must be torch tensors")
+    if depth.dim() == 4 and depth.shape[1] == 1:
+        depth = depth[:, 0]
+    if depth.dim() != 3:
+        raise ValueError(f"depth must be [V, H, W] or [V, 1, H, W]; got {tuple(depth.shape)}")
+    V, H, W = depth.shape
+    if V < 1:
+        raise ValueError("no views")
+    if H < 2 or W < 2:
+        raise ValueError(f"the maps must be at least 2 x 2; got {H} x {W}")
+    dev = depth.device
+    depth = depth.to(torch.float32).contiguous()
+    if rgb is not None:
+        if tuple(rgb.shape) != (V, 3, H, W):
+            raise ValueError(f"rgb must be [{V}, 3, {H}, {W}] like depth; got {tuple(rgb.shape)}")
+        rgb = rgb.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(full_proj.shape) not in ((V, 4, 4), (V, 16)):
+        raise ValueError(f"full_proj must be [{V}, 4, 4] or [{V}, 16]; got {tuple(full_proj.shape)}")
+    return depth, rgb, full_proj.to(device=dev, dtype=torch.float32).reshape(V, 16).contiguous()
+
+
+def _bilinear(img, fx, fy, x0, y0):
+    """img [C, H, W] at (fx, fy) with (x0, y0) = floor: grid_sample's four corners in its order; a corner past the last
+    row / column has weight 0 and is not read."""
+    H, W = img.shape[-2:]
+    x1, y1 = x0 + 1, y0 + 1
+    ex, ey, dx, dy = (x0 + 1).to(fx.dtype) - fx, (y0 + 1).to(fx.dtype) - fy, fx - x0.to(fx.dtype), fy - y0.to(fx.dtype)
+    zero = torch.zeros((), dtype=img.dtype)
+
+    def at(x, y):
+        ok = (x < W) & (y < H)
+        return torch.where(ok, img[:, y.clamp(max=H - 1), x.clamp(max=W - 1)], zero)
+    return at(x0, y0) * (ex * ey) + at(x1, y0) * (dx * ey) + at(x0, y1) * (ex * dy) + at(x1, y1) * (dx * dy)
+
+
+def _tsdf_fuse_torch(depth, rgb, full_proj, pts, voxel_size, contracted, center, radius):
+    """scorp_tsdf_fuse's statements on CPU tensors (include/scorp_gs.h), every view over all samples at once."""
+    V, H, W = depth.shape
+    trunc = torch.full((pts.shape[0],), float(np.float32(5.0 * voxel_size)), dtype=torch.float32)
+    if contracted:
+        n = torch.sqrt((pts * pts).sum(-1))
+        trunc = torch.where(n > 1, trunc * (1.0 / (2.0 - n.clamp(max=1.9))), trunc)
+        k = (1.0 / (2.0 - n))[:, None]
+        pts = torch.where((n < 1)[:, None], pts, k * (pts / n[:, None]))
+        pts = pts * float(radius) + center
+    tsdf = torch.ones(pts.shape[0])
+    w = torch.ones(pts.shape[0])
+    col = torch.zeros(pts.shape[0], 3)
+    M = full_proj.reshape(V, 4, 4)
+    for v in range(V):
+        m = M[v]
+        p = [pts[:, 2] * m[2, j] + (pts[:, 1] * m[1, j] + pts[:, 0] * m[0, j]) + m[3, j] for j in (0, 1, 3)]
+        zc = p[2]
+        u, t = p[0] / zc, p[1] / zc
+        inside = (u > -1) & (u < 1) & (t > -1) & (t < 1) & (zc > 0)
+        idx = torch.nonzero(inside)[:, 0]
+        if idx.numel() == 0:
+            continue
+        fx = ((u[idx] + 1) / 2 * (W - 1)).clamp(0, W - 1)
+        fy = ((t[idx] + 1) / 2 * (H - 1)).clamp(0, H - 1)
+        x0, y0 = fx.floor().long(), fy.floor().long()
+        sdf = _bilinear(depth[v][None], fx, fy, x0, y0)[0] - zc[idx]
+        hit = sdf > -trunc[idx]
+        idx, s = idx[hit], (sdf[hit] / trunc[idx[hit]]).clamp(-1.0, 1.0)
+        wp = w[idx] + 1
+        tsdf[idx] = (tsdf[idx] * w[idx] + s) / wp
+        if rgb is not None:
+            c = _bilinear(rgb[v], fx[hit], fy[hit], x0[hit], y0[hit]).T
+            col[idx] = (col[idx] * w[idx][:, None] + c) / wp[:, None]
+        w[idx] = wp
+    return tsdf, (col if rgb is not None else None)
+
+
+def tsdf_fuse(depth, rgb, full_proj, samples, voxel_size, contracted=False, center=None, radius=None):
+    """compute_unbounded_tsdf (mesh_utils.py:209-247) over the views depth [V, H, W] (or [V, 1, H, W]), rgb [V, 3, H, W]
+    or None, full_proj [V, 4, 4] (each camera's full_proj_transform as stored).  `samples` is [M, 3], or a tuple (x, y, z)
+    of 1-D coordinate tensors: the lattice of their product in C order, never materialised on the GPU path.  With
+    `contracted` the samples lie in the contracted space of the sphere (center [3], radius).  Returns the TSDF - [M], or
+    [X, Y, Z] for a lattice - and, when rgb is given, (tsdf, colours [..., 3])."""
+    depth, rgb, full_proj = _maps(depth, rgb, full_proj)
+    dev = depth.device
+    voxel_size = float(voxel_size)
+    if not voxel_size > 0.0:
+        raise ValueError(f"voxel_size must be positive; got {voxel_size}")
+    if contracted:
+        if center is None or radius is None:
+            raise ValueError("contracted samples need center and radius")
+        if not float(radius) > 0.0:
+            raise ValueError(f"radius must be positive; got {radius}")
+        center = torch.as_tensor(center, dtype=torch.float32, device="cpu").reshape(3)
+    lattice = isinstance(samples, (tuple, list))
+    if lattice:
+        if len(samples) != 3 or any(not isinstance(c, torch.Tensor) or c.dim() != 1 or c.numel() < 1 for c in samples):
+            raise ValueError("a lattice is a tuple of three non-empty 1-D coordinate tensors")
+        coords = [c.to(device=dev, dtype=torch.float32).contiguous() for c in samples]
+        shape = tuple(c.numel() for c in coords)
+        M = shape[0] * shape[1] * shape[2]
+        if max(shape) >= 2 ** 31:
+            raise ValueError("a lattice axis has more than 2^31 - 1 points")
+    else:
+        if not isinstance(samples, torch.Tensor) or samples.dim() != 2 or samples.shape[1] != 3:
+            raise ValueError("samples must be [M, 3] or a tuple (x, y, z)")
+        pts = samples.to(device=dev, dtype=torch.float32).contiguous()
+        M, shape = pts.shape[0], (pts.shape[0],)
+    if M < 1:
+        raise ValueError("no samples")
+    V, H, W = depth.shape
+    if not dev.type == "cuda":
+        if lattice:
+            pts = torch.stack(torch.meshgrid(*coords, indexing="ij"), dim=-1).reshape(-1, 3)
+        tsdf, col = _tsdf_fuse_torch(depth, rgb, full_proj, pts, voxel_size, contracted, center, radius)
+    else:
+        L = _C.lib()
+        tsdf = torch.empty(M, dtype=torch.float32, device=dev)
+        col = torch.empty(M, 3, dtype=torch.float32, device=dev) if rgb is not None else None
+        views = _C.ScorpTsdfViews(depth=depth.data_ptr(), rgb=rgb.data_ptr() if rgb is not None else None,
+                                  full_proj=full_proj.data_ptr(), num_views=V, width=W, height=H)
+        params = _C.ScorpTsdfParams(voxel_size=voxel_size, contracted=1 if contracted else 0, radius=float(radius or 0.0))
+        if contracted:
+            params.center[:] = center.tolist()
+        smp = _C.ScorpTsdfSamples()
+        if lattice:
+            smp.x, smp.y, smp.z = (c.data_ptr() for c in coords)
+            smp.nx, smp.ny, smp.nz = shape
+        else:
+            smp.xyz = pts.data_ptr()
+        with torch.cuda.device(dev):
+            stream = _C.current_stream_ptr()
+            for first in range(0, M, LAUNCH_SAMPLES):
+                smp.first, smp.count = first, min(LAUNCH_SAMPLES, M - first)
+                _C.check(L.scorp_tsdf_fuse(ctypes.byref(views), ctypes.byref(smp), ctypes.byref(params), tsdf.data_ptr(),
+                                           col.data_ptr() if col is not None else None, stream), "scorp_tsdf_fuse")
+    tsdf = tsdf.reshape(shape)
+    return (tsdf, col.reshape(*shape, 3)) if rgb is not None else tsdf
+
+
+# ---- surface extraction ----
+
+def _surface_nets_numpy(f, coords, level):
+    """The rules of include/scorp_gs.h (surface extraction) in vectorised numpy float32: the CPU form of extract_surface."""
+    f = np.ascontiguousarray(f, np.float32)
+    X, Y, Z = f.shape
+    level = np.float32(level)
+    inside = f < level
+
+    def corner(a, n):   # the values at corner n (4 di + 2 dj + dk) of every cell
+        di, dj, dk = n >> 2, (n >> 1) & 1, n & 1
+        return a[di:X - 1 + di, dj:Y - 1 + dj, dk:Z - 1 + dk]
+    s = [np.zeros((X - 1, Y - 1, Z - 1), np.float32) for _ in range(3)]
+    cnt = np.zeros((X - 1, Y - 1, Z - 1), np.int32)
+    with np.errstate(all="ignore"):
+        for axis in range(3):
+            step = 4 >> axis
+            for n0 in range(8):
+                if n0 & step:
+                    continue
+                v0, v1 = corner(f, n0), corner(f, n0 + step)
+                cross = corner(inside, n0) != corner(inside, n0 + step)
+                t = (level - v0) / (v1 - v0)
+                fixed = (np.float32(n0 >> 2), np.float32((n0 >> 1) & 1), np.float32(n0 & 1))
+                for d in range(3):
+                    s[d] += np.where(cross, t if d == axis else fixed[d], np.float32(0)).astype(np.float32)
+                cnt += cross
+    active = cnt > 0
+    ids = (np.cumsum(active.ravel(), dtype=np.int64) - 1).reshape(active.shape)
+    ci, cj, ck = np.nonzero(active)
+    n = cnt[active].astype(np.float32)
+    verts = np.empty((ci.size, 3), np.float32)
+    for d, (c, idx) in enumerate(zip(coords, (ci, cj, ck))):
+        c = np.asarray(c, np.float32)
+        verts[:, d] = c[idx] + (s[d][active] / n) * (c[idx + 1] - c[idx])
+    # quads: lattice edges q -> q + e_a, in the order (q, a)
+    E = np.zeros((X, Y, Z, 3), bool)
+    mid = [np.zeros(m, bool) for m in (X, Y, Z)]
+    for m in mid:
+        m[1:-1] = True
+    mi, mj, mk = mid[0][:, None, None], mid[1][None, :, None], mid[2][None, None, :]
+    E[:-1, :, :, 0] = (inside[:-1] != inside[1:]) & (mj & mk)
+    E[:, :-1, :, 1] = (inside[:, :-1] != inside[:, 1:]) & (mk & mi)
+    E[:, :, :-1, 2] = (inside[:, :, :-1] != inside[:, :, 1:]) & (mi & mj)
+    qi, qj, qk, qa = np.nonzero(E)
+    q = np.stack([qi, qj, qk], 1)
+    b = np.eye(3, dtype=np.int64)[(qa + 1) % 3]
+    c = np.eye(3, dtype=np.int64)[(qa + 2) % 3]
+    cell = lambda p: ids[p[:, 0], p[:, 1], p[:, 2]]
+    c00, c10, c11, c01 = cell(q), cell(q - b), cell(q - b - c), cell(q - c)
+    qin = inside[qi, qj, qk]
+    faces = np.stack([c00, np.where(qin, c10, c11), np.where(qin, c11, c10),
+                      c00, np.where(qin, c11, c01), np.where(qin, c01, c11)], 1).reshape(-1, 3).astype(np.int32)
+    return verts, faces
+
+
+def extract_surface(grid, coords, level=0.0):
+    """The surface f = level of the dense grid [X, Y, Z] (inside: f < level) over the lattice coords = (x, y, z) by surface
+    nets: (vertices [Nv, 3] float32, faces [Nf, 3] int32) on the grid's device, in the fixed order of include/scorp_gs.h.
+    The triangles' normals point from inside to outside."""
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+        raise ValueError("grid must be a [X, Y, Z] tensor")
+    if len(coords) != 3 or any(c.dim() != 1 or c.numel() != n for c, n in zip(coords, grid.shape)):
+        raise ValueError("coords must be three 1-D tensors matching the grid's shape")
+    if min(grid.shape) < 2:
+        raise ValueError(f"every grid dimension must be at least 2; got {tuple(grid.shape)}")
+    dev = grid.device
+    f = grid.to(torch.float32).contiguous()
+    xyz = [c.to(device=dev, dtype=torch.float32).contiguous() for c in coords]
+    if dev.type != "cuda":
+        v, t = _surface_nets_numpy(f.numpy(), [c.numpy() for c in xyz], level)
+        return torch.from_numpy(v), torch.from_numpy(t)
+    L = _C.lib()
+    X, Y, Z = f.shape
+    level = float(level)
+    verts = torch.empty(0, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(0, 3, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = _C.current_stream_ptr()
+        flags = torch.empty((X - 1) * (Y - 1) * (Z - 1), dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_isosurface_count_cells(f.data_ptr(), X, Y, Z, level, flags.data_ptr(), stream), "scorp_isosurface_count_cells")
+        cell_scan = torch.cumsum(flags, 0, dtype=torch.int64)
+        nv = int(cell_scan[-1])
+        if nv >= 2 ** 31:
+            raise ValueError("the surface has more than 2^31 - 1 vertices")
+        if nv == 0:
+            return verts, faces
+        cell_scan = cell_scan.to(torch.int32)
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        _C.check(L.scorp_isosurface_emit_vertices(f.data_ptr(), xyz[0].data_ptr(), xyz[1].data_ptr(), xyz[2].data_ptr(), X, Y, Z,
+                                                  level, cell_scan.data_ptr(), nv, verts.data_ptr(), stream),
+                 "scorp_isosurface_emit_vertices")
+        counts = torch.empty(X * Y * Z, dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_isosurface_count_faces(f.data_ptr(), X, Y, Z, level, counts.data_ptr(), stream), "scorp_isosurface_count_faces")
+        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64)
+        nq = int(edge_scan[-1])
+        if nq >= 2 ** 30:
+            raise ValueError("the surface has more than 2^31 - 1 triangles")
+        if nq == 0:
+            return verts, faces
+        edge_scan = edge_scan.to(torch.int32)
+        faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
+        _C.check(L.scorp_isosurface_emit_faces(f.data_ptr(), X, Y, Z, level, cell_scan.data_ptr(), edge_scan.data_ptr(), nq,
+                                               faces.data_ptr(), stream), "scorp_isosurface_emit_faces")
+    return verts, faces
+
+
+# ---- the extractor ----
+
+def focus_point(origins, directions):
+    """The point with the least summed squared distance to the rays (origins [n, 3], directions [n, 3], any length or sign):
+    with the projectors P_i = I - d_i d_i^T onto each ray's normal plane it solves (sum P_i) x = sum P_i o_i.  What the
+    reference's bounding-sphere estimate takes as the scene centre (focus_point_fn, render_utils.py:68-74)."""
+    d = directions / np.linalg.norm(directions, axis=1, keepdims=True)
+    P = np.eye(3)[None] - d[:, :, None] * d[:, None, :]
+    return np.linalg.solve(P.sum(0), np.einsum("nij,nj->i", P, origins))
+
+
+class GaussianExtractor:
+    """mesh_utils.py:72-295 GaussianExtractor on this package's 2DGS render():
+
+        ex = GaussianExtractor(gaussians, render, pipe)
+        ex.reconstruction(cameras)
+        mesh = ex.extract_mesh_unbounded(resolution=1024)
+    """
+
+    def __init__(self, gaussians, render, pipe, bg_color=None):
+        if bg_color is None:
+            bg_color = [0, 0, 0]
+        self.gaussians = gaussians
+        self.device = gaussians.get_xyz.device
+        self.render = partial(render, pipe=pipe, bg_color=torch.tensor(bg_color, dtype=torch.float32, device=self.device))
+        self.clean()
+
+    @torch.no_grad()
+    def clean(self):
+        self.depthmaps = None    # [V, H, W] on the device
+        self.rgbmaps = None      # [V, 3, H, W]
+        self.full_proj = None    # [V, 4, 4]
+        self.viewpoint_stack = []
+
+    @torch.no_grad()
+    def reconstruction(self, viewpoint_stack):
+        """Render every camera and keep its colour and surface-depth maps (the 'render' and 'render_depth' keys)."""
+        self.clean()
+        self.viewpoint_stack = list(viewpoint_stack)
+        if not self.viewpoint_stack:
+            raise ValueError("reconstruction needs at least one camera")
+        depths, rgbs = [], []
+        for cam in self.viewpoint_stack:
+            pkg = self.render(cam, self.gaussians)
+            rgb, depth = pkg["render"], pkg["render_depth"]
+            if depths and depth.shape != depths[0].shape:
+                raise ValueError(f"all views must share one resolution: {tuple(depth.shape)} after {tuple(depths[0].shape)}")
+            rgbs.append(rgb)
+            depths.append(depth)
+        self.depthmaps = torch.stack(depths, 0).reshape(len(depths), *depths[0].shape[-2:]).contiguous()
+        self.rgbmaps = torch.stack(rgbs, 0).contiguous()
+        self.full_proj = torch.stack([cam.full_proj_transform.to(self.device) for cam in self.viewpoint_stack], 0).contiguous()
+        self.estimate_bounding_sphere()
+
+    def estimate_bounding_sphere(self):
+        """centre = the focus point of the cameras' optical axes, radius = the nearest camera's distance to it
+        (mesh_utils.py:124-136).  world_view_transform is stored transposed, so its upper 3x3 holds the camera axes in world
+        coordinates as columns: column 2 is the optical axis."""
+        axes = np.stack([cam.world_view_transform[:3, 2].detach().cpu().numpy() for cam in self.viewpoint_stack]).astype(np.float64)
+        eyes = np.stack([cam.camera_center.detach().cpu().numpy() for cam in self.viewpoint_stack]).astype(np.float64)
+        center = focus_point(eyes, axes)
+        self.radius = float(np.sqrt(((eyes - center) ** 2).sum(1)).min())
+        self.center_host = tuple(float(np.float32(c)) for c in center)   # what the fusion calls take: no device read per call
+        self.center = torch.tensor(self.center_host, dtype=torch.float32, device=self.device)
+
+    def _need_maps(self):
+        if self.depthmaps is None:
+            raise RuntimeError("call reconstruction(viewpoint_stack) first")
+
+    @torch.no_grad()
+    def compute_unbounded_tsdf(self, samples, contracted, voxel_size, return_rgb=False):
+        """mesh_utils.py:209-247 over the kept views; `contracted`: the samples lie in the contracted unit space of the
+        bounding sphere (the reference's inv_contraction is not None).  samples: [M, 3] or a lattice (x, y, z)."""
+        self._need_maps()
+        return tsdf_fuse(self.depthmaps, self.rgbmaps if return_rgb else None, self.full_proj, samples, voxel_size,
+                         contracted=bool(contracted), center=self.center_host, radius=self.radius)
+
+    @torch.no_grad()
+    def tsdf_volume(self, resolution, bounds=None):
+        """(grid [N, N, N], (x, y, z)): the TSDF over the lattice linspace(-R, R, N)^3 of the contracted space, one dense
+        grid.  R defaults to the reference's bound (mesh_utils.py:259-261): the 0.95 quantile of the contracted surfel
+        radii plus 0.01, at most 1.9."""
+        self._need_maps()
+        N = int(resolution)
+        if N < 2:
+            raise ValueError(f"resolution must be at least 2; got {resolution}")
+        if bounds is None:
+            n = torch.linalg.vector_norm((self.gaussians.get_xyz.detach() - self.center) / self.radius, dim=-1)
+            contracted_n = torch.where(n < 1, n, 2 - 1 / n)   # the norm of the contracted point
+            R = min(float(np.quantile(contracted_n.cpu().numpy(), 0.95)) + 0.01, 1.9)
+            lo, hi = (-R, -R, -R), (R, R, R)
+        else:
+            lo, hi = bounds
+        coords = tuple(torch.linspace(float(a), float(b), N).to(self.device) for a, b in zip(lo, hi))
+        voxel_size = self.radius * 2 / N
+        return self.compute_unbounded_tsdf(coords, True, voxel_size), coords
+
+    @torch.no_grad()
+    def extract_mesh_unbounded(self, resolution=1024):
+        """mesh_utils.py:182-278: the TSDF volume of the contracted space, its zero surface, the vertices un-contracted and
+        clipped to +-32, coloured by a second fusion pass over the vertices."""
+        grid, coords = self.tsdf_volume(resolution)
+        verts, faces = extract_surface(grid, coords, level=0.0)
+        voxel_size = self.radius * 2 / int(resolution)
+        if verts.shape[0] == 0:
+            return Mesh(verts, faces, torch.empty(0, 3, dtype=torch.float32, device=verts.device))
+        verts = (uncontract(verts) * float(self.radius) + self.center).clamp(-MAX_RANGE, MAX_RANGE)
+        _, colors = self.compute_unbounded_tsdf(verts, False, voxel_size, return_rgb=True)
+        return Mesh(verts, faces, colors)
+
+    @torch.no_grad()
+    def export_image(self, path):
+        """mesh_utils.py:280-294: renders/NNNNN.png, vis/depth_NNNNN.tiff and (where the camera has one) gt/NNNNN.png."""
+        from PIL import Image
+        self._need_maps()
+        dirs = {k: os.path.join(path, k) for k in ("renders", "gt", "vis")}
+        for d in dirs.values():
+            os.makedirs(d, exist_ok=True)
+        u8 = lambda img: Image.fromarray((np.clip(np.nan_to_num(img.permute(1, 2, 0).cpu().numpy()), 0.0, 1.0) * 255).astype(np.uint8))
+        for idx, cam in enumerate(self.viewpoint_stack):
+            gt = getattr(cam, "original_image", None)
+            if gt is not None:
+                u8(gt[0:3]).save(os.path.join(dirs["gt"], f"{idx:05d}.png"))
+            u8(self.rgbmaps[idx]).save(os.path.join(dirs["renders"], f"{idx:05d}.png"))
+            Image.fromarray(self.depthmaps[idx].cpu().numpy().astype(np.float32)).save(os.path.join(dirs["vis"], f"depth_{idx:05d}.tiff"))

@@ -104,3 +104,48 @@ def read_gaussian_ply(path, max_sh_degree=None):
     return dict(xyz=xyz, features_dc=np.ascontiguousarray(dc.transpose(0, 2, 1)),
                 features_rest=np.ascontiguousarray(rest.transpose(0, 2, 1)), opacity=col("opacity").reshape(n, 1),
                 scaling=scaling, rotation=rotation)
+
+
+def write_mesh_ply(path, mesh):
+    """A triangle mesh (scorp_amd.mesh.Mesh, or anything with vertices [Nv,3], faces [Nf,3] and colors [Nv,3] in [0,1])
+    as binary little-endian PLY: element vertex with float x y z and uchar red green blue, element face with
+    `list uchar int vertex_indices` - the layout Open3D and MeshLab write for a coloured mesh."""
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    verts, faces, colors = host(mesh.vertices), host(mesh.faces), host(mesh.colors)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    v = np.empty(len(verts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    for k, nm in enumerate(("x", "y", "z")):
+        v[nm] = verts[:, k]
+    rgb8 = np.rint(np.clip(np.nan_to_num(colors.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
+    for k, nm in enumerate(("red", "green", "blue")):
+        v[nm] = rgb8[:, k]
+    f = np.empty(len(faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    f["n"] = 3
+    f["i"] = faces
+    header = ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {len(verts)}\n" +
+              "property float x\nproperty float y\nproperty float z\n" +
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n" +
+              f"element face {len(faces)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+
+
+def read_mesh_ply(path):
+    """(vertices [Nv,3] float32, faces [Nf,3] int32, colors [Nv,3] uint8) of a file written by write_mesh_ply."""
+    v = read_ply_vertices(path)
+    with open(path, "rb") as fh:
+        data = fh.read()
+    head_end = data.index(b"end_header\n") + len(b"end_header\n")
+    nf = [int(l.split()[2]) for l in data[:head_end].decode("ascii").splitlines() if l.startswith("element face")]
+    if not nf:
+        raise ValueError(f"{path}: no face element")
+    f = np.frombuffer(data, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=nf[0], offset=head_end + v.nbytes)
+    if nf[0] and not np.all(f["n"] == 3):
+        raise ValueError(f"{path}: only triangles are supported")
+    verts = np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float32)
+    colors = np.stack([v["red"], v["green"], v["blue"]], 1)
+    return verts, np.ascontiguousarray(f["i"]).astype(np.int32), colors
