@@ -26,7 +26,9 @@ constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 
 struct Window { float w[11]; };
 
-// Window exactly as the reference builds it (loss_utils.py:23-26): python-double exp rounded to fp32, fp32 sum.
+// Window as the reference builds it (loss_utils.py:23-26): python-double exp rounded to fp32, fp32 sum.  The sum is taken
+// one tap after the other here and ends 1 ulp below torch's g.sum() (3.7592325 against 3.7592328), so nine of the eleven
+// taps are 1 ulp above the reference's: 3e-7 .. 6e-7 of max |grad| (tests/test_loss_cpu.py).
 Window make_window() {
   Window win;
   float s = 0.0f;
@@ -43,6 +45,30 @@ __device__ __forceinline__ float block_sum_256(float v, float *s_red) {
   if ((threadIdx.x & 63) == 0) s_red[wave] = v;
   __syncthreads();
   return s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+
+// One pixel's SSIM and d ssim / d{mu1, E[x^2], E[xy]} from its four windowed moments.  Every operation is rounded on its
+// own, in the order written (no contraction: tests/loss_reference.py::kernel_order_values restates it in numpy), and each
+// hardware reciprocal gets one Newton step: v_rcp_f32 alone is 1 ulp and errs to one side, which left the mean SSIM of a
+// small image 1 to 2 ulps (6e-8 .. 1.4e-7) low - many ulps of the loss 1 - SSIM.  B1 >= C1, B2 >= ~C2 > 0.
+struct SsimPixel { float ssim, d_mu1, d_ex2, d_exy; };
+__device__ __forceinline__ float rcp_refined(float b) {
+  const float r = __builtin_amdgcn_rcpf(b);
+  return __builtin_fmaf(__builtin_fmaf(-b, r, 1.0f), r, r);
+}
+__device__ __forceinline__ SsimPixel ssim_pixel(float m1, float m2, float ess, float e12, float c1, float c2) {
+#pragma clang fp contract(off)
+  const float m1s = m1 * m1, m2s = m2 * m2, m12 = m1 * m2;
+  const float s12 = e12 - m12;
+  const float A1 = 2 * m12 + c1, A2 = 2 * s12 + c2, B1 = m1s + m2s + c1, B2 = (ess - m1s - m2s) + c2;
+  const float rB2 = rcp_refined(B2);
+  const float inv = rcp_refined(B1) * rB2;
+  SsimPixel p;
+  p.ssim = A1 * A2 * inv;
+  p.d_mu1 = (2 * m2 * (A2 - A1) - 2 * m1 * p.ssim * (B2 - B1)) * inv;
+  p.d_ex2 = -p.ssim * rB2;
+  p.d_exy = 2 * A1 * inv;
+  return p;
 }
 
 // Workgroup -> (channel, tile) with XCD locality: the hardware deals consecutive workgroup ids round-robin to the 8
@@ -150,22 +176,16 @@ ssim_l1_forward_strip_kernel(const float *__restrict__ img, const float *__restr
     if (__ballot(any) == 0) {
       float c1 = kC1, c2 = kC2, zero = 0.0f;
       asm volatile("" : "+v"(c1), "+v"(c2), "+v"(zero));
-      const float m1 = zero, m2 = zero, ess = zero, e12 = zero;
-      const float m1s = m1 * m1, m2s = m2 * m2, m12 = m1 * m2;
-      const float s12 = e12 - m12;
-      const float A1 = 2 * m12 + c1, A2 = 2 * s12 + c2, B1 = m1s + m2s + c1, B2 = (ess - m1s - m2s) + c2;
-      const float rB2 = __builtin_amdgcn_rcpf(B2);
-      const float inv = __builtin_amdgcn_rcpf(B1) * rB2;
-      const float ssim = A1 * A2 * inv;
+      const SsimPixel px = ssim_pixel(zero, zero, zero, zero, c1, c2);
       float ssim_sum = 0.0f;
       for (int ro = ry0; ro < min(ry0 + kStripRows, H); ro++) {
         if (gx < W) {
-          ssim_sum += ssim;
+          ssim_sum += px.ssim;
           if (dmaps) {
             float *d0 = dmaps + ch * HW + (size_t)ro * W;
-            d0[(uint32_t)gx] = (2 * m2 * (A2 - A1) - 2 * m1 * ssim * (B2 - B1)) * inv;
-            (d0 + CHW)[(uint32_t)gx] = -ssim * rB2;
-            (d0 + 2 * CHW)[(uint32_t)gx] = 2 * A1 * inv;
+            d0[(uint32_t)gx] = px.d_mu1;
+            (d0 + CHW)[(uint32_t)gx] = px.d_ex2;
+            (d0 + 2 * CHW)[(uint32_t)gx] = px.d_exy;
           }
         }
       }
@@ -196,11 +216,11 @@ ssim_l1_forward_strip_kernel(const float *__restrict__ img, const float *__restr
       {
         const float m = (rin && cin_a) ? cur.ma : 0.0f;
         const float xv = cur.xa * m, yv = cur.ya * m;
-        buf4[lane] = make_float4(xv, yv, xv * xv + yv * yv, xv * yv);
+        buf4[lane] = make_float4(xv, yv, __builtin_fmaf(yv, yv, xv * xv), xv * yv);
         if (lane < 2 * kLH) {
           const float m2 = (rin && cin_b) ? cur.mb : 0.0f;
           const float x2 = cur.xb * m2, y2 = cur.yb * m2;
-          buf4[64 + lane] = make_float4(x2, y2, x2 * x2 + y2 * y2, x2 * y2);
+          buf4[64 + lane] = make_float4(x2, y2, __builtin_fmaf(y2, y2, x2 * x2), x2 * y2);
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -227,21 +247,15 @@ ssim_l1_forward_strip_kernel(const float *__restrict__ img, const float *__restr
           m1 += w * hist[0][sl]; m2 += w * hist[1][sl]; ess += w * hist[2][sl]; e12 += w * hist[3][sl];
         }
         if (gx < W) {
-          const float m1s = m1 * m1, m2s = m2 * m2, m12 = m1 * m2;
-          const float s12 = e12 - m12;
-          const float A1 = 2 * m12 + kC1, A2 = 2 * s12 + kC2, B1 = m1s + m2s + kC1, B2 = (ess - m1s - m2s) + kC2;
-          // B1 >= C1, B2 >= ~C2 > 0: hardware reciprocals (1 ulp) instead of two IEEE division sequences
-          const float rB2 = __builtin_amdgcn_rcpf(B2);
-          const float inv = __builtin_amdgcn_rcpf(B1) * rB2;
-          const float ssim = A1 * A2 * inv;
-          ssim_sum += ssim;
+          const SsimPixel px = ssim_pixel(m1, m2, ess, e12, kC1, kC2);
+          ssim_sum += px.ssim;
           const int sc = (u + 11 - kLH) % 11;               // the centre row's x, y
           l1_sum += fabsf(cx[sc] - cy[sc]);
           if (dmaps) {
             float *d0 = dmaps + ch * HW + (size_t)ro * W;    // uniform row base + lane offset
-            d0[(uint32_t)gx] = (2 * m2 * (A2 - A1) - 2 * m1 * ssim * (B2 - B1)) * inv;  // d ssim / d mu1
-            (d0 + CHW)[(uint32_t)gx] = -ssim * rB2;                                      // d ssim / d E[x^2]
-            (d0 + 2 * CHW)[(uint32_t)gx] = 2 * A1 * inv;                                  // d ssim / d E[xy]
+            d0[(uint32_t)gx] = px.d_mu1;             // d ssim / d mu1
+            (d0 + CHW)[(uint32_t)gx] = px.d_ex2;     // d ssim / d E[x^2]
+            (d0 + 2 * CHW)[(uint32_t)gx] = px.d_exy; // d ssim / d E[xy]
           }
         }
       }
