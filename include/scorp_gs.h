@@ -352,6 +352,36 @@ int scorp_isosurface_count_faces(const float *f, int32_t nx, int32_t ny, int32_t
 int scorp_isosurface_emit_faces(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, const int32_t *cell_scan,
                                 const int32_t *edge_scan, int64_t num_quads, int32_t *out_faces, scorp_stream_t stream);
 
+/* ---- connected triangles of a mesh (Open3D's cluster_connected_triangles, as gs2dgs/utils/mesh_utils.py:30 calls it) ----
+ * faces[num_faces, 3] int32 vertex indices, each in [0, 2^31 - 1].  Two triangles are ADJACENT when they share an edge, an
+ * edge being the unordered pair of vertex INDICES: positions do not count, and two triangles that touch at one vertex are
+ * not adjacent.  An edge may carry any number of triangles (surface nets give edges with 4).  A degenerate triangle
+ * contributes its three edges like any other, (v, v) included; there is no special case.  A cluster is a connected
+ * component of that adjacency.  Clusters are numbered in ascending order of the smallest triangle index they contain (the
+ * order in which a search over the triangles in index order opens them); cluster_n_triangles[c] is the triangle count of
+ * cluster c, cluster_area[c] the sum of its triangles' areas 0.5 |(v1 - v0) x (v2 - v0)|, in float64 from the float32 vertices.
+ * Lock-free union-find over the triangles with the edges matched through an open-addressing hash table; a root is only
+ * hooked under a smaller index, so the integer outputs do not depend on the execution order.  The caller owns every buffer
+ * and the scan between the last two calls:
+ *   link:  keys[num_slots] (uint64), owner[num_slots] (int32) and parent[num_faces] (int32) are scratch the call fills
+ *          itself, the caller pre-fills nothing; num_slots is a power of two >= 6 num_faces (3 num_faces insertions: load
+ *          <= 0.5) and <= 2^32.  A key is min(a, b) << 32 | max(a, b).
+ *   roots: out_root[t] = the smallest triangle index of t's cluster, out_is_root[t] = (out_root[t] == t) as one byte.
+ *   stats: root_scan[num_faces] = the INCLUSIVE int32 prefix sum of the bytes, num_clusters its last entry;
+ *          out_cluster[t] = root_scan[root[t]] - 1, out_count[num_clusters] and - unless out_area or vertices is NULL -
+ *          out_area[num_clusters] (float64), both zeroed by the call.  A vertex index outside [0, num_vertices) is not read
+ *          and its triangle adds area 0.  The counts are exact.  The areas are float64 sums by atomic adds: they depend on
+ *          the order of arrival in their last bits (within num_faces 2^-52 of the summed area), two calls need not agree there.
+ * None synchronises.  SCORP_ERR_INVALID: a NULL pointer (other than out_area / vertices), num_faces < 1 or > 2^28,
+ * num_slots not a power of two, < 6 num_faces or > 2^32, num_clusters outside [1, num_faces]. */
+int scorp_mesh_cluster_link(const int32_t *faces, int64_t num_faces, uint64_t *keys, int32_t *owner, uint64_t num_slots,
+                            int32_t *parent, scorp_stream_t stream);
+int scorp_mesh_cluster_roots(const int32_t *parent, int64_t num_faces, int32_t *out_root, uint8_t *out_is_root,
+                             scorp_stream_t stream);
+int scorp_mesh_cluster_stats(const int32_t *faces, const float *vertices, int64_t num_vertices, const int32_t *root,
+                             const int32_t *root_scan, int64_t num_faces, int64_t num_clusters, int32_t *out_cluster,
+                             int32_t *out_count, double *out_area, scorp_stream_t stream);
+
 /* ---- introspection for stage-level parity tests (device->host copies; synchronises) ---- */
 /* xy[N,2], depth[N], conic_opacity[N,4], rgb[N,3], rect[N,4] (tile units, max exclusive); any may be NULL. */
 int scorp_gs3d_debug_geom(const void *state, int32_t num_gaussians, int32_t image_width, int32_t image_height,

@@ -122,6 +122,7 @@ EXPORTS = [
     "scorp_pose_fit_workspace_bytes", "scorp_pose_ransac", "scorp_pose_adam_9dof",
     "scorp_tsdf_fuse", "scorp_isosurface_count_cells", "scorp_isosurface_emit_vertices", "scorp_isosurface_count_faces",
     "scorp_isosurface_emit_faces",
+    "scorp_mesh_cluster_link", "scorp_mesh_cluster_roots", "scorp_mesh_cluster_stats",
 ]
 
 BACKWARD_EXACT_FP32 = 1   # scorp_gs3d_backward_ex flag (include/scorp_gs.h)
@@ -238,6 +239,9 @@ def lib():
     L.scorp_isosurface_emit_vertices.argtypes = [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, i64, vp, vp]
     L.scorp_isosurface_count_faces.argtypes = [vp, i32, i32, i32, ctypes.c_float, vp, vp]
     L.scorp_isosurface_emit_faces.argtypes = [vp, i32, i32, i32, ctypes.c_float, vp, vp, i64, vp, vp]
+    L.scorp_mesh_cluster_link.argtypes = [vp, i64, vp, vp, u64, vp, vp]
+    L.scorp_mesh_cluster_roots.argtypes = [vp, i64, vp, vp, vp]
+    L.scorp_mesh_cluster_stats.argtypes = [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp]
     L.scorp_prof_enable.argtypes = [ctypes.c_int]
     L.scorp_prof_select.argtypes = [u64]
     L.scorp_prof_kernel_name.restype = ctypes.c_char_p

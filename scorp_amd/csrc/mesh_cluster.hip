@@ -1,0 +1,249 @@
+// mesh_cluster.hip — connected components of a triangle mesh over shared EDGES (Open3D's cluster_connected_triangles, what
+// gs2dgs/utils/mesh_utils.py:22-43 post_process_mesh calls): lock-free union-find over the triangles, the triangles of an
+// edge found through an open-addressing hash table.  The rules (adjacency, cluster numbering, counts, areas) are in
+// include/scorp_gs.h; tests/mesh_cluster_reference.py restates them as a breadth-first search in plain Python.
+//
+// Three calls with the caller's scan between the last two, as in isosurface.hip:
+//   link   fills the table and the parent array itself, then every triangle inserts its three edge keys.  A slot is claimed
+//          by ONE 64-bit compare-and-swap on the key; the triangle then takes old = atomicMin(&owner[slot], tri) and, when the
+//          slot had an owner, unites itself with it.  The owner is never stored by a separate plain write: the value an
+//          arrival gets back is always an earlier arrival of the same edge (or nothing), so the atomicMin returns chain all
+//          triangles of an edge together, however many there are.
+//   roots  root[t] = find(t) and one byte root[t] == t; the inclusive scan of the bytes numbers the clusters.
+//   stats  cluster[t] = scan[root[t]] - 1, triangle counts and float64 areas per cluster.  One component is usually almost
+//          the whole mesh: the lanes of a wave that hold the same cluster combine first, and a wave issues one atomic per
+//          distinct cluster it holds.  The counts are exact; the float64 area sums depend on the order in which the
+//          waves' atomic adds arrive, in their last bits.
+// A root is only ever hooked under a SMALLER index, so the root of a finished component is its smallest triangle: labels
+// and numbering do not depend on the execution order, two calls give the same integers.  Nothing waits on another lane's
+// progress: no locks, no spinning on a value someone else must write.
+#include "common.hpp"
+
+namespace scorp {
+namespace {
+
+constexpr int kClusterThreads = 256;
+constexpr int64_t kClusterMaxFaces = (int64_t)1 << 28;
+constexpr uint64_t kEmptyKey = ~(uint64_t)0;     // no edge has it: vertex indices are non-negative int32
+constexpr int32_t kEmptyOwner = 0x7FFFFFFF;      // above every triangle index (num_faces <= 2^28)
+
+// parent[] while other lanes hook roots: an agent-scope relaxed atomic load.  A plain load may be served from a line of the
+// CU's vector cache that another CU's compare-and-swap has rewritten since, for as long as the loop runs.  (A stale value
+// would still be a former parent - the index itself - and the compare-and-swap in unite() is what decides; the fresh load
+// saves the retries.)
+__device__ __forceinline__ int32_t load_parent(const int32_t *parent, int32_t x) {
+  return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The root above x, halving the path on the way.  The only write is atomicMin(&parent[x], grandparent): parent[x] goes
+// down to another ancestor of x and can never rise, so it cannot undo a hook that lands at the same time (a plain store of
+// the grandparent could: it might overwrite the smaller parent a concurrent hook has just given x).  A root has
+// parent[x] == x and is not written here.
+__device__ __forceinline__ int32_t find_root(int32_t *parent, int32_t x) {
+  int32_t p = load_parent(parent, x);
+  while (p != x) {
+    const int32_t g = load_parent(parent, p);
+    if (g != p) atomicMin(parent + x, g);
+    x = p;
+    p = g;
+  }
+  return x;
+}
+
+// Joins the trees of a and b.  Terminates: parent[hi] == hi holds only while hi is a root, and parent[x] <= x always.  A
+// failed compare-and-swap returns the parent hi has by now, old < hi, and the loop goes on from (old, lo): every retry
+// replaces one of the two indices by a strictly smaller one, and indices are bounded below by 0.  The walk inside find_root
+// descends strictly as well.  No step depends on what another lane does next.
+__device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b) {
+  for (;;) {
+    a = find_root(parent, a);
+    b = find_root(parent, b);
+    if (a == b) return;
+    const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+    const int32_t old = atomicCAS(parent + hi, hi, lo);
+    if (old == hi) return;
+    a = old;
+    b = lo;
+  }
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t k) {   // (the 64-bit finaliser of MurmurHash3: both halves of the key reach the low bits)
+  k ^= k >> 33;
+  k *= 0xFF51AFD7ED558CCDull;
+  k ^= k >> 33;
+  k *= 0xC4CEB9FE1A85EC53ull;
+  k ^= k >> 33;
+  return k;
+}
+
+__global__ void __launch_bounds__(kClusterThreads) cluster_init_kernel(uint64_t *__restrict__ keys, int32_t *__restrict__ owner,
+                                                                       uint64_t slots, int32_t *__restrict__ parent, int32_t faces) {
+  const uint64_t i = (uint64_t)blockIdx.x * kClusterThreads + threadIdx.x;
+  if (i < slots) {
+    keys[i] = kEmptyKey;
+    owner[i] = kEmptyOwner;
+  }
+  if (i < (uint64_t)faces) parent[i] = (int32_t)i;
+}
+
+__global__ void __launch_bounds__(kClusterThreads) cluster_link_kernel(const int32_t *__restrict__ tri_idx, int32_t faces,
+                                                                       uint64_t *keys, int32_t *owner, uint64_t slot_mask,
+                                                                       int32_t *parent) {
+  const int64_t t64 = (int64_t)blockIdx.x * kClusterThreads + threadIdx.x;
+  if (t64 >= faces) return;
+  const int32_t t = (int32_t)t64;
+  const uint32_t v[3] = {(uint32_t)tri_idx[3 * t64], (uint32_t)tri_idx[3 * t64 + 1], (uint32_t)tri_idx[3 * t64 + 2]};
+#pragma unroll
+  for (int e = 0; e < 3; e++) {
+    const uint32_t a = v[e], b = v[e == 2 ? 0 : e + 1];
+    const uint64_t key = (uint64_t)(a < b ? a : b) << 32 | (uint64_t)(a < b ? b : a);
+    if (key == kEmptyKey) continue;   // (two indices of -1: not a mesh; the empty marker is never claimed as an edge)
+    uint64_t slot = mix64(key) & slot_mask;
+    // linear probing, bounded by the table's size: with num_slots >= 6 num_faces at most half the slots are ever taken
+    for (uint64_t probe = 0; probe <= slot_mask; probe++) {
+      const uint64_t prev = atomicCAS((unsigned long long *)(keys + slot), (unsigned long long)kEmptyKey, (unsigned long long)key);
+      if (prev == kEmptyKey || prev == key) {
+        const int32_t old = atomicMin(owner + slot, t);
+        if (old != kEmptyOwner) unite(parent, t, old);
+        break;
+      }
+      slot = (slot + 1) & slot_mask;
+    }
+  }
+}
+
+// (after the link launch has ended: plain loads)
+__global__ void __launch_bounds__(kClusterThreads) cluster_roots_kernel(const int32_t *__restrict__ parent, int32_t faces,
+                                                                        int32_t *__restrict__ out_root,
+                                                                        uint8_t *__restrict__ out_is_root) {
+  const int64_t t = (int64_t)blockIdx.x * kClusterThreads + threadIdx.x;
+  if (t >= faces) return;
+  int32_t x = (int32_t)t, p = parent[x];
+  // (p < x while x is not a root, and an entry outside [0, x] - an array the link call did not fill - ends the walk)
+  while (p != x && p >= 0 && p < x) {
+    x = p;
+    p = parent[x];
+  }
+  out_root[t] = x;
+  out_is_root[t] = x == (int32_t)t;
+}
+
+// the sum of v over all 64 lanes, in every lane (a fixed butterfly: the same lanes give the same bits)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+  return v;
+}
+
+__global__ void __launch_bounds__(kClusterThreads) cluster_stats_kernel(const int32_t *__restrict__ tri_idx,
+                                                                        const float *__restrict__ verts, int64_t num_vertices,
+                                                                        const int32_t *__restrict__ root,
+                                                                        const int32_t *__restrict__ root_scan, int32_t faces,
+                                                                        int32_t clusters, int32_t *__restrict__ out_cluster,
+                                                                        int32_t *out_count, double *out_area) {
+#pragma clang fp contract(off)   // every product and sum of the area rounded on its own, as the float64 restatements round
+  const bool with_area = out_area != nullptr;   // (uniform: a kernel argument)
+  const int64_t t = (int64_t)blockIdx.x * kClusterThreads + threadIdx.x;
+  int32_t c = -1;
+  double area = 0.0;
+  if (t < faces) {
+    const int32_t r = root[t];
+    if (r >= 0 && r < faces) c = root_scan[r] - 1;
+    out_cluster[t] = c;
+    if (c < 0 || c >= clusters) c = -1;   // (a scan that does not belong to these roots adds nothing out of bounds)
+    if (with_area && c >= 0) {
+      const int64_t i0 = tri_idx[3 * t], i1 = tri_idx[3 * t + 1], i2 = tri_idx[3 * t + 2];
+      if (i0 >= 0 && i0 < num_vertices && i1 >= 0 && i1 < num_vertices && i2 >= 0 && i2 < num_vertices) {
+        const double ax = verts[3 * i0], ay = verts[3 * i0 + 1], az = verts[3 * i0 + 2];
+        const double ux = (double)verts[3 * i1] - ax, uy = (double)verts[3 * i1 + 1] - ay, uz = (double)verts[3 * i1 + 2] - az;
+        const double wx = (double)verts[3 * i2] - ax, wy = (double)verts[3 * i2 + 1] - ay, wz = (double)verts[3 * i2 + 2] - az;
+        const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+        area = 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
+      }
+    }
+  }
+  // Lanes of the wave that hold the same cluster combine, and the first of them issues the atomics: one per distinct
+  // cluster in the wave instead of 64 on one address.  The loop is wave-uniform (every lane runs every round, the lanes past
+  // the last triangle with c = -1), so the ballots and the butterfly see all 64 lanes.
+  const int lane = threadIdx.x & 63;
+  uint64_t todo = __ballot(c >= 0);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const int32_t lc = __shfl(c, leader);
+    const bool mine = c == lc;
+    const uint64_t same = __ballot(mine);
+    double s = 0.0;
+    if (with_area) s = wave_sum(mine ? area : 0.0);
+    if (lane == leader) {
+      atomicAdd(out_count + lc, (int32_t)__builtin_popcountll(same));
+      if (with_area) atomicAdd(out_area + lc, s);
+    }
+    todo &= ~same;
+  }
+}
+
+inline unsigned cluster_blocks(uint64_t n) { return (unsigned)((n + kClusterThreads - 1) / kClusterThreads); }
+
+int check_faces(int64_t num_faces, const char *what) {
+  if (num_faces < 1 || num_faces > kClusterMaxFaces) {
+    set_error("%s: num_faces must be in [1, 2^28]", what); return SCORP_ERR_INVALID;
+  }
+  return SCORP_OK;
+}
+
+}  // namespace
+}  // namespace scorp
+
+using namespace scorp;
+
+extern "C" int scorp_mesh_cluster_link(const int32_t *faces, int64_t num_faces, uint64_t *keys, int32_t *owner, uint64_t num_slots,
+                                       int32_t *parent, scorp_stream_t stream) {
+  if (!faces || !keys || !owner || !parent) { set_error("mesh_cluster_link: NULL argument"); return SCORP_ERR_INVALID; }
+  if (int e = check_faces(num_faces, "mesh_cluster_link")) return e;
+  if (num_slots == 0 || (num_slots & (num_slots - 1)) != 0) {
+    set_error("mesh_cluster_link: num_slots must be a power of two"); return SCORP_ERR_INVALID;
+  }
+  if (num_slots < 6 * (uint64_t)num_faces) {
+    set_error("mesh_cluster_link: num_slots must be at least 6 num_faces (%llu < %llu)", (unsigned long long)num_slots,
+              (unsigned long long)(6 * (uint64_t)num_faces));
+    return SCORP_ERR_INVALID;
+  }
+  if (num_slots > ((uint64_t)1 << 32)) { set_error("mesh_cluster_link: num_slots above 2^32"); return SCORP_ERR_INVALID; }
+  hipStream_t s = (hipStream_t)stream;
+  cluster_init_kernel<<<cluster_blocks(num_slots), kClusterThreads, 0, s>>>(keys, owner, num_slots, parent, (int32_t)num_faces);
+  SCORP_KERNEL_CHECK("cluster_init", 0, s);
+  cluster_link_kernel<<<cluster_blocks((uint64_t)num_faces), kClusterThreads, 0, s>>>(faces, (int32_t)num_faces, keys, owner,
+                                                                                     num_slots - 1, parent);
+  SCORP_KERNEL_CHECK("cluster_link", 0, s);
+  return SCORP_OK;
+}
+
+extern "C" int scorp_mesh_cluster_roots(const int32_t *parent, int64_t num_faces, int32_t *out_root, uint8_t *out_is_root,
+                                        scorp_stream_t stream) {
+  if (!parent || !out_root || !out_is_root) { set_error("mesh_cluster_roots: NULL argument"); return SCORP_ERR_INVALID; }
+  if (int e = check_faces(num_faces, "mesh_cluster_roots")) return e;
+  hipStream_t s = (hipStream_t)stream;
+  cluster_roots_kernel<<<cluster_blocks((uint64_t)num_faces), kClusterThreads, 0, s>>>(parent, (int32_t)num_faces, out_root, out_is_root);
+  SCORP_KERNEL_CHECK("cluster_roots", 0, s);
+  return SCORP_OK;
+}
+
+extern "C" int scorp_mesh_cluster_stats(const int32_t *faces, const float *vertices, int64_t num_vertices, const int32_t *root,
+                                        const int32_t *root_scan, int64_t num_faces, int64_t num_clusters, int32_t *out_cluster,
+                                        int32_t *out_count, double *out_area, scorp_stream_t stream) {
+  if (!faces || !root || !root_scan || !out_cluster || !out_count) { set_error("mesh_cluster_stats: NULL argument"); return SCORP_ERR_INVALID; }
+  if (int e = check_faces(num_faces, "mesh_cluster_stats")) return e;
+  if (num_clusters < 1 || num_clusters > num_faces) {
+    set_error("mesh_cluster_stats: num_clusters must be in [1, num_faces]"); return SCORP_ERR_INVALID;
+  }
+  const bool area = out_area && vertices;
+  if (area && num_vertices < 0) { set_error("mesh_cluster_stats: num_vertices < 0"); return SCORP_ERR_INVALID; }
+  hipStream_t s = (hipStream_t)stream;
+  SCORP_HIP_CHECK(hipMemsetAsync(out_count, 0, (size_t)num_clusters * sizeof(int32_t), s));
+  if (area) SCORP_HIP_CHECK(hipMemsetAsync(out_area, 0, (size_t)num_clusters * sizeof(double), s));
+  cluster_stats_kernel<<<cluster_blocks((uint64_t)num_faces), kClusterThreads, 0, s>>>(
+      faces, area ? vertices : nullptr, area ? num_vertices : 0, root, root_scan, (int32_t)num_faces, (int32_t)num_clusters, out_cluster,
+      out_count, area ? out_area : nullptr);
+  SCORP_KERNEL_CHECK("cluster_stats", 0, s);
+  return SCORP_OK;
+}
