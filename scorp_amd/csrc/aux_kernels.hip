@@ -148,8 +148,9 @@ namespace {
 //   rotation <- q (x) normalize(rotation)            (Hamilton product, q = the quaternion of R)
 //   scaling  <- scaling + log(s)                     (log-space scales; `dims` of them: 3, or 2 for surfels)
 //   rest[l]  <- D_l rest[l]  for the SH bands l = 1..3 present (real Wigner-D blocks, row-major 3x3, 5x5, 7x7), per channel
-// instead of ~20 elementwise / einsum torch launches over the model.  params (device, 113 floats):
-//   R[9] c[3] t[3] s[3] q[4] D1[9] D2[25] D3[49] | flags[8] (floats: 1 = rotate SH).
+// instead of ~20 elementwise / einsum torch launches over the model.  params (device, 105 floats, 16-byte aligned: the
+// struct below is all the kernel reads; a band is rotated when k_rest holds all of it and `rest` is given):
+//   R[9] c[3] t[3] s[3] q[4] D1[9] D2[25] D3[49].
 struct TransformParams { float R[9], c[3], t[3], s[3], q[4], D1[9], D2[25], D3[49]; };
 __global__ void __launch_bounds__(256)
 transform_gaussians_kernel(int N, int k_rest, int dims, float *__restrict__ xyz, float *__restrict__ rot, float *__restrict__ scaling,

@@ -86,7 +86,8 @@ def gaussians_transform(g, R=None, T=None, scale=None, fix_center=False, blocks=
         D[l] = torch.as_tensor(B).double().cpu()
     q = matrix_to_quat(Rh).double() if R is not None else torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float64)
     flat = torch.cat([Rh.reshape(-1), torch.zeros(3, dtype=torch.float64), Th, Sh[:3], q, D[0].reshape(-1), D[1].reshape(-1),
-                      D[2].reshape(-1), torch.zeros(3, dtype=torch.float64)]).float()     # 113 floats + padding to 116
+                      D[2].reshape(-1), torch.zeros(3, dtype=torch.float64)]).float()     # the 105 floats the kernel reads
+    #                                                                 (R 9, c 3, t 3, s 3, q 4, D1 9, D2 25, D3 49) + 3 of padding: 108
     params = flat.to(dev)
     if fix_center:
         params[9:12] = g._xyz.data.mean(0)
