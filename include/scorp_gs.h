@@ -382,6 +382,84 @@ int scorp_mesh_cluster_stats(const int32_t *faces, const float *vertices, int64_
                              const int32_t *root_scan, int64_t num_faces, int64_t num_clusters, int32_t *out_cluster,
                              int32_t *out_count, double *out_area, scorp_stream_t stream);
 
+/* ---- bounded TSDF volume: sparse 16^3-voxel blocks, fused and meshed (the route of gs2dgs/utils/mesh_utils.py:138-180
+ * extract_mesh_bounded, which hands the work to Open3D's ScalableTSDFVolume) ----
+ * Open3D's volume could be neither read nor run where this was written.  The rules below ARE the specification; nothing
+ * was compared with Open3D's own output.  All quantities are fp32 unless said otherwise, every product and sum rounded on
+ * its own (no fp contraction), sums of three terms as (a + b) + c.
+ *
+ * Geometry.  A voxel has integer coordinates g = (gx, gy, gz); its sample point is its centre, voxel_length (g + 0.5).  A
+ * block is 16^3 voxels: b = floor(g / 16) per axis (negative coordinates included), local index l = g - 16 b, linear index
+ * (lx 16 + ly) 16 + lz.  Block key = (bx + 2^20) << 42 | (by + 2^20) << 21 | (bz + 2^20), each component in [-2^20, 2^20).
+ * Ascending key order is the lexicographic order of (bx, by, bz); it is the block order of every output.
+ *
+ * Views.  depth[V, H, W] (0 = no measurement), rgb[V, H, W, 3] uint8 (optional), cam[V, 16] = the world-to-camera matrix
+ * E[3, 4] row-major (p_cam = R p_w + t) followed by the pinhole fx, fy, cx, cy.  All views share one resolution.
+ *
+ * Touch (which blocks exist, and which views may write to them).  For view i, every pixel (u, v) with u % stride == 0,
+ * v % stride == 0 and d = depth_i[v, u] > 0:  p_cam = ((u - cx) d / fx, (v - cy) d / fy, d),  p_w = R^T (p_cam - t);  every
+ * block that meets the box [p_w - sdf_trunc, p_w + sdf_trunc] - per axis floor((p_w -+ sdf_trunc) / (16 voxel_length)) -
+ * exists and carries bit i of its view mask (word i / 32, bit i % 32).  sdf_trunc <= 16 voxel_length is required, so at
+ * most 27 blocks per pixel.
+ *
+ * Integrate.  Every voxel starts with tsdf = 0, w = 0, colour = 0.  Views run in order; view i skips a block whose mask
+ * lacks bit i.  For the rest:  p = E [centre 1], skip unless p.z > 0;  u_f = p.x fx / p.z + cx + 0.5, v_f likewise;  skip
+ * unless 1e-4 <= u_f < W - 1e-4 and 1e-4 <= v_f < H - 1e-4;  u = (int)u_f, v = (int)v_f (the nearest pixel, no
+ * interpolation);  d = depth_i[v, u], skip unless d > 0;  sdf = (d - p.z) sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1);
+ * where sdf > -sdf_trunc:  tsdf = (tsdf w + min(1, sdf / sdf_trunc)) / (w + 1),  colour = (colour w + rgb_i[v, u]) / (w + 1)
+ * per channel in [0, 255],  w += 1.
+ *
+ * Surface (surface nets over the voxel centres: the rules of scorp_isosurface_* applied through block borders, level 0,
+ * inside = tsdf < 0).  Cell g has the corners g + {0, 1}^3 and belongs to the block of g.  It is VALID when all eight
+ * corners lie in existing blocks and have w > 0, ACTIVE when it is valid and its corners are neither all inside nor all
+ * outside.  An active cell owns one vertex: the mean of its edge crossings, in the edge order of scorp_isosurface_*, at
+ * voxel_length ((g + 0.5) + frac); its colour is the mean over the same edges of the linearly interpolated voxel colours
+ * c0 + t (c1 - c0), divided by 255.  A lattice edge q -> q + e_a whose ends differ in inside-ness and whose four
+ * surrounding cells are all valid gives the quad of those cells, diagonal and winding as in scorp_isosurface_* (the normal
+ * points from inside to outside); it belongs to the block of q.  Vertices come in ascending (block rank, local cell index),
+ * quads in ascending (block rank, local index of q, axis).  No atomic decides a position; the scans are the caller's.
+ *
+ *   touch:      keys[num_slots] (uint64) and view_mask[num_slots, ceil(V / 32)] (uint32) form an open-addressing table the
+ *               call clears itself (empty key = all ones), *overflow (uint32) likewise.  One lane per sampled pixel; a key
+ *               is claimed by one 64-bit compare-and-swap, linear probing bounded by num_slots, the view bit set by atomicOr.
+ *               When probing is exhausted the insert is dropped, bit 0 of *overflow is set and the inserts still to come are dropped
+ *               unprobed: the table is then incomplete in an order-dependent way (the caller doubles num_slots
+ *               and repeats); bit 1 is set for a point whose blocks leave [-2^20, 2^20) (or are not finite).  The slot of a
+ *               key depends on the order of arrival; the set of keys and their masks do not.
+ *   (caller):   keys != empty, sorted ascending, the masks gathered by the same permutation: block_keys[B], view_mask[B, words].
+ *   neighbors:  out_nbr[B, 27] int32, entry (dx + 1) 9 + (dy + 1) 3 + (dz + 1) = the rank of block b + (dx, dy, dz) or -1
+ *               (binary search in block_keys).
+ *   integrate:  out_tsdf[B, 4096], out_weight[B, 4096] (fp32 counts), out_colour[B, 4096, 3] (NULL: views->rgb is not read),
+ *               every entry written once.
+ *   isosurface_blocks_count_cells / emit_vertices / count_faces / emit_faces: the flag, scan and count contracts of the dense
+ *               four over B 4096 cells / lattice points; emit_vertices also writes out_colours[num_vertices, 3] in [0, 1]
+ *               unless it or colour is NULL.
+ * None synchronises.  SCORP_ERR_INVALID: a NULL pointer (other than the optional ones), num_views < 1 or > 65535, stride < 1,
+ * voxel_length <= 0, sdf_trunc <= 0 or > 16 voxel_length, num_slots not a power of two (or > 2^32), num_blocks < 1 or
+ * > (2^31 - 1) / 16, more than 2^31 - 1 vertices or quads, a colour output without its input. */
+typedef struct ScorpTsdfBlockViews {
+  const float *depth;
+  const uint8_t *rgb;
+  const float *cam;
+  int32_t num_views, width, height, _pad;
+} ScorpTsdfBlockViews;
+int scorp_tsdf_blocks_touch(const ScorpTsdfBlockViews *views, float voxel_length, float sdf_trunc, int32_t stride, uint64_t *keys,
+                            uint32_t *view_mask, uint64_t num_slots, uint32_t *overflow, scorp_stream_t stream);
+int scorp_tsdf_blocks_neighbors(const uint64_t *block_keys, int64_t num_blocks, int32_t *out_nbr, scorp_stream_t stream);
+int scorp_tsdf_blocks_integrate(const ScorpTsdfBlockViews *views, float voxel_length, float sdf_trunc, const uint64_t *block_keys,
+                                const uint32_t *view_mask, int64_t num_blocks, float *out_tsdf, float *out_weight,
+                                float *out_colour, scorp_stream_t stream);
+int scorp_isosurface_blocks_count_cells(const float *tsdf, const float *weight, const int32_t *nbr, int64_t num_blocks,
+                                        uint8_t *out_flags, scorp_stream_t stream);
+int scorp_isosurface_blocks_emit_vertices(const float *tsdf, const float *weight, const float *colour, const uint64_t *block_keys,
+                                          const int32_t *nbr, int64_t num_blocks, float voxel_length, const int32_t *cell_scan,
+                                          int64_t num_vertices, float *out_vertices, float *out_colours, scorp_stream_t stream);
+int scorp_isosurface_blocks_count_faces(const float *tsdf, const float *weight, const int32_t *nbr, int64_t num_blocks,
+                                        uint8_t *out_counts, scorp_stream_t stream);
+int scorp_isosurface_blocks_emit_faces(const float *tsdf, const float *weight, const int32_t *nbr, int64_t num_blocks,
+                                       const int32_t *cell_scan, const int32_t *edge_scan, int64_t num_quads, int32_t *out_faces,
+                                       scorp_stream_t stream);
+
 /* ---- introspection for stage-level parity tests (device->host copies; synchronises) ---- */
 /* xy[N,2], depth[N], conic_opacity[N,4], rgb[N,3], rect[N,4] (tile units, max exclusive); any may be NULL. */
 int scorp_gs3d_debug_geom(const void *state, int32_t num_gaussians, int32_t image_width, int32_t image_height,

@@ -92,6 +92,11 @@ class ScorpTsdfParams(ctypes.Structure):
                 ("contracted", ctypes.c_int32), ("_pad", ctypes.c_int32)]
 
 
+class ScorpTsdfBlockViews(ctypes.Structure):
+    _fields_ = [("depth", c_float_p), ("rgb", ctypes.c_void_p), ("cam", c_float_p), ("num_views", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
 class ScorpRowTensor(ctypes.Structure):
     _fields_ = [("src", c_float_p), ("dst", c_float_p), ("row_floats", ctypes.c_uint32), ("zero_if_fresh", ctypes.c_uint32)]
 
@@ -123,6 +128,9 @@ EXPORTS = [
     "scorp_tsdf_fuse", "scorp_isosurface_count_cells", "scorp_isosurface_emit_vertices", "scorp_isosurface_count_faces",
     "scorp_isosurface_emit_faces",
     "scorp_mesh_cluster_link", "scorp_mesh_cluster_roots", "scorp_mesh_cluster_stats",
+    "scorp_tsdf_blocks_touch", "scorp_tsdf_blocks_neighbors", "scorp_tsdf_blocks_integrate",
+    "scorp_isosurface_blocks_count_cells", "scorp_isosurface_blocks_emit_vertices", "scorp_isosurface_blocks_count_faces",
+    "scorp_isosurface_blocks_emit_faces",
 ]
 
 BACKWARD_EXACT_FP32 = 1   # scorp_gs3d_backward_ex flag (include/scorp_gs.h)
@@ -242,6 +250,14 @@ def lib():
     L.scorp_mesh_cluster_link.argtypes = [vp, i64, vp, vp, u64, vp, vp]
     L.scorp_mesh_cluster_roots.argtypes = [vp, i64, vp, vp, vp]
     L.scorp_mesh_cluster_stats.argtypes = [vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp]
+    bv, f32 = ctypes.POINTER(ScorpTsdfBlockViews), ctypes.c_float
+    L.scorp_tsdf_blocks_touch.argtypes = [bv, f32, f32, i32, vp, vp, u64, vp, vp]
+    L.scorp_tsdf_blocks_neighbors.argtypes = [vp, i64, vp, vp]
+    L.scorp_tsdf_blocks_integrate.argtypes = [bv, f32, f32, vp, vp, i64, vp, vp, vp, vp]
+    L.scorp_isosurface_blocks_count_cells.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.scorp_isosurface_blocks_emit_vertices.argtypes = [vp, vp, vp, vp, vp, i64, f32, vp, i64, vp, vp, vp]
+    L.scorp_isosurface_blocks_count_faces.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.scorp_isosurface_blocks_emit_faces.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp]
     L.scorp_prof_enable.argtypes = [ctypes.c_int]
     L.scorp_prof_select.argtypes = [u64]
     L.scorp_prof_kernel_name.restype = ctypes.c_char_p
