@@ -352,6 +352,51 @@ int scorp_isosurface_count_faces(const float *f, int32_t nx, int32_t ny, int32_t
 int scorp_isosurface_emit_faces(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, const int32_t *cell_scan,
                                 const int32_t *edge_scan, int64_t num_quads, int32_t *out_faces, scorp_stream_t stream);
 
+/* ---- marching cubes on a dense grid: one vertex per crossed lattice edge, triangles from a generated case table ----
+ * Grid, coordinates, INSIDE (f < level) and corner numbering (n = 4 di + 2 dj + dk) as for scorp_isosurface_*.  The edges of a
+ * cell are numbered 0 .. 11: the x-edges, then the y-edges, then the z-edges, each by ascending first corner (x: corners 0, 1,
+ * 2, 3; y: 0, 1, 4, 5; z: 0, 2, 4, 6); edge e has the axis e / 4.  The CASE of a cell has bit n set when corner n is inside.
+ *
+ * Vertices.  A lattice edge q -> q + e_a (q_a + 1 < n_a) whose ends differ in inside-ness carries ONE vertex, shared by every
+ * cell round it: along the axis c[q_a] + t (c[q_a + 1] - c[q_a]) with t = (level - f0) / (f1 - f0), f0 = f(q), f1 = f(q + e_a)
+ * (fp32, no contraction), the other two coordinates straight from the coordinate arrays.  Vertices come in ascending (linear
+ * index of q, axis).  A crossing exactly on a lattice point (f0 == level) gives coincident vertices and zero-area triangles;
+ * they are kept.
+ *
+ * Triangles.  The table (csrc/mc_table.hpp, generated by scorp_amd/mc_table.py: 256 rows of 16 bytes = five triangles x three
+ * edge ids, 0xFF padding, the count in the last byte) follows this rule.  Each of the six cube faces has 0, 2 or 4 crossed
+ * edges; two crossings are joined; with four (two inside corners on a face diagonal) the two edges at each INSIDE corner are
+ * joined, the inside corners being cut off separately.  The choice depends on the face's four signs alone, so the two cells
+ * that share a face agree and the surface is closed.  Every crossed edge then has two partners; the loops are the cycles of
+ * that graph, opened at the lowest unused edge id, oriented so that the Newell normal over the edge midpoints agrees with the
+ * sum over the loop's edges of (outside end - inside end), and rotated to start at their lowest edge id.  A loop p[0 .. k - 1]
+ * is triangulated by the first triangulation none of whose diagonals joins two crossings on one cube face, in this order:
+ * tri(p) = the triangle (p[0], p[m], p[k - 1]) with the apex m descending from k - 2 to 1, for each apex every tri(p[0 .. m])
+ * (outer) with every tri(p[m .. k - 1]) (inner), listed left part, apex triangle, right part - the fan from p[0] comes first.
+ * The normals point from inside to outside.  The table is this project's own; it was compared with no other library's.
+ * Triangles come in ascending cell index, then table order; the index of edge id e of cell c is the vertex of the lattice edge
+ * (q, a) = (c + corner(n0(e)), e / 4):  edge_scan[q] - popc(mask[q]) + popc(mask[q] & ((1 << a) - 1)).
+ *
+ * Two passes with a scan (the caller's) between them, no atomics:
+ *   count_edges:   out_masks[nx ny nz]: bit a set when the edge q -> q + e_a exists and is crossed; out_counts = its popcount
+ *   emit_vertices: edge_scan[nx ny nz] = the INCLUSIVE int32 prefix sum of the counts; the vertices of q from
+ *                  edge_scan[q] - popc(mask[q]) on into out_vertices[num_vertices, 3]
+ *   count_faces:   out_counts[cells] = triangles of cell c (0 .. 5)
+ *   emit_faces:    face_scan[cells] = the inclusive int32 prefix sum of those counts; the triangles of cell c from
+ *                  face_scan[c] - count on into out_faces[num_faces, 3] (int32 vertex indices)
+ * None synchronises.  SCORP_ERR_INVALID: a NULL pointer, a dimension < 2, more than (2^31 - 1) 256 lattice points, more
+ * than 2^31 - 1 vertices or triangles. */
+int scorp_marching_cubes_count_edges(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, uint8_t *out_masks,
+                                     uint8_t *out_counts, scorp_stream_t stream);
+int scorp_marching_cubes_emit_vertices(const float *f, const float *x, const float *y, const float *z, int32_t nx, int32_t ny,
+                                       int32_t nz, float level, const uint8_t *edge_masks, const int32_t *edge_scan,
+                                       int64_t num_vertices, float *out_vertices, scorp_stream_t stream);
+int scorp_marching_cubes_count_faces(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, uint8_t *out_counts,
+                                     scorp_stream_t stream);
+int scorp_marching_cubes_emit_faces(const float *f, int32_t nx, int32_t ny, int32_t nz, float level, const uint8_t *edge_masks,
+                                    const int32_t *edge_scan, const int32_t *face_scan, int64_t num_faces, int32_t *out_faces,
+                                    scorp_stream_t stream);
+
 /* ---- connected triangles of a mesh (Open3D's cluster_connected_triangles, as gs2dgs/utils/mesh_utils.py:30 calls it) ----
  * faces[num_faces, 3] int32 vertex indices, each in [0, 2^31 - 1].  Two triangles are ADJACENT when they share an edge, an
  * edge being the unordered pair of vertex INDICES: positions do not count, and two triangles that touch at one vertex are
@@ -459,6 +504,26 @@ int scorp_isosurface_blocks_count_faces(const float *tsdf, const float *weight, 
 int scorp_isosurface_blocks_emit_faces(const float *tsdf, const float *weight, const int32_t *nbr, int64_t num_blocks,
                                        const int32_t *cell_scan, const int32_t *edge_scan, int64_t num_quads, int32_t *out_faces,
                                        scorp_stream_t stream);
+
+/* Marching cubes over the same block volume: the rules of scorp_marching_cubes_* applied through block borders, level 0,
+ * inside = tsdf < 0, cell validity as above (all eight corners in existing blocks with w > 0).  A lattice edge q -> q + e_a
+ * carries a vertex when its ends differ in inside-ness and at least one of the four cells round it is valid (both ends are
+ * then valid), so no vertex is left unused at a rim; only valid cells emit triangles.  An edge belongs to the block of q, a
+ * cell and its triangles to the block of g.  Vertices come in ascending (block rank, local index of q, axis), triangles in
+ * ascending (block rank, local cell index, table order).  Position: voxel_length ((g + 0.5) + t e_a), t = (0 - f0) / (f1 - f0);
+ * colour (c0 + t (c1 - c0)) / 255, optional as above.  The mask, count and scan contracts are those of the dense four over
+ * B 4096 lattice points / cells.  SCORP_ERR_INVALID as for scorp_isosurface_blocks_*. */
+int scorp_marching_cubes_blocks_count_edges(const float *tsdf, const float *weight, const int32_t *nbr, int64_t num_blocks,
+                                            uint8_t *out_masks, uint8_t *out_counts, scorp_stream_t stream);
+int scorp_marching_cubes_blocks_emit_vertices(const float *tsdf, const float *weight, const float *colour, const uint64_t *block_keys,
+                                              const int32_t *nbr, int64_t num_blocks, float voxel_length, const uint8_t *edge_masks,
+                                              const int32_t *edge_scan, int64_t num_vertices, float *out_vertices,
+                                              float *out_colours, scorp_stream_t stream);
+int scorp_marching_cubes_blocks_count_faces(const float *tsdf, const float *weight, const int32_t *nbr, int64_t num_blocks,
+                                            uint8_t *out_counts, scorp_stream_t stream);
+int scorp_marching_cubes_blocks_emit_faces(const float *tsdf, const float *weight, const int32_t *nbr, int64_t num_blocks,
+                                           const uint8_t *edge_masks, const int32_t *edge_scan, const int32_t *face_scan,
+                                           int64_t num_faces, int32_t *out_faces, scorp_stream_t stream);
 
 /* ---- introspection for stage-level parity tests (device->host copies; synchronises) ---- */
 /* xy[N,2], depth[N], conic_opacity[N,4], rgb[N,3], rect[N,4] (tile units, max exclusive); any may be NULL. */

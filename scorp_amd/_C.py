@@ -131,6 +131,10 @@ EXPORTS = [
     "scorp_tsdf_blocks_touch", "scorp_tsdf_blocks_neighbors", "scorp_tsdf_blocks_integrate",
     "scorp_isosurface_blocks_count_cells", "scorp_isosurface_blocks_emit_vertices", "scorp_isosurface_blocks_count_faces",
     "scorp_isosurface_blocks_emit_faces",
+    "scorp_marching_cubes_count_edges", "scorp_marching_cubes_emit_vertices", "scorp_marching_cubes_count_faces",
+    "scorp_marching_cubes_emit_faces",
+    "scorp_marching_cubes_blocks_count_edges", "scorp_marching_cubes_blocks_emit_vertices", "scorp_marching_cubes_blocks_count_faces",
+    "scorp_marching_cubes_blocks_emit_faces",
 ]
 
 BACKWARD_EXACT_FP32 = 1   # scorp_gs3d_backward_ex flag (include/scorp_gs.h)
@@ -258,6 +262,14 @@ def lib():
     L.scorp_isosurface_blocks_emit_vertices.argtypes = [vp, vp, vp, vp, vp, i64, f32, vp, i64, vp, vp, vp]
     L.scorp_isosurface_blocks_count_faces.argtypes = [vp, vp, vp, i64, vp, vp]
     L.scorp_isosurface_blocks_emit_faces.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp]
+    L.scorp_marching_cubes_count_edges.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp]
+    L.scorp_marching_cubes_emit_vertices.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, i64, vp, vp]
+    L.scorp_marching_cubes_count_faces.argtypes = [vp, i32, i32, i32, f32, vp, vp]
+    L.scorp_marching_cubes_emit_faces.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, i64, vp, vp]
+    L.scorp_marching_cubes_blocks_count_edges.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    L.scorp_marching_cubes_blocks_emit_vertices.argtypes = [vp, vp, vp, vp, vp, i64, f32, vp, vp, i64, vp, vp, vp]
+    L.scorp_marching_cubes_blocks_count_faces.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.scorp_marching_cubes_blocks_emit_faces.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, vp, vp]
     L.scorp_prof_enable.argtypes = [ctypes.c_int]
     L.scorp_prof_select.argtypes = [u64]
     L.scorp_prof_kernel_name.restype = ctypes.c_char_p

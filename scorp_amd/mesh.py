@@ -8,15 +8,17 @@ gs2dgs/utils/mcube_utils.py, on the GPU.
 
 The depth and colour maps stay on the device as two stacked tensors.  The TSDF of every sample is fused over all views by
 one launch (csrc/tsdf.hip: scorp_tsdf_fuse), the volume is ONE dense grid (no 512^3 crops, so no crop seams and no
-restriction of `resolution` to multiples of 512), and the surface is extracted by surface nets (csrc/isosurface.hip) -
-not marching cubes: one vertex per cell the surface crosses, which lies in the same cell as the marching-cubes vertices
-of that cell.  `post_process_mesh` (mesh_utils.py:22-43) drops the floaters: the triangles are clustered over shared edges
+restriction of `resolution` to multiples of 512), and the surface is extracted by surface nets (csrc/isosurface.hip: one
+vertex per cell the surface crosses, which lies in the same cell as the marching-cubes vertices of that cell) or, with
+method="marching_cubes", by marching cubes (csrc/marching_cubes.hip: one vertex per crossed lattice edge, the triangles
+from the case table that scorp_amd/mc_table.py generates).  `post_process_mesh` (mesh_utils.py:22-43) drops the floaters: the triangles are clustered over shared edges
 by a lock-free union-find on the device (csrc/mesh_cluster.hip, Open3D's cluster_connected_triangles), the largest
 clusters are kept and the mesh is compacted with torch ops, without a mesh-sized array visiting the host.
 `extract_mesh_bounded`, the route the 2DGS paper reports its meshes with, fuses the same maps into a SPARSE volume instead:
 16^3-voxel blocks that exist only within sdf_trunc of an observed depth point (csrc/tsdf_blocks.hip: a hashed block set, one
 workgroup per block with the view loop inside), meshed by surface nets whose corner fetch goes through a block-neighbour table
-(csrc/isosurface_blocks.hip).  The reference hands this to Open3D's ScalableTSDFVolume and marching cubes; the volume here
+(csrc/isosurface_blocks.hip) or by marching cubes that does (csrc/marching_cubes_blocks.hip).  The reference hands this to
+Open3D's ScalableTSDFVolume and its marching cubes; the volume here
 follows the rules written down in include/scorp_gs.h and was never compared with Open3D's own output, which was not
 available.  Mesh simplification is not built.
 
@@ -30,7 +32,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from . import _C
+from . import _C, mc_table
 
 MAX_RANGE = 32.0            # mcube_utils.py:26,93: the un-contracted vertices are clipped to +-max_range
 LAUNCH_SAMPLES = 1 << 30    # samples per scorp_tsdf_fuse call (the C ABI takes up to (2^31 - 1) * 256)
@@ -247,10 +249,103 @@ def _surface_nets_numpy(f, coords, level):
     return verts, faces
 
 
-def extract_surface(grid, coords, level=0.0):
-    """The surface f = level of the dense grid [X, Y, Z] (inside: f < level) over the lattice coords = (x, y, z) by surface
-    nets: (vertices [Nv, 3] float32, faces [Nf, 3] int32) on the grid's device, in the fixed order of include/scorp_gs.h.
-    The triangles' normals point from inside to outside."""
+METHODS = ("surface_nets", "marching_cubes")
+
+
+def _check_method(method):
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}; got {method!r}")
+
+
+def _mc_faces_numpy(case, emit, vid, table):
+    """The triangles of the cells case [..., X, Y, Z] (emit: which cells may emit) through the per-edge vertex ids
+    vid [..., X + 1, Y + 1, Z + 1, 3], in ascending cell index, then table order."""
+    n = np.where(emit, table[case, 15], 0)
+    cells = np.nonzero(n > 0)
+    rows = table[case[cells]]                                   # [m, 16]
+    e = rows[:, :15].reshape(-1, 5, 3).astype(np.int64)
+    live = np.arange(5)[None, :] < rows[:, 15:16]               # [m, 5]
+    e = np.where(live[..., None], e, 0)
+    n0, axis = mc_table.EDGE_N0[e], mc_table.EDGE_AXIS[e]
+    at = tuple(c[:, None, None] for c in cells[:-3]) + tuple(
+        cells[-3 + d][:, None, None] + ((n0 >> (2 - d)) & 1) for d in range(3)) + (axis,)
+    return vid[at][live].astype(np.int32).reshape(-1, 3)
+
+
+def _marching_cubes_numpy(f, coords, level):
+    """The marching-cubes rules of include/scorp_gs.h in vectorised numpy float32: the CPU form of extract_surface."""
+    f = np.ascontiguousarray(f, np.float32)
+    X, Y, Z = f.shape
+    level = np.float32(level)
+    inside = f < level
+    E = np.zeros((X, Y, Z, 3), bool)
+    E[:-1, :, :, 0] = inside[:-1] != inside[1:]
+    E[:, :-1, :, 1] = inside[:, :-1] != inside[:, 1:]
+    E[:, :, :-1, 2] = inside[:, :, :-1] != inside[:, :, 1:]
+    vid = (np.cumsum(E.ravel(), dtype=np.int64) - 1).reshape(E.shape)   # C order of [X, Y, Z, 3]: ascending (q, axis)
+    q = np.stack(np.nonzero(E), 1)
+    qa = q[:, 3]
+    q1 = q[:, :3] + np.eye(3, dtype=np.int64)[qa]
+    f0, f1 = f[q[:, 0], q[:, 1], q[:, 2]], f[q1[:, 0], q1[:, 1], q1[:, 2]]
+    with np.errstate(all="ignore"):
+        t = (level - f0) / (f1 - f0)
+    verts = np.empty((q.shape[0], 3), np.float32)
+    for d, c in enumerate(coords):
+        c = np.asarray(c, np.float32)
+        c0, c1 = c[q[:, d]], c[q1[:, d]]
+        verts[:, d] = np.where(qa == d, c0 + t * (c1 - c0), c0)
+    case = np.zeros((X - 1, Y - 1, Z - 1), np.int64)
+    for n in range(8):
+        di, dj, dk = n >> 2, (n >> 1) & 1, n & 1
+        case |= inside[di:X - 1 + di, dj:Y - 1 + dj, dk:Z - 1 + dk].astype(np.int64) << n
+    return verts, _mc_faces_numpy(case, np.ones(case.shape, bool), vid, mc_table.cached_table())
+
+
+def _marching_cubes_gpu(f, xyz, level):
+    L = _C.lib()
+    dev = f.device
+    X, Y, Z = f.shape
+    verts = torch.empty(0, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(0, 3, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = _C.current_stream_ptr()
+        masks = torch.empty(X * Y * Z, dtype=torch.uint8, device=dev)
+        counts = torch.empty(X * Y * Z, dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_marching_cubes_count_edges(f.data_ptr(), X, Y, Z, level, masks.data_ptr(), counts.data_ptr(), stream),
+                 "scorp_marching_cubes_count_edges")
+        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64)
+        nv = int(edge_scan[-1])
+        if nv >= 2 ** 31:
+            raise ValueError("the surface has more than 2^31 - 1 vertices")
+        if nv == 0:
+            return verts, faces
+        edge_scan = edge_scan.to(torch.int32)
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        _C.check(L.scorp_marching_cubes_emit_vertices(f.data_ptr(), xyz[0].data_ptr(), xyz[1].data_ptr(), xyz[2].data_ptr(), X, Y, Z,
+                                                      level, masks.data_ptr(), edge_scan.data_ptr(), nv, verts.data_ptr(), stream),
+                 "scorp_marching_cubes_emit_vertices")
+        counts = torch.empty((X - 1) * (Y - 1) * (Z - 1), dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_marching_cubes_count_faces(f.data_ptr(), X, Y, Z, level, counts.data_ptr(), stream), "scorp_marching_cubes_count_faces")
+        face_scan = torch.cumsum(counts, 0, dtype=torch.int64)
+        nf = int(face_scan[-1])
+        if nf >= 2 ** 31:
+            raise ValueError("the surface has more than 2^31 - 1 triangles")
+        if nf == 0:
+            return verts, faces
+        face_scan = face_scan.to(torch.int32)
+        faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+        _C.check(L.scorp_marching_cubes_emit_faces(f.data_ptr(), X, Y, Z, level, masks.data_ptr(), edge_scan.data_ptr(),
+                                                   face_scan.data_ptr(), nf, faces.data_ptr(), stream), "scorp_marching_cubes_emit_faces")
+    return verts, faces
+
+
+def extract_surface(grid, coords, level=0.0, method="surface_nets"):
+    """The surface f = level of the dense grid [X, Y, Z] (inside: f < level) over the lattice coords = (x, y, z):
+    (vertices [Nv, 3] float32, faces [Nf, 3] int32) on the grid's device, in the fixed order of include/scorp_gs.h.
+    method "surface_nets" puts one vertex in every cell the surface crosses; "marching_cubes" one on every lattice edge it
+    crosses, with the triangles of the case table of scorp_amd/mc_table.py.  The triangles' normals point from inside to
+    outside."""
+    _check_method(method)
     if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
         raise ValueError("grid must be a [X, Y, Z] tensor")
     if len(coords) != 3 or any(c.dim() != 1 or c.numel() != n for c, n in zip(coords, grid.shape)):
@@ -261,8 +356,11 @@ def extract_surface(grid, coords, level=0.0):
     f = grid.to(torch.float32).contiguous()
     xyz = [c.to(device=dev, dtype=torch.float32).contiguous() for c in coords]
     if dev.type != "cuda":
-        v, t = _surface_nets_numpy(f.numpy(), [c.numpy() for c in xyz], level)
+        form = _marching_cubes_numpy if method == "marching_cubes" else _surface_nets_numpy
+        v, t = form(f.numpy(), [c.numpy() for c in xyz], level)
         return torch.from_numpy(v), torch.from_numpy(t)
+    if method == "marching_cubes":
+        return _marching_cubes_gpu(f, xyz, float(level))
     L = _C.lib()
     X, Y, Z = f.shape
     level = float(level)
@@ -617,10 +715,101 @@ def _surface_blocks_numpy(keys, nbr, tsdf, weight, colour, voxel_length):
     return verts, faces, cols
 
 
-def extract_surface_blocks(volume):
-    """The zero surface of a BlockVolume by surface nets through the block borders (include/scorp_gs.h): a Mesh on the volume's
-    device, vertices in ascending (block, local cell index), colours in [0, 1] (zeros for a volume without colour).  Cells
-    with a corner no view has written, or in a block that does not exist, carry no vertex and no face."""
+def _marching_cubes_blocks_numpy(keys, nbr, tsdf, weight, colour, voxel_length):
+    """The marching-cubes surface rule of include/scorp_gs.h in vectorised numpy float32: (vertices, faces, colours or None)."""
+    f = np.float32
+    B = keys.size
+    coords = np.stack([((keys >> s) & 0x1FFFFF) - KEY_BIAS for s in (42, 21, 0)], -1)
+    nbr = nbr.copy()
+    nbr[:, 13] = np.arange(B)
+    shape = (B, 16, 16, 16)
+    T = _pad_blocks(tsdf.reshape(shape), nbr, -1, 17, f(0))          # local -1 .. 16 at index 0 .. 17
+    valid = _pad_blocks(weight.reshape(shape), nbr, -1, 17, f(0)) > 0
+    inside = (T < 0) & valid
+    cell_valid = np.ones((B, 17, 17, 17), bool)                      # cells -1 .. 15 at index 0 .. 16
+    for n in range(8):
+        di, dj, dk = n >> 2, (n >> 1) & 1, n & 1
+        cell_valid &= valid[:, di:di + 17, dj:dj + 17, dk:dk + 17]
+    own = lambda a, off=(0, 0, 0): a[:, 1 + off[0]:17 + off[0], 1 + off[1]:17 + off[1], 1 + off[2]:17 + off[2]]
+    eye = np.eye(3, dtype=np.int64)
+    E = np.zeros(shape + (3,), bool)
+    for a in range(3):
+        b, c = eye[(a + 1) % 3], eye[(a + 2) % 3]
+        some = np.zeros(shape, bool)
+        for off in (0 * b, -b, -b - c, -c):
+            some |= own(cell_valid, off)
+        E[..., a] = (own(inside) != own(inside, eye[a])) & some
+    vid = (np.cumsum(E.ravel(), dtype=np.int64) - 1).reshape(E.shape)   # ascending (block rank, local q, axis)
+    qb, qi, qj, qk, qa = np.nonzero(E)
+    q = np.stack([qi, qj, qk], 1)
+    q1 = q + eye[qa]
+    f0, f1 = T[qb, q[:, 0] + 1, q[:, 1] + 1, q[:, 2] + 1], T[qb, q1[:, 0] + 1, q1[:, 1] + 1, q1[:, 2] + 1]
+    with np.errstate(all="ignore"):
+        t = (f(0) - f0) / (f1 - f0)
+    verts = np.empty((qb.size, 3), f)
+    for d in range(3):
+        g = (coords[qb, d] * 16 + q[:, d]).astype(f) + f(0.5)
+        verts[:, d] = f(voxel_length) * np.where(qa == d, g + t, g)
+    cols = None
+    if colour is not None:
+        Cc = _pad_blocks(colour.reshape(shape + (3,)), nbr, 0, 17, f(0))
+        c0, c1 = Cc[qb, q[:, 0], q[:, 1], q[:, 2]], Cc[qb, q1[:, 0], q1[:, 1], q1[:, 2]]
+        cols = ((c0 + t[:, None] * (c1 - c0)) / f(255)).astype(f)
+    case = np.zeros(shape, np.int64)
+    for n in range(8):
+        case |= own(inside, (n >> 2, (n >> 1) & 1, n & 1)).astype(np.int64) << n
+    vid = _pad_blocks(np.where(E, vid, -1), nbr, 0, 17, -1)          # local 0 .. 16: the edges of the cells' far corners
+    return verts, _mc_faces_numpy(case, cell_valid[:, 1:, 1:, 1:], vid, mc_table.cached_table()), cols
+
+
+def _marching_cubes_blocks_gpu(keys, nbr, tsdf, weight, colour, voxel_length, empty):
+    L = _C.lib()
+    dev = tsdf.device
+    B = keys.numel()
+    with torch.cuda.device(dev):
+        stream = _C.current_stream_ptr()
+        masks = torch.empty(B * BLOCK_VOXELS, dtype=torch.uint8, device=dev)
+        counts = torch.empty(B * BLOCK_VOXELS, dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_marching_cubes_blocks_count_edges(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, masks.data_ptr(),
+                                                           counts.data_ptr(), stream), "scorp_marching_cubes_blocks_count_edges")
+        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64)
+        nv = int(edge_scan[-1])
+        if nv >= 2 ** 31:
+            raise ValueError("the surface has more than 2^31 - 1 vertices")
+        if nv == 0:
+            return empty
+        edge_scan = edge_scan.to(torch.int32)
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        cols = torch.empty(nv, 3, dtype=torch.float32, device=dev) if colour is not None else None
+        _C.check(L.scorp_marching_cubes_blocks_emit_vertices(tsdf.data_ptr(), weight.data_ptr(),
+                                                             colour.data_ptr() if colour is not None else None, keys.data_ptr(),
+                                                             nbr.data_ptr(), B, voxel_length, masks.data_ptr(), edge_scan.data_ptr(), nv,
+                                                             verts.data_ptr(), cols.data_ptr() if cols is not None else None, stream),
+                 "scorp_marching_cubes_blocks_emit_vertices")
+        if cols is None:
+            cols = torch.zeros(nv, 3, dtype=torch.float32, device=dev)
+        _C.check(L.scorp_marching_cubes_blocks_count_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, counts.data_ptr(), stream),
+                 "scorp_marching_cubes_blocks_count_faces")
+        face_scan = torch.cumsum(counts, 0, dtype=torch.int64)
+        nf = int(face_scan[-1])
+        if nf >= 2 ** 31:
+            raise ValueError("the surface has more than 2^31 - 1 triangles")
+        faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+        if nf:
+            face_scan = face_scan.to(torch.int32)
+            _C.check(L.scorp_marching_cubes_blocks_emit_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, masks.data_ptr(),
+                                                              edge_scan.data_ptr(), face_scan.data_ptr(), nf, faces.data_ptr(), stream),
+                     "scorp_marching_cubes_blocks_emit_faces")
+    return Mesh(verts, faces, cols)
+
+
+def extract_surface_blocks(volume, method="surface_nets"):
+    """The zero surface of a BlockVolume through the block borders (include/scorp_gs.h): a Mesh on the volume's device, colours
+    in [0, 1] (zeros for a volume without colour).  method "surface_nets": vertices in ascending (block, local cell index);
+    cells with a corner no view has written, or in a block that does not exist, carry no vertex and no face.
+    "marching_cubes": one vertex per crossed lattice edge that has a valid cell round it, in ascending (block, local index of
+    the edge's first point, axis); only valid cells emit triangles."""
+    _check_method(method)
     keys, tsdf, weight, colour = volume.keys, volume.tsdf, volume.weight, volume.colour
     dev = tsdf.device
     B = keys.numel()
@@ -637,9 +826,11 @@ def extract_surface_blocks(volume):
     voxel_length = float(np.float32(volume.voxel_length))
     nbr = block_neighbors(keys)
     if dev.type != "cuda":
-        v, t, c = _surface_blocks_numpy(keys.numpy(), nbr.numpy(), tsdf.numpy(), weight.numpy(),
-                                        colour.numpy() if colour is not None else None, voxel_length)
+        form = _marching_cubes_blocks_numpy if method == "marching_cubes" else _surface_blocks_numpy
+        v, t, c = form(keys.numpy(), nbr.numpy(), tsdf.numpy(), weight.numpy(), colour.numpy() if colour is not None else None, voxel_length)
         return Mesh(torch.from_numpy(v), torch.from_numpy(t), torch.from_numpy(c) if c is not None else torch.zeros(v.shape[0], 3))
+    if method == "marching_cubes":
+        return _marching_cubes_blocks_gpu(keys, nbr, tsdf, weight, colour, voxel_length, empty)
     L = _C.lib()
     with torch.cuda.device(dev):
         stream = _C.current_stream_ptr()
@@ -911,11 +1102,13 @@ class GaussianExtractor:
         return self.compute_unbounded_tsdf(coords, True, voxel_size), coords
 
     @torch.no_grad()
-    def extract_mesh_unbounded(self, resolution=1024):
-        """mesh_utils.py:182-278: the TSDF volume of the contracted space, its zero surface, the vertices un-contracted and
-        clipped to +-32, coloured by a second fusion pass over the vertices."""
+    def extract_mesh_unbounded(self, resolution=1024, method="surface_nets"):
+        """mesh_utils.py:182-278: the TSDF volume of the contracted space, its zero surface (`method`: "surface_nets" or
+        "marching_cubes", as in extract_surface), the vertices un-contracted and clipped to +-32, coloured by a second fusion
+        pass over the vertices."""
+        _check_method(method)
         grid, coords = self.tsdf_volume(resolution)
-        verts, faces = extract_surface(grid, coords, level=0.0)
+        verts, faces = extract_surface(grid, coords, level=0.0, method=method)
         voxel_size = self.radius * 2 / int(resolution)
         if verts.shape[0] == 0:
             return Mesh(verts, faces, torch.empty(0, 3, dtype=torch.float32, device=verts.device))
@@ -948,13 +1141,17 @@ class GaussianExtractor:
         return depth, rgb, E.contiguous(), K
 
     @torch.no_grad()
-    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True, stride=4):
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True, stride=4,
+                             method="surface_nets"):
         """mesh_utils.py:138-180 (the keyword spelling is the reference's): fuse the kept views into a sparse volume of 16^3
         blocks of `voxel_size` voxels, truncation sdf_trunc, depths above depth_trunc dropped, and mesh its zero surface.
         The volume follows the rules written down in include/scorp_gs.h, not Open3D's ScalableTSDFVolume, whose output was
-        never available to compare with; the surface is extracted by surface nets, not marching cubes."""
+        never available to compare with; the surface is extracted by surface nets unless method="marching_cubes" asks for
+        this project's marching cubes (scorp_amd/mc_table.py; its table was not compared with Open3D's either)."""
+        _check_method(method)
         depth, rgb, world_to_cam, intrinsics = self.bounded_views(depth_trunc, mask_backgrond)
-        return extract_surface_blocks(tsdf_blocks_fuse(depth, rgb, world_to_cam, intrinsics, voxel_size, sdf_trunc, stride=stride))
+        return extract_surface_blocks(tsdf_blocks_fuse(depth, rgb, world_to_cam, intrinsics, voxel_size, sdf_trunc, stride=stride),
+                                      method=method)
 
     @torch.no_grad()
     def export_image(self, path):
