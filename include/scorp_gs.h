@@ -427,6 +427,80 @@ int scorp_mesh_cluster_stats(const int32_t *faces, const float *vertices, int64_
                              const int32_t *root_scan, int64_t num_faces, int64_t num_clusters, int32_t *out_cluster,
                              int32_t *out_count, double *out_area, scorp_stream_t stream);
 
+/* ---- mesh simplification by vertex clustering (what Open3D's simplify_vertex_clustering does; the reference reduces its
+ * meshes through Open3D and TRELLIS post-processing) ----
+ * Open3D could not be run where this was written.  The rules below ARE the specification; nothing was compared with
+ * Open3D's own output.  Edge-collapse decimation to a target triangle count is not built.
+ *
+ * Inputs: vertices[Nv, 3] float32, finite; colors[Nv, 3] float32; faces[F, 3] int32 in [0, Nv); voxel_size h > 0 (a double);
+ * the placement, average (quadric = 0) or quadric.  All arithmetic below is float64 from the float32 values, every product,
+ * quotient and sum rounded on its own (no fp contraction), sums of three terms as (a + b) + c.
+ *
+ * 1. Cells.  min_bound[k] is the smallest coordinate k of all vertices (float32), origin[k] = double(min_bound[k]) - 0.5 h.
+ *    Vertex v lies in cell i[k] = floor((double(v[k]) - origin[k]) / h): one subtraction and one division.  Membership is an
+ *    exact integer function of the inputs; a vertex on a cell face belongs to the upper cell.  Every i[k] must be < 2^21
+ *    (cell key = i[0] << 42 | i[1] << 21 | i[2], 63 bits).  Every vertex takes part, whether a face references it or not.
+ * 2. Numbering.  Cells are numbered in ascending order of the smallest vertex index they contain; vertex_cell[v] is that
+ *    number, C the cell count, output vertex c belongs to cell c.
+ * 3. Colour and mean.  colour[c] and mean[c] are the sums of the members' colours / positions divided by the member count,
+ *    then rounded to float32.  With the average placement mean[c] is the output position.
+ * 4. Quadric placement.  p_c[k] = origin[k] + (i[k] + 0.5) h is the cell centre.  Every triangle (v0, v1, v2) with
+ *    N = (v1 - v0) x (v2 - v0), |N| = sqrt((Nx^2 + Ny^2) + Nz^2) > 0 has area a = 0.5 |N| and unit normal n = N / |N|.  For each
+ *    of its three corners, with that corner's cell c: d = -((nx (v0x - p_cx) + ny (v0y - p_cy)) + nz (v0z - p_cz)), then
+ *    A_c[j][k] += (a n[j]) n[k] for j <= k (six entries; A_c is symmetric) and b_c[k] += (a d) n[k].  One contribution per
+ *    corner: two corners in one cell add twice, there is no special case.  Zero-area triangles add nothing.
+ *    m = (the float64 mean before its rounding) - p_c; sigma_1 >= sigma_2 >= sigma_3 and u_i the eigenpairs of A_c;
+ *      x = m + sum over {i : sigma_i > 1e-3 sigma_1} of u_i (u_i . (-b_c - A_c m)) / sigma_i,
+ *    formed as r[k] = -b_c[k] - ((A_c[k][0] m[0] + A_c[k][1] m[1]) + A_c[k][2] m[2]), t_i = ((u_i[0] r[0] + u_i[1] r[1]) +
+ *    u_i[2] r[2]) / sigma_i, and x = m, then x += u_i t_i for i = 1, 2, 3 in turn.
+ *    If sigma_1 = 0, or some |x[k]| > h (the point has left the cell by more than half a cell), the output position is
+ *    mean[c] itself, bit for bit; otherwise it is float32(p_c + x).  A cell with ONE member keeps mean[c] as well, which is
+ *    that vertex: every triangle that adds to the cell has the vertex as a corner, so it lies on all their planes and is
+ *    the exact minimiser (r = 0); the solve would return it plus the rounding residue of r, some 1e-16 h, which is all there
+ *    is of a coordinate whose exact value is 0.  A mesh whose vertices all have cells of their own comes back unchanged.  On a flat cell the point is the mean projected onto the
+ *    plane, on a crease it slides to the crease, at a corner it lands on the corner.
+ * 5. Faces.  Each face is mapped through vertex_cell; a face with two equal cells is dropped; the rest are rotated
+ *    cyclically so that the smallest cell number comes first (the orientation stays).  Among faces that are then equal as
+ *    ORDERED triples only the one with the smallest input index is kept: (a, b, c) and (a, c, b) are different faces.
+ *    Survivors keep their input order.
+ * The integer outputs (vertex_cell, C, the faces and their keep flags) do not depend on the execution order: both hash
+ * tables resolve their slots by atomic min on an index.  Positions and colours come from float64 sums by atomic adds and
+ * depend on the order of arrival in their last bits: two calls need not agree there (the float32 results agree within one
+ * ulp wherever no decision of rule 4 sits on its threshold).
+ *
+ * The caller owns every buffer and the scans between the calls; scratch tables are filled by the call that uses them:
+ *   cells:      keys[num_slots] (uint64) and owner[num_slots] (int32) are scratch, num_slots a power of two >= 2 num_vertices
+ *               and <= 2^31; min_bound[3] is DEVICE memory (the stream stays asynchronous).  out_slot[v] = the slot of v's
+ *               cell.  A condition on device data cannot fail the call without a synchronisation: out_overflow (one int32,
+ *               device) is set to 0 by the call and to 1 when a cell index falls outside [0, 2^21) (or a coordinate is not
+ *               finite); that vertex gets slot -1 and the outputs of the later calls are then meaningless (never out of
+ *               bounds).  A caller that knows the bounds on the host checks the extent itself and reports SCORP_ERR_INVALID's
+ *               meaning there, as scorp_amd/mesh.py does.
+ *   roots:      out_rep[v] = the smallest vertex index of v's cell, out_is_root[v] = (out_rep[v] == v) as one byte.
+ *   accumulate: rep_scan[num_vertices] = the INCLUSIVE int32 prefix sum of the bytes, num_cells its last entry.
+ *               out_vertex_cell[v] = rep_scan[rep[v]] - 1; out_cell_ijk[num_cells, 3] (int32) the cells' indices;
+ *               out_acc[num_cells, 16] (float64, zeroed by the call): position sums 3, colour sums 3, member count, A_c as
+ *               xx xy xz yy yz zz, b_c 3 (the last nine stay 0 with quadric = 0, and faces may then be NULL).
+ *   place:      out_vertices[num_cells, 3], out_colors[num_cells, 3] by rules 3 and 4.
+ *   faces:      table[num_slots] (int32) is scratch, num_slots a power of two >= 2 num_faces and <= 2^31.
+ *               out_faces[num_faces, 3] = the rotated triples ((-1, -1, -1) for a face with two equal cells),
+ *               out_keep[num_faces] one byte per face; the caller scans the bytes and compacts.
+ * None synchronises.  SCORP_ERR_INVALID: a NULL pointer, num_vertices < 1 or > 2^30, num_faces < 1 or > 2^28, voxel_size not
+ * positive and finite, num_slots not a power of two, too small or > 2^31, num_cells outside [1, num_vertices]. */
+int scorp_mesh_simplify_cells(const float *vertices, int64_t num_vertices, const float *min_bound, double voxel_size,
+                              uint64_t *keys, int32_t *owner, uint64_t num_slots, int32_t *out_slot, int32_t *out_overflow,
+                              scorp_stream_t stream);
+int scorp_mesh_simplify_roots(const int32_t *owner, uint64_t num_slots, const int32_t *slot, int64_t num_vertices,
+                              int32_t *out_rep, uint8_t *out_is_root, scorp_stream_t stream);
+int scorp_mesh_simplify_accumulate(const float *vertices, const float *colors, int64_t num_vertices, const int32_t *faces,
+                                   int64_t num_faces, const float *min_bound, double voxel_size, const int32_t *rep,
+                                   const int32_t *rep_scan, int64_t num_cells, int32_t quadric, int32_t *out_vertex_cell,
+                                   int32_t *out_cell_ijk, double *out_acc, scorp_stream_t stream);
+int scorp_mesh_simplify_place(const double *acc, const int32_t *cell_ijk, int64_t num_cells, const float *min_bound,
+                              double voxel_size, int32_t quadric, float *out_vertices, float *out_colors, scorp_stream_t stream);
+int scorp_mesh_simplify_faces(const int32_t *faces, int64_t num_faces, const int32_t *vertex_cell, int64_t num_vertices,
+                              int32_t *table, uint64_t num_slots, int32_t *out_faces, uint8_t *out_keep, scorp_stream_t stream);
+
 /* ---- bounded TSDF volume: sparse 16^3-voxel blocks, fused and meshed (the route of gs2dgs/utils/mesh_utils.py:138-180
  * extract_mesh_bounded, which hands the work to Open3D's ScalableTSDFVolume) ----
  * Open3D's volume could be neither read nor run where this was written.  The rules below ARE the specification; nothing
