@@ -106,6 +106,17 @@ __device__ __forceinline__ float splat_exponent(float dx, float dy, float A, flo
   return __builtin_fmaf(__builtin_fmaf(A, dx, B * dy), dx, __builtin_fmaf(C * dy, dy, L));
 }
 
+// The 64-bit finaliser of MurmurHash3: every bit of the key reaches the low bits, which the open-addressing tables take their
+// slot from (tsdf_blocks.hip, mesh_cluster.hip, mesh_simplify.hip).
+__device__ __forceinline__ uint64_t mix64(uint64_t k) {
+  k ^= k >> 33;
+  k *= 0xFF51AFD7ED558CCDull;
+  k ^= k >> 33;
+  k *= 0xC4CEB9FE1A85EC53ull;
+  k ^= k >> 33;
+  return k;
+}
+
 // A float in the constant address space: uniform loads through such a pointer go to the scalar cache (s_load) instead of
 // occupying VMEM slots.  Only for data no kernel of the same launch writes (camera matrices).
 typedef __attribute__((address_space(4))) float CFloat;

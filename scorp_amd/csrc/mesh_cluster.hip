@@ -67,15 +67,6 @@ __device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b) {
   }
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t k) {   // (the 64-bit finaliser of MurmurHash3: both halves of the key reach the low bits)
-  k ^= k >> 33;
-  k *= 0xFF51AFD7ED558CCDull;
-  k ^= k >> 33;
-  k *= 0xC4CEB9FE1A85EC53ull;
-  k ^= k >> 33;
-  return k;
-}
-
 __global__ void __launch_bounds__(kClusterThreads) cluster_init_kernel(uint64_t *__restrict__ keys, int32_t *__restrict__ owner,
                                                                        uint64_t slots, int32_t *__restrict__ parent, int32_t faces) {
   const uint64_t i = (uint64_t)blockIdx.x * kClusterThreads + threadIdx.x;

@@ -32,15 +32,6 @@ constexpr int32_t kEmptyOwner = 0x7FFFFFFF;     // above every vertex and face i
 constexpr int32_t kCellSide = 1 << 21;          // cell indices per axis
 constexpr int kAcc = 16;                        // doubles per cell: position 3, colour 3, count, A 6 (xx xy xz yy yz zz), b 3
 
-__device__ __forceinline__ uint64_t mix64(uint64_t k) {   // (the 64-bit finaliser of MurmurHash3, as in mesh_cluster.hip)
-  k ^= k >> 33;
-  k *= 0xFF51AFD7ED558CCDull;
-  k ^= k >> 33;
-  k *= 0xC4CEB9FE1A85EC53ull;
-  k ^= k >> 33;
-  return k;
-}
-
 // The grid: origin = double(min_bound) - 0.5 h per axis; cell index floor((double(x) - origin) / h), one subtraction and one
 // division, each rounded on its own.
 struct Grid {

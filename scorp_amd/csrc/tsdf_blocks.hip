@@ -20,16 +20,12 @@
 //              block-uniform (scalar), a voxel's tsdf / w / colour stay in registers over all views and are stored once.
 // No LDS, no scratch.  The arithmetic is compiled without fp contraction: every product and sum rounds on its own, as the
 // numpy float32 restatement rounds.
-#include "common.hpp"
+#include "lattice.hpp"
 
 namespace scorp {
 namespace {
 
-constexpr int kBlkThreads = 256;
-constexpr int kBlkSide = 16, kBlkVoxels = 4096;
-constexpr int32_t kBlkBias = 1 << 20;               // block coordinates lie in [-2^20, 2^20)
-constexpr uint64_t kBlkEmpty = ~(uint64_t)0;        // no block has it: a key is below 2^63
-constexpr int64_t kBlkMaxBlocks = 0x7FFFFFFF / 16;  // 16 workgroups per block in the per-voxel launches
+constexpr uint64_t kBlkEmpty = ~(uint64_t)0;   // no block has it: a key is below 2^63
 
 struct BlkViews {
   const float *depth;
@@ -37,25 +33,6 @@ struct BlkViews {
   const float *cam;   // [V, 16]: E row-major (12), fx, fy, cx, cy
   int V, W, H;
 };
-
-__device__ __forceinline__ uint64_t blk_mix64(uint64_t k) {   // (the 64-bit finaliser of MurmurHash3, as in mesh_cluster.hip)
-  k ^= k >> 33;
-  k *= 0xFF51AFD7ED558CCDull;
-  k ^= k >> 33;
-  k *= 0xC4CEB9FE1A85EC53ull;
-  k ^= k >> 33;
-  return k;
-}
-
-__device__ __forceinline__ uint64_t blk_key(int32_t bx, int32_t by, int32_t bz) {
-  return (uint64_t)(uint32_t)(bx + kBlkBias) << 42 | (uint64_t)(uint32_t)(by + kBlkBias) << 21 | (uint64_t)(uint32_t)(bz + kBlkBias);
-}
-
-__device__ __forceinline__ void blk_coords(uint64_t key, int32_t &bx, int32_t &by, int32_t &bz) {
-  bx = (int32_t)((key >> 42) & 0x1FFFFFu) - kBlkBias;
-  by = (int32_t)((key >> 21) & 0x1FFFFFu) - kBlkBias;
-  bz = (int32_t)(key & 0x1FFFFFu) - kBlkBias;
-}
 
 __global__ void __launch_bounds__(kBlkThreads) blocks_clear_kernel(uint64_t *__restrict__ keys, uint32_t *__restrict__ view_mask,
                                                                    uint64_t slots, uint64_t mask_words, uint32_t *__restrict__ overflow) {
@@ -102,7 +79,7 @@ __global__ void __launch_bounds__(kBlkThreads) blocks_touch_kernel(const BlkView
         // look every later insert of an absent key would walk all num_slots slots before giving up.
         if (__hip_atomic_load(overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u) return;
         const uint64_t key = blk_key(bx, by, bz);
-        uint64_t slot = blk_mix64(key) & slot_mask;
+        uint64_t slot = mix64(key) & slot_mask;
         bool done = false;
         for (uint64_t probe = 0; probe <= slot_mask; probe++) {
           uint64_t cur = __hip_atomic_load(keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -223,7 +200,7 @@ extern "C" int scorp_tsdf_blocks_touch(const ScorpTsdfBlockViews *views, float v
                                        uint64_t *keys, uint32_t *view_mask, uint64_t num_slots, uint32_t *overflow,
                                        scorp_stream_t stream) {
   if (int e = check_block_views(views, "tsdf_blocks_touch")) return e;
-  if (!keys || !view_mask || !overflow) { set_error("tsdf_blocks_touch: NULL argument"); return SCORP_ERR_INVALID; }
+  if (int e = check_not_null({keys, view_mask, overflow}, "tsdf_blocks_touch", "argument")) return e;
   if (stride < 1) { set_error("tsdf_blocks_touch: stride < 1"); return SCORP_ERR_INVALID; }
   if (int e = check_block_lengths(voxel_length, sdf_trunc, "tsdf_blocks_touch")) return e;
   if (num_slots == 0 || (num_slots & (num_slots - 1)) != 0 || num_slots > ((uint64_t)1 << 32)) {
@@ -246,8 +223,8 @@ extern "C" int scorp_tsdf_blocks_touch(const ScorpTsdfBlockViews *views, float v
 }
 
 extern "C" int scorp_tsdf_blocks_neighbors(const uint64_t *block_keys, int64_t num_blocks, int32_t *out_nbr, scorp_stream_t stream) {
-  if (!block_keys || !out_nbr) { set_error("tsdf_blocks_neighbors: NULL argument"); return SCORP_ERR_INVALID; }
-  if (num_blocks < 1 || num_blocks > kBlkMaxBlocks) { set_error("tsdf_blocks_neighbors: num_blocks must be in [1, (2^31 - 1) / 16]"); return SCORP_ERR_INVALID; }
+  if (int e = check_not_null({block_keys, out_nbr}, "tsdf_blocks_neighbors", "argument")) return e;
+  if (int e = check_num_blocks(num_blocks, "tsdf_blocks_neighbors")) return e;
   hipStream_t s = (hipStream_t)stream;
   blocks_neighbors_kernel<<<blk_grid((uint64_t)num_blocks * 27), kBlkThreads, 0, s>>>(block_keys, (int32_t)num_blocks, out_nbr);
   SCORP_KERNEL_CHECK("blocks_neighbors", 0, s);
@@ -258,10 +235,10 @@ extern "C" int scorp_tsdf_blocks_integrate(const ScorpTsdfBlockViews *views, flo
                                            const uint64_t *block_keys, const uint32_t *view_mask, int64_t num_blocks,
                                            float *out_tsdf, float *out_weight, float *out_colour, scorp_stream_t stream) {
   if (int e = check_block_views(views, "tsdf_blocks_integrate")) return e;
-  if (!block_keys || !view_mask || !out_tsdf || !out_weight) { set_error("tsdf_blocks_integrate: NULL argument"); return SCORP_ERR_INVALID; }
+  if (int e = check_not_null({block_keys, view_mask, out_tsdf, out_weight}, "tsdf_blocks_integrate", "argument")) return e;
   if (out_colour && !views->rgb) { set_error("tsdf_blocks_integrate: out_colour without views->rgb"); return SCORP_ERR_INVALID; }
   if (int e = check_block_lengths(voxel_length, sdf_trunc, "tsdf_blocks_integrate")) return e;
-  if (num_blocks < 1 || num_blocks > kBlkMaxBlocks) { set_error("tsdf_blocks_integrate: num_blocks must be in [1, (2^31 - 1) / 16]"); return SCORP_ERR_INVALID; }
+  if (int e = check_num_blocks(num_blocks, "tsdf_blocks_integrate")) return e;
   BlkViews a{views->depth, views->rgb, views->cam, views->num_views, views->width, views->height};
   const int words = (views->num_views + 31) / 32;
   const float u_max = (float)views->width - 1e-4f, v_max = (float)views->height - 1e-4f;

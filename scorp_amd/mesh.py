@@ -304,6 +304,16 @@ def _marching_cubes_numpy(f, coords, level):
     return verts, _mc_faces_numpy(case, np.ones(case.shape, bool), vid, mc_table.cached_table())
 
 
+def _scan_counts(counts, limit, what):
+    """The inclusive prefix sums of the count bytes a count kernel wrote, and their total n (one host read): (n, the scan as
+    int32, or None when n == 0).  n >= limit does not fit the mesh's int32 indices."""
+    scan = torch.cumsum(counts, 0, dtype=torch.int64)
+    n = int(scan[-1])
+    if n >= limit:
+        raise ValueError(f"the surface has more than 2^31 - 1 {what}")
+    return n, (scan.to(torch.int32) if n else None)
+
+
 def _marching_cubes_gpu(f, xyz, level):
     L = _C.lib()
     dev = f.device
@@ -316,29 +326,49 @@ def _marching_cubes_gpu(f, xyz, level):
         counts = torch.empty(X * Y * Z, dtype=torch.uint8, device=dev)
         _C.check(L.scorp_marching_cubes_count_edges(f.data_ptr(), X, Y, Z, level, masks.data_ptr(), counts.data_ptr(), stream),
                  "scorp_marching_cubes_count_edges")
-        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64)
-        nv = int(edge_scan[-1])
-        if nv >= 2 ** 31:
-            raise ValueError("the surface has more than 2^31 - 1 vertices")
+        nv, edge_scan = _scan_counts(counts, 2 ** 31, "vertices")
         if nv == 0:
             return verts, faces
-        edge_scan = edge_scan.to(torch.int32)
         verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
         _C.check(L.scorp_marching_cubes_emit_vertices(f.data_ptr(), xyz[0].data_ptr(), xyz[1].data_ptr(), xyz[2].data_ptr(), X, Y, Z,
                                                       level, masks.data_ptr(), edge_scan.data_ptr(), nv, verts.data_ptr(), stream),
                  "scorp_marching_cubes_emit_vertices")
         counts = torch.empty((X - 1) * (Y - 1) * (Z - 1), dtype=torch.uint8, device=dev)
         _C.check(L.scorp_marching_cubes_count_faces(f.data_ptr(), X, Y, Z, level, counts.data_ptr(), stream), "scorp_marching_cubes_count_faces")
-        face_scan = torch.cumsum(counts, 0, dtype=torch.int64)
-        nf = int(face_scan[-1])
-        if nf >= 2 ** 31:
-            raise ValueError("the surface has more than 2^31 - 1 triangles")
+        nf, face_scan = _scan_counts(counts, 2 ** 31, "triangles")
         if nf == 0:
             return verts, faces
-        face_scan = face_scan.to(torch.int32)
         faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
         _C.check(L.scorp_marching_cubes_emit_faces(f.data_ptr(), X, Y, Z, level, masks.data_ptr(), edge_scan.data_ptr(),
                                                    face_scan.data_ptr(), nf, faces.data_ptr(), stream), "scorp_marching_cubes_emit_faces")
+    return verts, faces
+
+
+def _surface_nets_gpu(f, xyz, level):
+    L = _C.lib()
+    dev = f.device
+    X, Y, Z = f.shape
+    verts = torch.empty(0, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(0, 3, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = _C.current_stream_ptr()
+        flags = torch.empty((X - 1) * (Y - 1) * (Z - 1), dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_isosurface_count_cells(f.data_ptr(), X, Y, Z, level, flags.data_ptr(), stream), "scorp_isosurface_count_cells")
+        nv, cell_scan = _scan_counts(flags, 2 ** 31, "vertices")
+        if nv == 0:
+            return verts, faces
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        _C.check(L.scorp_isosurface_emit_vertices(f.data_ptr(), xyz[0].data_ptr(), xyz[1].data_ptr(), xyz[2].data_ptr(), X, Y, Z,
+                                                  level, cell_scan.data_ptr(), nv, verts.data_ptr(), stream),
+                 "scorp_isosurface_emit_vertices")
+        counts = torch.empty(X * Y * Z, dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_isosurface_count_faces(f.data_ptr(), X, Y, Z, level, counts.data_ptr(), stream), "scorp_isosurface_count_faces")
+        nq, edge_scan = _scan_counts(counts, 2 ** 30, "triangles")   # (two triangles per quad)
+        if nq == 0:
+            return verts, faces
+        faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
+        _C.check(L.scorp_isosurface_emit_faces(f.data_ptr(), X, Y, Z, level, cell_scan.data_ptr(), edge_scan.data_ptr(), nq,
+                                               faces.data_ptr(), stream), "scorp_isosurface_emit_faces")
     return verts, faces
 
 
@@ -362,41 +392,8 @@ def extract_surface(grid, coords, level=0.0, method="surface_nets"):
         form = _marching_cubes_numpy if method == "marching_cubes" else _surface_nets_numpy
         v, t = form(f.numpy(), [c.numpy() for c in xyz], level)
         return torch.from_numpy(v), torch.from_numpy(t)
-    if method == "marching_cubes":
-        return _marching_cubes_gpu(f, xyz, float(level))
-    L = _C.lib()
-    X, Y, Z = f.shape
-    level = float(level)
-    verts = torch.empty(0, 3, dtype=torch.float32, device=dev)
-    faces = torch.empty(0, 3, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = _C.current_stream_ptr()
-        flags = torch.empty((X - 1) * (Y - 1) * (Z - 1), dtype=torch.uint8, device=dev)
-        _C.check(L.scorp_isosurface_count_cells(f.data_ptr(), X, Y, Z, level, flags.data_ptr(), stream), "scorp_isosurface_count_cells")
-        cell_scan = torch.cumsum(flags, 0, dtype=torch.int64)
-        nv = int(cell_scan[-1])
-        if nv >= 2 ** 31:
-            raise ValueError("the surface has more than 2^31 - 1 vertices")
-        if nv == 0:
-            return verts, faces
-        cell_scan = cell_scan.to(torch.int32)
-        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-        _C.check(L.scorp_isosurface_emit_vertices(f.data_ptr(), xyz[0].data_ptr(), xyz[1].data_ptr(), xyz[2].data_ptr(), X, Y, Z,
-                                                  level, cell_scan.data_ptr(), nv, verts.data_ptr(), stream),
-                 "scorp_isosurface_emit_vertices")
-        counts = torch.empty(X * Y * Z, dtype=torch.uint8, device=dev)
-        _C.check(L.scorp_isosurface_count_faces(f.data_ptr(), X, Y, Z, level, counts.data_ptr(), stream), "scorp_isosurface_count_faces")
-        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64)
-        nq = int(edge_scan[-1])
-        if nq >= 2 ** 30:
-            raise ValueError("the surface has more than 2^31 - 1 triangles")
-        if nq == 0:
-            return verts, faces
-        edge_scan = edge_scan.to(torch.int32)
-        faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
-        _C.check(L.scorp_isosurface_emit_faces(f.data_ptr(), X, Y, Z, level, cell_scan.data_ptr(), edge_scan.data_ptr(), nq,
-                                               faces.data_ptr(), stream), "scorp_isosurface_emit_faces")
-    return verts, faces
+    form = _marching_cubes_gpu if method == "marching_cubes" else _surface_nets_gpu
+    return form(f, xyz, float(level))
 
 
 # ---- bounded TSDF volume: sparse 16^3-voxel blocks (the rules are in include/scorp_gs.h) ----
@@ -467,6 +464,11 @@ def _check_lengths(voxel_length, sdf_trunc, stride):
     return voxel_length, sdf_trunc, stride
 
 
+def _block_coords_numpy(keys):
+    """block_coords on a numpy array of keys, in int64."""
+    return np.stack([((keys >> s) & 0x1FFFFF) - KEY_BIAS for s in (42, 21, 0)], -1)
+
+
 def _pack_keys_numpy(b):
     b = b.astype(np.int64) + KEY_BIAS
     return b[..., 0] << 42 | b[..., 1] << 21 | b[..., 2]
@@ -510,7 +512,7 @@ def _blocks_integrate_numpy(depth, rgb, cam, keys, mask, voxel_length, sdf_trunc
     V, H, W = depth.shape
     B = keys.size
     vl, trunc = f(voxel_length), f(sdf_trunc)
-    coords = np.stack([((keys >> s) & 0x1FFFFF) - KEY_BIAS for s in (42, 21, 0)], -1)
+    coords = _block_coords_numpy(keys)
     local = np.stack(np.unravel_index(np.arange(BLOCK_VOXELS), (16, 16, 16)), -1)
     tsdf, w = np.zeros(B * BLOCK_VOXELS, f), np.zeros(B * BLOCK_VOXELS, f)
     col = np.zeros((B * BLOCK_VOXELS, 3), f) if rgb is not None else None
@@ -618,7 +620,7 @@ def block_neighbors(keys):
                          "scorp_tsdf_blocks_neighbors")
         return nbr
     k = keys.numpy()
-    coords = np.stack([((k >> s) & 0x1FFFFF) - KEY_BIAS for s in (42, 21, 0)], -1)
+    coords = _block_coords_numpy(k)
     nbr = np.full((B, 27), -1, np.int32)
     for n, o in enumerate(np.ndindex(3, 3, 3)):
         c = coords + (np.asarray(o) - 1)
@@ -653,7 +655,7 @@ def _surface_blocks_numpy(keys, nbr, tsdf, weight, colour, voxel_length):
     """The surface rule of include/scorp_gs.h in vectorised numpy float32: (vertices, faces, colours or None)."""
     f = np.float32
     B = keys.size
-    coords = np.stack([((keys >> s) & 0x1FFFFF) - KEY_BIAS for s in (42, 21, 0)], -1)
+    coords = _block_coords_numpy(keys)
     nbr = nbr.copy()
     nbr[:, 13] = np.arange(B)
     shape = (B, 16, 16, 16)
@@ -722,7 +724,7 @@ def _marching_cubes_blocks_numpy(keys, nbr, tsdf, weight, colour, voxel_length):
     """The marching-cubes surface rule of include/scorp_gs.h in vectorised numpy float32: (vertices, faces, colours or None)."""
     f = np.float32
     B = keys.size
-    coords = np.stack([((keys >> s) & 0x1FFFFF) - KEY_BIAS for s in (42, 21, 0)], -1)
+    coords = _block_coords_numpy(keys)
     nbr = nbr.copy()
     nbr[:, 13] = np.arange(B)
     shape = (B, 16, 16, 16)
@@ -775,13 +777,9 @@ def _marching_cubes_blocks_gpu(keys, nbr, tsdf, weight, colour, voxel_length, em
         counts = torch.empty(B * BLOCK_VOXELS, dtype=torch.uint8, device=dev)
         _C.check(L.scorp_marching_cubes_blocks_count_edges(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, masks.data_ptr(),
                                                            counts.data_ptr(), stream), "scorp_marching_cubes_blocks_count_edges")
-        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64)
-        nv = int(edge_scan[-1])
-        if nv >= 2 ** 31:
-            raise ValueError("the surface has more than 2^31 - 1 vertices")
+        nv, edge_scan = _scan_counts(counts, 2 ** 31, "vertices")
         if nv == 0:
             return empty
-        edge_scan = edge_scan.to(torch.int32)
         verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
         cols = torch.empty(nv, 3, dtype=torch.float32, device=dev) if colour is not None else None
         _C.check(L.scorp_marching_cubes_blocks_emit_vertices(tsdf.data_ptr(), weight.data_ptr(),
@@ -793,16 +791,44 @@ def _marching_cubes_blocks_gpu(keys, nbr, tsdf, weight, colour, voxel_length, em
             cols = torch.zeros(nv, 3, dtype=torch.float32, device=dev)
         _C.check(L.scorp_marching_cubes_blocks_count_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, counts.data_ptr(), stream),
                  "scorp_marching_cubes_blocks_count_faces")
-        face_scan = torch.cumsum(counts, 0, dtype=torch.int64)
-        nf = int(face_scan[-1])
-        if nf >= 2 ** 31:
-            raise ValueError("the surface has more than 2^31 - 1 triangles")
+        nf, face_scan = _scan_counts(counts, 2 ** 31, "triangles")
         faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
         if nf:
-            face_scan = face_scan.to(torch.int32)
             _C.check(L.scorp_marching_cubes_blocks_emit_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, masks.data_ptr(),
                                                               edge_scan.data_ptr(), face_scan.data_ptr(), nf, faces.data_ptr(), stream),
                      "scorp_marching_cubes_blocks_emit_faces")
+    return Mesh(verts, faces, cols)
+
+
+def _surface_nets_blocks_gpu(keys, nbr, tsdf, weight, colour, voxel_length, empty):
+    L = _C.lib()
+    dev = tsdf.device
+    B = keys.numel()
+    with torch.cuda.device(dev):
+        stream = _C.current_stream_ptr()
+        flags = torch.empty(B * BLOCK_VOXELS, dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_isosurface_blocks_count_cells(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, flags.data_ptr(), stream),
+                 "scorp_isosurface_blocks_count_cells")
+        nv, cell_scan = _scan_counts(flags, 2 ** 31, "vertices")
+        if nv == 0:
+            return empty
+        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        cols = torch.empty(nv, 3, dtype=torch.float32, device=dev) if colour is not None else None
+        _C.check(L.scorp_isosurface_blocks_emit_vertices(tsdf.data_ptr(), weight.data_ptr(), colour.data_ptr() if colour is not None else None,
+                                                         keys.data_ptr(), nbr.data_ptr(), B, voxel_length, cell_scan.data_ptr(), nv,
+                                                         verts.data_ptr(), cols.data_ptr() if cols is not None else None, stream),
+                 "scorp_isosurface_blocks_emit_vertices")
+        if cols is None:
+            cols = torch.zeros(nv, 3, dtype=torch.float32, device=dev)
+        counts = torch.empty(B * BLOCK_VOXELS, dtype=torch.uint8, device=dev)
+        _C.check(L.scorp_isosurface_blocks_count_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, counts.data_ptr(), stream),
+                 "scorp_isosurface_blocks_count_faces")
+        nq, edge_scan = _scan_counts(counts, 2 ** 30, "triangles")   # (two triangles per quad)
+        faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
+        if nq:
+            _C.check(L.scorp_isosurface_blocks_emit_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, cell_scan.data_ptr(),
+                                                          edge_scan.data_ptr(), nq, faces.data_ptr(), stream),
+                     "scorp_isosurface_blocks_emit_faces")
     return Mesh(verts, faces, cols)
 
 
@@ -832,43 +858,8 @@ def extract_surface_blocks(volume, method="surface_nets"):
         form = _marching_cubes_blocks_numpy if method == "marching_cubes" else _surface_blocks_numpy
         v, t, c = form(keys.numpy(), nbr.numpy(), tsdf.numpy(), weight.numpy(), colour.numpy() if colour is not None else None, voxel_length)
         return Mesh(torch.from_numpy(v), torch.from_numpy(t), torch.from_numpy(c) if c is not None else torch.zeros(v.shape[0], 3))
-    if method == "marching_cubes":
-        return _marching_cubes_blocks_gpu(keys, nbr, tsdf, weight, colour, voxel_length, empty)
-    L = _C.lib()
-    with torch.cuda.device(dev):
-        stream = _C.current_stream_ptr()
-        flags = torch.empty(B * BLOCK_VOXELS, dtype=torch.uint8, device=dev)
-        _C.check(L.scorp_isosurface_blocks_count_cells(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, flags.data_ptr(), stream),
-                 "scorp_isosurface_blocks_count_cells")
-        cell_scan = torch.cumsum(flags, 0, dtype=torch.int64)
-        nv = int(cell_scan[-1])
-        if nv >= 2 ** 31:
-            raise ValueError("the surface has more than 2^31 - 1 vertices")
-        if nv == 0:
-            return empty
-        cell_scan = cell_scan.to(torch.int32)
-        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-        cols = torch.empty(nv, 3, dtype=torch.float32, device=dev) if colour is not None else None
-        _C.check(L.scorp_isosurface_blocks_emit_vertices(tsdf.data_ptr(), weight.data_ptr(), colour.data_ptr() if colour is not None else None,
-                                                         keys.data_ptr(), nbr.data_ptr(), B, voxel_length, cell_scan.data_ptr(), nv,
-                                                         verts.data_ptr(), cols.data_ptr() if cols is not None else None, stream),
-                 "scorp_isosurface_blocks_emit_vertices")
-        if cols is None:
-            cols = torch.zeros(nv, 3, dtype=torch.float32, device=dev)
-        counts = torch.empty(B * BLOCK_VOXELS, dtype=torch.uint8, device=dev)
-        _C.check(L.scorp_isosurface_blocks_count_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, counts.data_ptr(), stream),
-                 "scorp_isosurface_blocks_count_faces")
-        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64)
-        nq = int(edge_scan[-1])
-        if nq >= 2 ** 30:
-            raise ValueError("the surface has more than 2^31 - 1 triangles")
-        faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
-        if nq:
-            edge_scan = edge_scan.to(torch.int32)
-            _C.check(L.scorp_isosurface_blocks_emit_faces(tsdf.data_ptr(), weight.data_ptr(), nbr.data_ptr(), B, cell_scan.data_ptr(),
-                                                          edge_scan.data_ptr(), nq, faces.data_ptr(), stream),
-                     "scorp_isosurface_blocks_emit_faces")
-    return Mesh(verts, faces, cols)
+    form = _marching_cubes_blocks_gpu if method == "marching_cubes" else _surface_nets_blocks_gpu
+    return form(keys, nbr, tsdf, weight, colour, voxel_length, empty)
 
 
 # ---- triangle clustering and floater removal ----

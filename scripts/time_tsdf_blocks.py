@@ -1,7 +1,8 @@
 """Time the bounded TSDF route (scorp_amd.mesh.tsdf_blocks_fuse / extract_surface_blocks, csrc/tsdf_blocks.hip and
-csrc/isosurface_blocks.hip) at a working size: scripts/time_tsdf.py's scene (a unit sphere over a ground plane, ray-cast; ring
-cameras), 32 views at 1600 x 1200, a voxel size that gives tens of thousands of blocks.  Timed, each as the median of --reps
-runs after a warm-up with a hipEvent pair round the call:
+csrc/isosurface_blocks.hip or, with --method marching_cubes, csrc/marching_cubes_blocks.hip) at a working size:
+scripts/time_tsdf.py's scene (a unit sphere over a ground plane, ray-cast; ring cameras), 32 views at 1600 x 1200, a voxel size
+that gives tens of thousands of blocks.  Timed, each as the median of --reps runs after a warm-up with a hipEvent pair round
+the call:
   (a) every C-ABI call on its own: touch (with its table clear), neighbors, integrate, the four surface calls;
   (b) tsdf_blocks_fuse and extract_surface_blocks as the Python layer runs them (compaction, scans and the host reads of the
       counts included), and the two together: what extract_mesh_bounded costs after its maps exist;
@@ -65,6 +66,7 @@ def main():
     ap.add_argument("--width", type=int, default=1600)
     ap.add_argument("--height", type=int, default=1200)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--method", choices=("surface_nets", "marching_cubes"), default="surface_nets")
     ap.add_argument("--skip-restatement", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -99,13 +101,15 @@ def main():
             ts.append(e0.elapsed_time(e1))
         return {"ms": float(np.median(ts)), "ms_all": [round(t, 3) for t in ts]}, out
 
-    out = {"views": a.views, "width": a.width, "height": a.height, "voxel_size": vl, "sdf_trunc": trunc, "stride": a.stride}
+    mc = a.method == "marching_cubes"
+    out = {"method": a.method} if mc else {}   # (the default's record keeps the keys it always had)
+    out.update({"views": a.views, "width": a.width, "height": a.height, "voxel_size": vl, "sdf_trunc": trunc, "stride": a.stride})
     out["tsdf_blocks_fuse"], vol = timed(lambda: M.tsdf_blocks_fuse(depth, rgb, E, K, vl, trunc, stride=a.stride))
     B = vol.keys.numel()
     out["blocks"], out["observed_share"] = B, float((vol.weight > 0).float().mean())
-    out["extract_surface_blocks"], mesh = timed(lambda: M.extract_surface_blocks(vol))
+    out["extract_surface_blocks"], mesh = timed(lambda: M.extract_surface_blocks(vol, method=a.method))
     out["vertices"], out["faces"] = mesh.vertices.shape[0], mesh.faces.shape[0]
-    out["fuse_and_extract"], _ = timed(lambda: M.extract_surface_blocks(M.tsdf_blocks_fuse(depth, rgb, E, K, vl, trunc, stride=a.stride)))
+    out["fuse_and_extract"], _ = timed(lambda: M.extract_surface_blocks(M.tsdf_blocks_fuse(depth, rgb, E, K, vl, trunc, stride=a.stride), method=a.method))
 
     # (a) the calls on their own, on buffers sized once
     L, stream = _C.lib(), _C.current_stream_ptr()
@@ -128,25 +132,44 @@ def main():
     out["integrate"]["voxel_views_per_s"] = float(vol.weight.sum()) / (out["integrate"]["ms"] * 1e-3)
     out["integrate_without_colour"], _ = timed(lambda: _C.check(L.scorp_tsdf_blocks_integrate(
         ctypes.byref(views), vl, trunc, vol.keys.data_ptr(), vol.view_mask.data_ptr(), B, t.data_ptr(), w.data_ptr(), None, stream), "integrate"))
+    vp = (vol.tsdf.data_ptr(), vol.weight.data_ptr(), nbr.data_ptr(), B)   # what every surface call starts with
     flags = torch.empty(B * 4096, dtype=torch.uint8, device=dev)
-    out["count_cells"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_count_cells(vol.tsdf.data_ptr(), vol.weight.data_ptr(), nbr.data_ptr(), B,
-                                                                                        flags.data_ptr(), stream), "count_cells"))
-    cell_scan = torch.cumsum(flags, 0, dtype=torch.int64).to(torch.int32)
-    nv = int(cell_scan[-1])
-    verts, cols = torch.empty(nv, 3, device=dev), torch.empty(nv, 3, device=dev)
-    out["emit_vertices"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_emit_vertices(
-        vol.tsdf.data_ptr(), vol.weight.data_ptr(), vol.colour.data_ptr(), vol.keys.data_ptr(), nbr.data_ptr(), B, vl, cell_scan.data_ptr(), nv,
-        verts.data_ptr(), cols.data_ptr(), stream), "emit_vertices"))
     counts = torch.empty(B * 4096, dtype=torch.uint8, device=dev)
-    out["count_faces"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_count_faces(vol.tsdf.data_ptr(), vol.weight.data_ptr(), nbr.data_ptr(), B,
-                                                                                        counts.data_ptr(), stream), "count_faces"))
-    edge_scan = torch.cumsum(counts, 0, dtype=torch.int64).to(torch.int32)
-    nq = int(edge_scan[-1])
-    faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
-    out["emit_faces"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_emit_faces(vol.tsdf.data_ptr(), vol.weight.data_ptr(), nbr.data_ptr(), B,
-                                                                                      cell_scan.data_ptr(), edge_scan.data_ptr(), nq, faces.data_ptr(),
-                                                                                      stream), "emit_faces"))
-    out["scans"], _ = timed(lambda: (torch.cumsum(flags, 0, dtype=torch.int64).to(torch.int32), torch.cumsum(counts, 0, dtype=torch.int64).to(torch.int32)))
+    verts_of = lambda n: (torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev))
+    if mc:   # count_edges / emit_vertices / count_faces / emit_faces; flags = the edge masks, first_scan = the edge scan
+        edge_counts = torch.empty(B * 4096, dtype=torch.uint8, device=dev)
+        out["count_edges"], _ = timed(lambda: _C.check(L.scorp_marching_cubes_blocks_count_edges(*vp, flags.data_ptr(), edge_counts.data_ptr(), stream),
+                                                       "count_edges"))
+        first_scan = torch.cumsum(edge_counts, 0, dtype=torch.int64).to(torch.int32)
+        nv = int(first_scan[-1])
+        verts, cols = verts_of(nv)
+        out["emit_vertices"], _ = timed(lambda: _C.check(L.scorp_marching_cubes_blocks_emit_vertices(
+            vol.tsdf.data_ptr(), vol.weight.data_ptr(), vol.colour.data_ptr(), vol.keys.data_ptr(), nbr.data_ptr(), B, vl, flags.data_ptr(),
+            first_scan.data_ptr(), nv, verts.data_ptr(), cols.data_ptr(), stream), "emit_vertices"))
+        out["count_faces"], _ = timed(lambda: _C.check(L.scorp_marching_cubes_blocks_count_faces(*vp, counts.data_ptr(), stream), "count_faces"))
+        face_scan = torch.cumsum(counts, 0, dtype=torch.int64).to(torch.int32)
+        nf = int(face_scan[-1])
+        faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+        out["emit_faces"], _ = timed(lambda: _C.check(L.scorp_marching_cubes_blocks_emit_faces(
+            *vp, flags.data_ptr(), first_scan.data_ptr(), face_scan.data_ptr(), nf, faces.data_ptr(), stream), "emit_faces"))
+        first_counts = edge_counts
+    else:
+        out["count_cells"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_count_cells(*vp, flags.data_ptr(), stream), "count_cells"))
+        cell_scan = torch.cumsum(flags, 0, dtype=torch.int64).to(torch.int32)
+        nv = int(cell_scan[-1])
+        verts, cols = verts_of(nv)
+        out["emit_vertices"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_emit_vertices(
+            vol.tsdf.data_ptr(), vol.weight.data_ptr(), vol.colour.data_ptr(), vol.keys.data_ptr(), nbr.data_ptr(), B, vl, cell_scan.data_ptr(), nv,
+            verts.data_ptr(), cols.data_ptr(), stream), "emit_vertices"))
+        out["count_faces"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_count_faces(*vp, counts.data_ptr(), stream), "count_faces"))
+        edge_scan = torch.cumsum(counts, 0, dtype=torch.int64).to(torch.int32)
+        nq = int(edge_scan[-1])
+        faces = torch.empty(2 * nq, 3, dtype=torch.int32, device=dev)
+        out["emit_faces"], _ = timed(lambda: _C.check(L.scorp_isosurface_blocks_emit_faces(
+            *vp, cell_scan.data_ptr(), edge_scan.data_ptr(), nq, faces.data_ptr(), stream), "emit_faces"))
+        first_counts = flags
+    out["scans"], _ = timed(lambda: (torch.cumsum(first_counts, 0, dtype=torch.int64).to(torch.int32),
+                                     torch.cumsum(counts, 0, dtype=torch.int64).to(torch.int32)))
     if not a.skip_restatement:
         out["integrate_torch_ops"], (t_ref, w_ref, c_ref) = timed(lambda: integrate_torch(d32, rgb, cam, vol.keys, vol.view_mask, vl, trunc))
         out["weights_differing_kernel_vs_torch_ops"] = int((w_ref != vol.weight).sum())

@@ -69,3 +69,20 @@ def test_extract_surface_argument_errors():
         extract_surface(torch.zeros(4, 4, 5), c)
     with pytest.raises(ValueError, match="at least 2"):
         extract_surface(torch.zeros(4, 4, 1), [c[0], c[1], torch.zeros(1)])
+
+
+def test_scan_counts_totals_scans_and_limits():
+    """_scan_counts, the step between every count and emit call of the four GPU drivers, on CPU tensors."""
+    from scorp_amd.mesh import _scan_counts
+    assert _scan_counts(torch.zeros(37, dtype=torch.uint8), 2 ** 31, "vertices") == (0, None)
+    counts = torch.from_numpy(np.random.default_rng(5).integers(0, 6, 1000).astype(np.uint8))   # sums far above 255
+    total = int(counts.numpy().astype(np.int64).sum())
+    assert total > 255
+    n, scan = _scan_counts(counts, 2 ** 31, "triangles")
+    assert n == total and scan.dtype == torch.int32
+    assert np.array_equal(scan.numpy(), np.cumsum(counts.numpy(), dtype=np.int64))
+    assert _scan_counts(counts, total + 1, "vertices")[0] == total
+    for what in ("vertices", "triangles"):
+        for limit in (total, total - 1):
+            with pytest.raises(ValueError, match=rf"^the surface has more than 2\^31 - 1 {what}$"):
+                _scan_counts(counts, limit, what)
