@@ -430,7 +430,7 @@ int scorp_mesh_cluster_stats(const int32_t *faces, const float *vertices, int64_
 /* ---- mesh simplification by vertex clustering (what Open3D's simplify_vertex_clustering does; the reference reduces its
  * meshes through Open3D and TRELLIS post-processing) ----
  * Open3D could not be run where this was written.  The rules below ARE the specification; nothing was compared with
- * Open3D's own output.  Edge-collapse decimation to a target triangle count is not built.
+ * Open3D's own output.  Edge-collapse decimation to a target triangle count is the next block (scorp_mesh_decimate_*).
  *
  * Inputs: vertices[Nv, 3] float32, finite; colors[Nv, 3] float32; faces[F, 3] int32 in [0, Nv); voxel_size h > 0 (a double);
  * the placement, average (quadric = 0) or quadric.  All arithmetic below is float64 from the float32 values, every product,
@@ -500,6 +500,106 @@ int scorp_mesh_simplify_place(const double *acc, const int32_t *cell_ijk, int64_
                               double voxel_size, int32_t quadric, float *out_vertices, float *out_colors, scorp_stream_t stream);
 int scorp_mesh_simplify_faces(const int32_t *faces, int64_t num_faces, const int32_t *vertex_cell, int64_t num_vertices,
                               int32_t *table, uint64_t num_slots, int32_t *out_faces, uint8_t *out_keep, scorp_stream_t stream);
+
+/* ---- edge-collapse decimation to a target triangle count (what Open3D's simplify_quadric_decimation and the simplify
+ * step of TRELLIS post-processing are used for) ----
+ * Open3D could not be run where this was written.  The rules below ARE the specification; nothing was compared with
+ * Open3D's own output.  tests/mesh_decimate_reference.py restates them in plain Python.
+ *
+ * Inputs: vertices[Nv, 3] float32, finite; colors[Nv, 3] float32; faces[F, 3] int32 in [0, Nv); the target triangle count
+ * >= 0; maximum_error >= 0 (may be +inf); boundary_weight >= 0, finite.  All arithmetic is float64, every product,
+ * quotient, sum and square root rounded on its own (no fp contraction), sums of three terms as (a + b) + c; u . w means
+ * (u0 w0 + u1 w1) + u2 w2, |u|^2 = u . u, u x w = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0).
+ *
+ *  0. State.  origin[k] = double(min over the vertices of coordinate k); P[v] = double(vertex v) - origin; the colour C[v]
+ *     as doubles; the member count n[v] = 1.  Faces with two equal indices are dropped, the rest keep their order.  Every
+ *     vertex has a quadric Q[v] = (A as xx xy xz yy yz zz, b[3], c), ten doubles.  Adding the plane (unit normal m, offset
+ *     d) with weight w to a quadric means, with wm = (w m0, w m1, w m2) and wd = w d:  A_jk += wm_j m_k (j <= k),
+ *     b_k += wd m_k, c += wd d.
+ *  1. Initial quadrics, gathered per vertex, never scattered: Q[v] starts at 0 and v visits its faces in ascending face
+ *     index.  A face (i0, i1, i2) with N = (P[i1] - P[i0]) x (P[i2] - P[i0]) and |N| = sqrt(N . N) > 0 adds the plane
+ *     (n = N / |N|, d = -(n . P[i0])) with weight 0.5 |N|.  Then its edges k = 0, 1, 2, from corner k to corner k + 1 (mod 3),
+ *     in that order: an edge (va, vb) that lies in exactly one face and has v as an end adds a second plane, with e =
+ *     P[vb] - P[va], M = e x n, |M| = sqrt(M . M) > 0: (m = M / |M|, d = -(m . P[va])) with weight boundary_weight (e . e).
+ *     Faces of zero area add nothing.
+ *  2. Per round; `round` counts from 1, F is the current face count, K = F - target.  The loop ends when K <= 0 or a round
+ *     has no candidate.  The edges are the unique pairs (lo < hi) of the current faces, numbered in ascending (lo, hi); each
+ *     carries the count of its faces.  A vertex is BOUNDARY when it is on an edge with one face, LOCKED when it is on an edge
+ *     with three or more.
+ *  3. Candidates.  An edge is a candidate only if: it has 1 or 2 faces; neither end is locked; it is not a 2-face edge
+ *     between two boundary vertices; the link condition holds - the set of common neighbours of lo and hi (u neighbours v
+ *     when (u, v) is a current edge) equals the set of apexes of the edge's faces, and that set has as many members as the
+ *     edge has faces; its cost (rule 4) is <= maximum_error; the flip test (rule 5) passes.
+ *  4. Placement and cost.  Q = Q[lo] + Q[hi], element by element, lo's term first; A00 .. A22, b0 .. b2, c its parts.
+ *       c00 = A11 A22 - A12 A12   c01 = A02 A12 - A01 A22   c02 = A01 A12 - A02 A11
+ *       c11 = A00 A22 - A02 A02   c12 = A01 A02 - A00 A12   c22 = A00 A11 - A01 A01      (c10 = c01, c20 = c02, c21 = c12)
+ *       det = (A00 c00 + A01 c01) + A02 c02,    x_k = -((c_k0 b0 + c_k1 b1) + c_k2 b2) / det,
+ *     with mid = 0.5 (P[lo] + P[hi]) and t = (A00 + A11) + A22.  The solved point is taken iff det > 1e-9 ((t t) t) and
+ *     |x - mid|^2 <= 4 |P[hi] - P[lo]|^2 (both false for NaN).  Otherwise x is whichever of P[lo], P[hi], mid has the
+ *     least cost, ties in that order.
+ *       cost(x) = max(0, ((s2 + 2 s1) + 2 s0) + c),   s2 = (A00 (x0 x0) + A11 (x1 x1)) + A22 (x2 x2),
+ *       s1 = (A01 (x0 x1) + A02 (x0 x2)) + A12 (x1 x2),   s0 = (b0 x0 + b1 x1) + b2 x2.
+ *     The two constants are conditions, not measurements: with them the yardstick takes the cube, the sphere and the sheets
+ *     of tests/mesh_decimate_reference.py to their targets through the cofactor solve.
+ *  5. Flip test.  For every current face (i0, i1, i2) that contains lo or hi but not both: N_old = (P[i1] - P[i0]) x
+ *     (P[i2] - P[i0]), N_new the same with that end's position replaced by x; N_old . N_new > 0 is required.
+ *  6. Window.  The candidates sorted by (cost, edge number) ascending; the first max(1, K div 2) are the window.
+ *  7. Priority.  h(e) = mix((lo << 32 | hi) ^ mix(round)) >> 1, mix the splitmix64 finaliser modulo 2^64: z += 0x9E3779B97F4A7C15;
+ *     z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  The window's edges are
+ *     ranked by (h, edge number); the rank is an int32.  (Ranking by cost instead left two collapses per round on a cube.)
+ *  8. Independent set.  vmin[v] = the least rank of a window edge at v, 2^31 - 1 if there is none; vmin2[v] = the least of
+ *     vmin[v] and vmin[u] over all current edges (u, v).  A window edge is SELECTED iff rank == vmin2[lo] == vmin2[hi].
+ *     No vertex of a selected edge equals or neighbours a vertex of another selected edge:  let e (rank r) and e' (rank r')
+ *     be selected and w a vertex of e' that equals or neighbours the vertex v of e.  vmin[w] <= r' since e' is at w, and
+ *     vmin2[v] <= vmin[w], so r = vmin2[v] <= r'.  By the same argument with the roles exchanged r' <= r; ranks are
+ *     distinct, so e = e'.  Hence every test of rules 3 - 5 read only data that no other collapse of the round changes.
+ *  9. Budget.  Walk the selected edges in rank order with the running sum of their face counts; an edge is applied iff the
+ *     sum before it is < K.  For any reachable target target - 1 <= F_out <= target.  The window's rank-0 edge is always
+ *     selected and applied, so a round with a candidate removes a face and the loop ends within F rounds.
+ * 10. Apply.  P[lo] = x; Q[lo] = Q[lo] + Q[hi]; C[lo] = (n_lo C[lo] + n_hi C[hi]) / (n_lo + n_hi) per channel, the counts as
+ *     doubles; n[lo] += n[hi]; faces are mapped through hi -> lo and those with two equal indices are dropped, the
+ *     survivors keep their order.
+ * 11. Output.  Vertices no face references are dropped, the survivors keep their order and the faces are re-indexed;
+ *     positions are float32(origin + P), colours float32(C).
+ * No float is summed by atomics: every result, float or integer, is a function of the input alone, and two runs agree
+ * bit for bit.
+ *
+ * The caller owns every buffer and, between the calls, the sorts, the scans, the compaction and ONE `unique` per round over
+ * the 3 F keys lo << 32 | hi of the faces' edges (edge k of face t at 3 t + k), which yields edge_keys[E] (int64, ascending:
+ * the edge numbering), face_edge[F, 3] (int32) and edge_faces[E] (int32 counts).  vf_start[Nv + 1], vf_face[3 F] (int32) is
+ * the vertex -> face CSR of the current faces, every vertex's faces in ascending index.  The state is positions[Nv, 3],
+ * quadrics[Nv, 10], colors[Nv, 3] (float64) and count[Nv] (int32); Nv never changes, a collapsed vertex just loses its faces.
+ *   quadrics:   rule 1, once, from the cleaned faces of rule 0.
+ *   flags:      out_flags[Nv] (int32, zeroed by the call): bit 0 boundary, bit 1 locked.
+ *   candidates: out_cost[E] = the cost of rule 4, or +inf for an edge that is no candidate; out_x[E, 3] its point.
+ *   hash:       out_hash[i] = h(window[i]) (int64, < 2^63) for the window's edge numbers window[W]; the caller passes them in
+ *               ascending edge number and sorts stably by the hash, which ranks by (h, edge number).
+ *   select:     ranked[W] = the window's edges by rank; vmin[Nv], vmin2[Nv] (int32) are scratch the call fills;
+ *               out_selected[W] one byte per rank.
+ *   apply:      applied[W] one byte per rank (rule 9, the caller's prefix sum); rule 10 on the state; out_vmap[Nv] = the
+ *               identity but for vmap[hi] = lo of the applied edges.
+ *   faces:      out_faces[F, 3] = the faces through vmap, out_keep[F] = 0 for a face with two equal indices.
+ * None synchronises.  An index that is out of range in a caller's array is never followed out of bounds.
+ * SCORP_ERR_INVALID: a NULL pointer, num_vertices < 1 or > 2^30, num_faces < 1 or > 2^28, num_edges < 1 or > 3 num_faces,
+ * num_window outside [1, num_edges], round < 1, maximum_error negative or NaN, boundary_weight negative or not finite. */
+int scorp_mesh_decimate_quadrics(const double *positions, int64_t num_vertices, const int32_t *faces, int64_t num_faces,
+                                 const int32_t *face_edge, const int32_t *edge_faces, int64_t num_edges, const int32_t *vf_start,
+                                 const int32_t *vf_face, double boundary_weight, double *out_quadrics, scorp_stream_t stream);
+int scorp_mesh_decimate_flags(const int64_t *edge_keys, const int32_t *edge_faces, int64_t num_edges, int64_t num_vertices,
+                              int32_t *out_flags, scorp_stream_t stream);
+int scorp_mesh_decimate_candidates(const double *positions, const double *quadrics, int64_t num_vertices, const int32_t *faces,
+                                   int64_t num_faces, const int64_t *edge_keys, const int32_t *edge_faces, int64_t num_edges,
+                                   const int32_t *vf_start, const int32_t *vf_face, const int32_t *flags, double maximum_error,
+                                   double *out_cost, double *out_x, scorp_stream_t stream);
+int scorp_mesh_decimate_hash(const int64_t *edge_keys, int64_t num_edges, const int32_t *window, int64_t num_window, int64_t round,
+                             int64_t *out_hash, scorp_stream_t stream);
+int scorp_mesh_decimate_select(const int64_t *edge_keys, int64_t num_edges, const int32_t *ranked, int64_t num_window,
+                               int64_t num_vertices, int32_t *vmin, int32_t *vmin2, uint8_t *out_selected, scorp_stream_t stream);
+int scorp_mesh_decimate_apply(const int64_t *edge_keys, int64_t num_edges, const int32_t *ranked, const uint8_t *applied,
+                              int64_t num_window, const double *x, int64_t num_vertices, double *positions, double *quadrics,
+                              double *colors, int32_t *count, int32_t *out_vmap, scorp_stream_t stream);
+int scorp_mesh_decimate_faces(const int32_t *faces, int64_t num_faces, const int32_t *vmap, int64_t num_vertices, int32_t *out_faces,
+                              uint8_t *out_keep, scorp_stream_t stream);
 
 /* ---- bounded TSDF volume: sparse 16^3-voxel blocks, fused and meshed (the route of gs2dgs/utils/mesh_utils.py:138-180
  * extract_mesh_bounded, which hands the work to Open3D's ScalableTSDFVolume) ----

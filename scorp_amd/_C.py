@@ -130,6 +130,8 @@ EXPORTS = [
     "scorp_mesh_cluster_link", "scorp_mesh_cluster_roots", "scorp_mesh_cluster_stats",
     "scorp_mesh_simplify_cells", "scorp_mesh_simplify_roots", "scorp_mesh_simplify_accumulate", "scorp_mesh_simplify_place",
     "scorp_mesh_simplify_faces",
+    "scorp_mesh_decimate_quadrics", "scorp_mesh_decimate_flags", "scorp_mesh_decimate_candidates", "scorp_mesh_decimate_hash",
+    "scorp_mesh_decimate_select", "scorp_mesh_decimate_apply", "scorp_mesh_decimate_faces",
     "scorp_tsdf_blocks_touch", "scorp_tsdf_blocks_neighbors", "scorp_tsdf_blocks_integrate",
     "scorp_isosurface_blocks_count_cells", "scorp_isosurface_blocks_emit_vertices", "scorp_isosurface_blocks_count_faces",
     "scorp_isosurface_blocks_emit_faces",
@@ -261,6 +263,13 @@ def lib():
     L.scorp_mesh_simplify_accumulate.argtypes = [vp, vp, i64, vp, i64, vp, f64, vp, vp, i64, i32, vp, vp, vp, vp]
     L.scorp_mesh_simplify_place.argtypes = [vp, vp, i64, vp, f64, i32, vp, vp, vp]
     L.scorp_mesh_simplify_faces.argtypes = [vp, i64, vp, i64, vp, u64, vp, vp, vp]
+    L.scorp_mesh_decimate_quadrics.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, vp, f64, vp, vp]
+    L.scorp_mesh_decimate_flags.argtypes = [vp, vp, i64, i64, vp, vp]
+    L.scorp_mesh_decimate_candidates.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, f64, vp, vp, vp]
+    L.scorp_mesh_decimate_hash.argtypes = [vp, i64, vp, i64, i64, vp, vp]
+    L.scorp_mesh_decimate_select.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp]
+    L.scorp_mesh_decimate_apply.argtypes = [vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.scorp_mesh_decimate_faces.argtypes = [vp, i64, vp, i64, vp, vp, vp]
     bv, f32 = ctypes.POINTER(ScorpTsdfBlockViews), ctypes.c_float
     L.scorp_tsdf_blocks_touch.argtypes = [bv, f32, f32, i32, vp, vp, u64, vp, vp]
     L.scorp_tsdf_blocks_neighbors.argtypes = [vp, i64, vp, vp]
