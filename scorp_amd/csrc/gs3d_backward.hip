@@ -32,8 +32,9 @@ namespace {
 //      dL/dalpha_i = (s - R) * T - T_final / (1 - alpha) * (bg . dL/dcolor);
 //   lane (= pixel) writes v, w into two wave-private LDS matrices [slot][pixel] (row stride 68 dwords: conflict-free
 //   row writes, 16-byte-aligned rows for the transposed A-operand reads);
-//   the 16x16 MFMA result holds block-frame moments, which sixteen lanes turn into the ten screen-space gradients;
-//   they are flushed with float atomics shaped as whole 40-byte row segments (lanes = consecutive floats).
+//   the matrix result holds block-frame moments, which stay in the splats' staging entries until the wave's chunk of 64
+//   hits is done; then ONE pass (lane = splat) turns them into the ten screen-space gradients, and they are flushed with
+//   float atomics shaped as whole 40-byte row segments (lanes = consecutive floats).
 //
 // Two forms of the reduction (template parameter kExact, entry point scorp_gs3d_backward_ex):
 //   * SPLIT (default): v and w leave the lane as TWO fp16 terms each - h1 = rtz16(x), h2 = rtz16(x - h1), 22 bits
@@ -78,12 +79,17 @@ constexpr float kWScale = 1024.0f;           // split form: blend weights (<= 1)
 // lane gathers one record (list entries are fetched two chunks ahead, records one) into a 64-slot staging buffer in the
 // wave's own LDS, and the chunk's four groups of 16 go through the 1a / 1b / MFMA pipeline described above.  A hit's
 // position in the list is arithmetic (no per-slot position array): slot i of a group whose first slot has 1-based
-// position `top` belongs to the pixel's blend iff top - i <= last contributor of the pixel.  The 16x16 result is
-// converted from block-frame moments to the ten gradients by lanes 0..15 and added to the per-Gaussian accumulators
-// with float atomics (zero terms are skipped).  Blocks are numbered so that the four waves of a tile land on the same
-// XCD (same L2).
+// position `top` belongs to the pixel's blend iff top - i <= last contributor of the pixel.  A group ends with its hits'
+// block-frame moments in the hits' own staging entries (the exact form's row sums land there directly, the split form adds
+// its two terms per group).  The tail runs once per chunk: every lane converts one hit's moments to the ten gradients
+// (the same instructions as a per-group tail on sixteen lanes, issued a quarter as often) and leaves them as a row of the
+// idle matrix; the chunk's 64 rows are added to the per-Gaussian accumulators with up to sixteen wave-wide float atomics
+// (four rows each, zero terms skipped) while the next chunk is being staged, and after the loop for the last chunk.
+// Blocks are numbered so that the four waves of a tile land on the same XCD (same L2).
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kChunk = 64;
+constexpr int kRStride = 12;                  // floats per row of a chunk's 64 x 10 results: 16-byte aligned rows, and the four rows
+                                             // a flush instruction reads (ten floats each, 12 apart) sit on distinct banks
 
 #ifndef SCORP_BWD_WAVES
 #define SCORP_BWD_WAVES 4
@@ -134,9 +140,12 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   // [row][pixel] matrix of one half-group (8 splats).  split form: rows 0..7 = first fp16 terms (v | w << 16) of the 8
   // splats, rows 8..15 = second terms; exact form: rows 0..7 = v, rows 8..15 = w (fp32)
   __shared__ __attribute__((aligned(16))) uint32_t xm[16 * kXStride];
-  float *dbuf = reinterpret_cast<float *>(xm);   // the 2 x 16 x 14 result tile reuses the matrix once the MFMAs have consumed it
+  float *dbuf = reinterpret_cast<float *>(xm);   // split form: the 2 x 16 x 14 result tile reuses the matrix once the MFMAs have consumed it
+  float *rbuf = reinterpret_cast<float *>(xm);   // a chunk's 64 result rows wait here between the chunk's last group and the next one's first
   float *xs = reinterpret_cast<float *>(xm);     // prologue scratch: 64 x 4 floats
-  static_assert(2 * kGroup * kDStride <= 13 * kXStride && 64 * 4 <= 13 * kXStride, "scratch fits below the zero fragments");
+  static_assert(2 * kGroup * kDStride <= 13 * kXStride && kChunk * kRStride <= 13 * kXStride && 64 * 4 <= 13 * kXStride,
+                "scratch fits below the zero fragments");
+  static_assert(kAccStride == 16 && kRStride >= 10 && kRStride % 4 == 0, "a result row's ten floats map onto an accumulator row lane for lane");
   static_assert(kXStride != 68 ||
                 sizeof(uint4) * 3 * kChunk + sizeof(float4) * 2 * kChunk + sizeof(float2) * kChunk + 4 * kChunk + 4 * 16 * kXStride == 10240,
                 "10 KiB of LDS per wave: four waves per SIMD fill the CU's 160 KiB exactly");
@@ -243,24 +252,55 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   // exact form, the sums over the block's rows: rows rb and rb ^ 2 meet in a permlane32 swap (lane bit 5), whose two outputs
   // hold the rows with rb bit 1 clear (y = yl_lo) / set (y = yl_lo + 2)
   const float yl_lo = (float)(rb & 5) - 3.5f;
-  float park_v[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // a group's sums, parked until flush_sums
-  uint32_t park_o[4] = {det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u, det ? 0xFFFFFFFFu : 0u};
-                                                // ... and their float offsets in acc (N * 16 < 2^32, checked at the entry
-                                                // point); det: offsets in `partial`, 0xFFFFFFFF = nothing parked
-  auto flush_sums = [&]() {
-    if (det) {   // rows are written whole (zeros included): nothing was cleared beforehand
+  // A chunk's results wait in LDS as 64 rows of kRStride floats (`rbuf`, written by convert_chunk) with the rows' ids still in
+  // q_id; `nflush` = the number of rows waiting (wave-uniform).  flush_rows sends them off: up to sixteen wave-wide atomic
+  // instructions (lane = float of a 64-byte accumulator row, four rows per instruction, ten lanes of sixteen active: one
+  // memory-side request per splat; zero terms are skipped).  It is called behind the issue of the NEXT chunk's gathers and
+  // in front of the staging stores that overwrite q_id: vmcnt counts loads and atomics alike and the compiler waits with
+  // vmcnt(0) for the gathers, so atomics issued at the end of the chunk would be waited for, at their full memory-side
+  // latency, at the top of the next one.  Offsets: N * 16 < 2^32 floats (checked at the entry point).
+  // det: the rows are written whole to partial[4 * pair + quad] (zeros included: nothing was cleared beforehand), q_id
+  // holds the pair ordinal
+  int nflush = 0;
+  auto flush_rows = [&]() {
+    const int col = lane & 15, r4 = lane >> 4;
+    const float *rp = rbuf + r4 * kRStride + col;
+    const uint32_t *ip = q_id + r4;
+    const bool used = kColorOnly ? (col >= 6 && col < 9) : col < 10;
+    // the rows' values and ids are fetched together (one LDS round trip for the burst, not two per instruction); the addresses
+    // are in bounds for every lane, rows beyond the chunk and unused columns are masked afterwards
+#ifndef SCORP_BWD_FLUSH_BATCH
+#define SCORP_BWD_FLUSH_BATCH 16
+#endif
+    constexpr int kBatch = SCORP_BWD_FLUSH_BATCH;   // atomic instructions per LDS round trip
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        if (park_o[k] != 0xFFFFFFFFu) partial[park_o[k]] = park_v[k];
-        park_o[k] = 0xFFFFFFFFu;
+    for (int k0 = 0; k0 < kChunk / 4; k0 += kBatch) {
+      if (4 * k0 < nflush) {   // wave-uniform
+        float val[kBatch];
+        uint32_t rid[kBatch];
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) {
+          val[j] = rp[4 * (k0 + j) * kRStride];
+          rid[j] = ip[4 * (k0 + j)];
+        }
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) asm volatile("" : "+v"(val[j]), "+v"(rid[j]));   // (the reads stay in front of the branches)
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) {
+          const bool row = r4 < nflush - 4 * (k0 + j);
+          if (det) {
+            const uint32_t pair = row ? rid[j] : 0xFFFFFFFFu;
+            if (pair < capacity && col < 10) {   // (an ordinal beyond the reservation: an overflowed view, discarded anyway)
+              partial[(pair * 4u + (uint32_t)quad) * (uint32_t)kAccStride + col] = used ? val[j] : 0.0f;
+              if (col == 0) row_flags[pair * 4u + (uint32_t)quad] = 1;
+            }
+          } else if (row && used && val[j] != 0.0f) {
+            atomicAdd(acc + (rid[j] * (uint32_t)kAccStride + col), val[j]);
+          }
+        }
       }
-      return;
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (park_v[k] != 0.0f) atomicAdd(acc + park_o[k], park_v[k]);
-      park_v[k] = 0.0f;
-    }
+    nflush = 0;
   };
   // slots of a group: head + i, head a multiple of kGroup: one LDS base per array, immediate offsets.  `top` = 1-based
   // position in the hit list of the group's first slot (positions fall by one per slot).
@@ -268,14 +308,12 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
   // (8 slots) x (first term | second term) [exact form: (8 slots) x (v | w)], so the [row][pixel] matrix in LDS is
   // 16 x 64 dwords whatever the form; the two halves' results wait in registers and leave together.
   auto process_group = [&](auto full, auto clampy, int nslots, int head, int top) {
-    flush_sums();   // (a later group of the same chunk: the previous one's sums leave now)
     constexpr bool kFull = decltype(full)::value;   // full groups run straight-line; only a wave's last one is partial
     constexpr bool kClamp = decltype(clampy)::value;   // the chunk holds a splat with opacity > 0.99 (the forward's rule:
                                                        // only such a splat can reach alpha = 0.99; the others skip the v_min)
     int hv = head;
     asm volatile("" : "+v"(hv));   // keep the group's LDS bases in VGPRs (else every ds_read re-moves an SGPR base)
-    const float4 *gcol = q_col + hv, *gt0 = q_t0 + hv;
-    const float2 *gt1 = q_t1 + hv;
+    const float4 *gcol = q_col + hv;
     const int first = top - (int)last;   // slot i takes part in this pixel's blend iff top - i <= last, i.e. i >= first
     // log2(opacity * G) of the group's 16 hits at this lane's pixel: three MFMAs (the forward's, bit for bit)
     const uint4 *ka0 = a_on ? &q_k[0][hv + a_slot] : reinterpret_cast<const uint4 *>(&xm[13 * kXStride + 64]);
@@ -401,84 +439,74 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
         __builtin_amdgcn_wave_barrier();   // the next half (and the result tile) overwrite the matrix
       }
     }
-    // split form: result tile [term][slot][column] (it reuses the matrix): lane (bn, bk) holds rows 4 bk .. 4 bk + 3 of column bn
-    if (!kExact && bn < 14) {
+    // split form: result tile [term][slot][column] (it reuses the matrix): lane (bn, bk) holds rows 4 bk .. 4 bk + 3 of column
+    // bn.  Sixteen lanes add the two terms and leave the slot's ten block-frame moments in the slot's own staging entries,
+    // laid out like the exact form's sums (the group is done with them): one tail serves every form (convert_chunk)
+    if constexpr (!kExact) {
+      if (bn < 14) {
 #pragma unroll
-      for (int h = 0; h < 2; h++)
+        for (int h = 0; h < 2; h++)
 #pragma unroll
-        for (int r = 0; r < 4; r++)
-          dbuf[((bk >> 1) * kGroup + h * 8 + ((4 * bk + r) & 7)) * kDStride + bn] = dd[h][r];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane < nslots) {  // block-frame moments -> the ten screen-space gradients of slot `lane`
-      float *m = dbuf + lane * kDStride;
-      const float *m2 = m + kGroup * kDStride;
-      const float4 a = gt0[lane];     // x - cx, y - cy, A, B
-      const float2 b = gt1[lane];     // C, opacity
-      const float opac = b.y;
-      const float cA = a.z * (-1.0f / kConicScale), cB = a.w * (-0.5f / kConicScale), cC = b.x * (-1.0f / kConicScale);
-      const float xl = a.x, yl = a.y;
-      float mm[10];
-      if constexpr (kExact) {        // (v, x v, x^2 v, y v), (., y x v, ., y^2 v), w sums
-        const float4 u0 = *reinterpret_cast<const float4 *>(&q_k[1][hv + lane]), u1 = *reinterpret_cast<const float4 *>(&q_k[2][hv + lane]),
-                     u2 = gcol[lane];
-        mm[0] = u0.x; mm[1] = u0.y; mm[2] = u0.w; mm[3] = u0.z; mm[4] = u1.y; mm[5] = u1.w;
-        mm[6] = u2.x; mm[7] = u2.y; mm[8] = u2.z; mm[9] = u2.w;
-      } else {
+          for (int r = 0; r < 4; r++)
+            dbuf[((bk >> 1) * kGroup + h * 8 + ((4 * bk + r) & 7)) * kDStride + bn] = dd[h][r];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (lane < nslots) {
+        const float *m = dbuf + lane * kDStride;
+        const float *m2 = m + kGroup * kDStride;
         const float4 u0 = *reinterpret_cast<const float4 *>(m), u1 = *reinterpret_cast<const float4 *>(m + 4),
                      u2 = *reinterpret_cast<const float4 *>(m + 8), u3 = *reinterpret_cast<const float4 *>(m + 12);
         const float4 w0 = *reinterpret_cast<const float4 *>(m2), w1 = *reinterpret_cast<const float4 *>(m2 + 4),
                      w2 = *reinterpret_cast<const float4 *>(m2 + 8), w3 = *reinterpret_cast<const float4 *>(m2 + 12);
         // first + second term; W sums = (first-term + remainder columns) of the upstream gradients
         const float inv_w = inv_sv * (1.0f / kWScale);
+        float mm[10];
         mm[0] = (u0.x + w0.x) * inv_sv; mm[1] = (u0.y + w0.y) * inv_sv; mm[2] = (u0.z + w0.z) * inv_sv;
         mm[3] = (u0.w + w0.w) * inv_sv; mm[4] = (u1.x + w1.x) * inv_sv; mm[5] = (u1.y + w1.y) * inv_sv;
         mm[6] = ((u1.z + w1.z) + (u2.z + w2.z)) * inv_w; mm[7] = ((u1.w + w1.w) + (u2.w + w2.w)) * inv_w;
         mm[8] = ((u2.x + w2.x) + (u3.x + w3.x)) * inv_w; mm[9] = ((u2.y + w2.y) + (u3.y + w3.y)) * inv_w;
+        if constexpr (!kColorOnly) {
+          *reinterpret_cast<float4 *>(&q_k[1][hv + lane]) = make_float4(mm[0], mm[1], mm[3], mm[2]);
+          *reinterpret_cast<float4 *>(&q_k[2][hv + lane]) = make_float4(0.0f, mm[4], 0.0f, mm[5]);
+        }
+        q_col[hv + lane] = make_float4(mm[6], mm[7], mm[8], mm[9]);
       }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();   // (the next group overwrites the result tile)
+    }
+  };
+  // The chunk's tail, once per 64 hits with every lane holding a slot: the slot's block-frame moments (sum v {1, x, x^2, y},
+  // sum y v {., x, ., y}, sum w {dL/dr, dL/dg, dL/db, dL/ddepth} in its three staging entries) -> its ten screen-space
+  // gradients, left as row `lane` of rbuf for flush_rows.  The matrix is idle between chunks; 64 rows of kRStride floats end
+  // below the zero fragments of its rows 13..15.
+  auto convert_chunk = [&](int n) {
+    if (lane < n) {
+      const float4 a = q_t0[lane];     // x - cx, y - cy, A, B
+      const float2 b = q_t1[lane];     // C, opacity
+      const float opac = b.y;
+      const float cA = a.z * (-1.0f / kConicScale), cB = a.w * (-0.5f / kConicScale), cC = b.x * (-1.0f / kConicScale);
+      const float xl = a.x, yl = a.y;
+      float *m = rbuf + lane * kRStride;
+      const float4 u2 = q_col[lane];
       if constexpr (kColorOnly) {
         *reinterpret_cast<float4 *>(m) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        *reinterpret_cast<float4 *>(m + 4) = make_float4(0.0f, 0.0f, mm[6], mm[7]);
-        *reinterpret_cast<float2 *>(m + 8) = make_float2(mm[8], 0.0f);
+        *reinterpret_cast<float4 *>(m + 4) = make_float4(0.0f, 0.0f, u2.x, u2.y);
+        *reinterpret_cast<float2 *>(m + 8) = make_float2(u2.z, 0.0f);
       } else {
-        const float m0 = mm[0], mx = mm[1], my = mm[2], mxx = mm[3], mxy = mm[4], myy = mm[5];
+        const float4 u0 = *reinterpret_cast<const float4 *>(&q_k[1][lane]), u1 = *reinterpret_cast<const float4 *>(&q_k[2][lane]);
+        const float m0 = u0.x, mx = u0.y, my = u0.w, mxx = u0.z, mxy = u1.y, myy = u1.w;
         const float svdx = xl * m0 - mx, svdy = yl * m0 - my;
         const float svdx2 = xl * xl * m0 - 2.0f * xl * mx + mxx;
         const float svdxdy = xl * yl * m0 - xl * my - yl * mx + mxy;
         const float svdy2 = yl * yl * m0 - 2.0f * yl * my + myy;
         *reinterpret_cast<float4 *>(m) = make_float4(0.5f * W * (-cA * svdx - cB * svdy), 0.5f * H * (-cC * svdy - cB * svdx),
                                                      -0.5f * svdx2, -svdxdy);
-        *reinterpret_cast<float4 *>(m + 4) = make_float4(-0.5f * svdy2, m0 / opac, mm[6], mm[7]);
-        *reinterpret_cast<float2 *>(m + 8) = make_float2(mm[8], mm[9]);
+        *reinterpret_cast<float4 *>(m + 4) = make_float4(-0.5f * svdy2, m0 / opac, u2.x, u2.y);
+        *reinterpret_cast<float2 *>(m + 8) = make_float2(u2.z, u2.w);
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // The 160 sums go out as four wave-wide atomic instructions (lane = float of a 64-byte accumulator row, four rows
-    // per instruction, ten lanes of sixteen active: one memory-side request per splat) - but not yet: they are parked in registers and
-    // issued after the next chunk's gathers have been picked up (flush_sums).  vmcnt counts loads and atomics alike
-    // and the compiler waits with vmcnt(0) for the gathers, so atomics issued right here would be waited for, at
-    // their full memory-side latency, at the top of the next chunk.
-    static_assert(kAccStride == 16 && kDStride >= 16 && kDStride % 4 == 0, "a result row's first 16 floats map onto an accumulator row lane for lane");
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int sl = 4 * k + (lane >> 4), col = lane & 15;
-      park_v[k] = 0.0f;
-      if (det) {
-        park_o[k] = 0xFFFFFFFFu;
-        const uint32_t pair = sl < nslots ? q_id[head + sl] : 0xFFFFFFFFu;   // (det: the staging lane left the pair ordinal here)
-        if (pair < capacity && col < 10) {   // (an ordinal beyond the reservation: an overflowed view, discarded anyway)
-          const bool used = kColorOnly ? (col >= 6 && col < 9) : true;
-          park_v[k] = used ? dbuf[sl * kDStride + col] : 0.0f;
-          park_o[k] = (pair * 4u + (uint32_t)quad) * (uint32_t)kAccStride + col;
-          if (col == 0) row_flags[pair * 4u + (uint32_t)quad] = 1;
-        }
-      } else if (sl < nslots && (kColorOnly ? (col >= 6 && col < 9) : col < 10)) {
-        park_v[k] = dbuf[sl * kDStride + col];
-        park_o[k] = q_id[head + sl] * (uint32_t)kAccStride + col;
-      }
-    }
+    nflush = n;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
   };
@@ -507,7 +535,9 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
     float4 a1, b1, c1;
     fetch_rec(id1, a1, b1, c1);
     const uint32_t id2 = fetch_id(ch + 2);
-    flush_sums();
+    flush_rows();   // the previous chunk's rows: behind the issue of this chunk's gathers, in front of the staging stores
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
     if (id != 0xFFFFFFFFu) {
       uint4 k0, k1, k2;
       splat_block_coefs(a.x, a.y, a.z, a.w, b.x, b.y, cx, cy, k0, k1, k2);
@@ -537,9 +567,10 @@ blend_backward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32
       else if (hot) process_group(std::true_type{}, std::true_type{}, kGroup, head, top - head);
       else process_group(std::true_type{}, std::false_type{}, kGroup, head, top - head);
     }
+    convert_chunk(n);
     id = id1; a = a1; b = b1; c = c1; id1 = id2;
   }
-  flush_sums();
+  flush_rows();
 }
 }  // namespace
 }  // namespace scorp
