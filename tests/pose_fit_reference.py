@@ -48,17 +48,93 @@ def ransac_fit(source, target, samples, threshold, min_inlier_ratio=-1.0, method
             m = residuals(p, q, R, t, s) < threshold
             masks.append(m)
             counts[h] = m.sum()
-    winner, iterations = int(np.argmax(counts)), len(samples)
-    if min_inlier_ratio > 0:
-        over = np.nonzero((counts > min_inlier_ratio * n) & (counts > 0))[0]
-        if len(over):
-            winner, iterations = int(over[0]), int(over[0]) + 1
+    winner, iterations = select_winner(counts, n, min_inlier_ratio)
     count = int(counts[winner])
     if count < 3:
         raise ValueError("No inliers found in RANSAC.")
     mask = masks[winner]
     R, t, s = similarity_fit(p[mask], q[mask], method)
     return {"R": R, "t": t, "s": s, "winner": winner, "count": count, "counts": counts, "mask": mask, "iterations": iterations}
+
+
+def select_winner(counts, n, min_inlier_ratio=-1.0):
+    """(winner, iterations) by the reference's rule: the first hypothesis with the highest count; with min_inlier_ratio > 0
+    the first whose count exceeds (strictly) min_inlier_ratio * n, where the reference's loop ends."""
+    winner, iterations = int(np.argmax(counts)), len(counts)
+    if min_inlier_ratio > 0:
+        over = np.nonzero((counts > min_inlier_ratio * n) & (counts > 0))[0]
+        if len(over):
+            winner, iterations = int(over[0]), int(over[0]) + 1
+    return winner, iterations
+
+
+def similarity_fits(p3, q3, method="umeyama"):
+    """similarity_fit over a batch of samples p3, q3 [n_hyp, k, 3] with one stacked np.linalg.svd: (R [n_hyp, 3, 3],
+    t [n_hyp, 3], s [n_hyp], sv [n_hyp, 3]).  A sample with a non-finite covariance (LAPACK refuses it) gets a NaN model,
+    which counts nothing."""
+    if method not in ("umeyama", "kabsch"):
+        raise NotImplementedError(method)
+    p3 = np.asarray(p3, dtype=np.float64)
+    q3 = np.asarray(q3, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        pm, qm = p3.mean(axis=1), q3.mean(axis=1)
+        pc, qc = p3 - pm[:, None], q3 - qm[:, None]
+        cov = np.matmul(pc.transpose(0, 2, 1), qc)
+        finite = np.isfinite(cov).all(axis=(1, 2))
+        U, S, Vt = np.linalg.svd(np.where(finite[:, None, None], cov, 0.0))
+        d = np.ones((len(cov), 3))
+        d[:, 2] = np.where(np.linalg.det(np.matmul(U, Vt)) < 0, -1.0, 1.0)
+        R = np.matmul(Vt.transpose(0, 2, 1) * d[:, None, :], U.transpose(0, 2, 1))
+        s = (S * d).sum(axis=1) / (pc ** 2).sum(axis=(1, 2)) if method == "umeyama" else np.ones(len(cov))
+        t = qm - s[:, None] * np.einsum("hab,hb->ha", R, pm)
+    bad = ~finite
+    R[bad], t[bad], s[bad], S[bad] = np.nan, np.nan, np.nan, np.nan
+    return R, t, s, S
+
+
+def ransac_table(source, target, samples, threshold, method="umeyama", chunk=4096):
+    """Every hypothesis against every pair, batched: dict(counts [n_hyp] int32, margin: the smallest |residual - threshold|
+    / threshold over all finite (hypothesis, pair), cond: the smallest second-over-first singular value of the hypotheses
+    whose three indices differ, R, t, s: the models)."""
+    p = np.asarray(source, dtype=np.float64)
+    q = np.asarray(target, dtype=np.float64)
+    samples = np.asarray(samples)
+    R, t, s, S = similarity_fits(p[samples], q[samples], method)
+    counts = np.zeros(len(samples), dtype=np.int32)
+    margin = np.inf
+    with np.errstate(all="ignore"):
+        for b in range(0, len(samples), chunk):
+            e = slice(b, b + chunk)
+            pred = np.einsum("hab,nb->hna", R[e], p) * s[e, None, None] + t[e, None, :]
+            res = np.linalg.norm(pred - q[None], axis=2)
+            counts[e] = (res < threshold).sum(axis=1)
+            gap = np.abs(res - threshold)[np.isfinite(res)]
+            if gap.size:
+                margin = min(margin, float(gap.min()) / threshold)
+        distinct = (samples[:, 0] != samples[:, 1]) & (samples[:, 0] != samples[:, 2]) & (samples[:, 1] != samples[:, 2])
+        distinct &= np.isfinite(S).all(axis=1)
+        cond = float((S[distinct, 1] / S[distinct, 0]).min()) if distinct.any() else np.inf
+    return {"counts": counts, "margin": margin, "cond": cond, "R": R, "t": t, "s": s}
+
+
+def ransac_counts(source, target, samples, threshold, method="umeyama"):
+    """ransac_fit's counts with one stacked SVD over all hypotheses (65 535 of them take seconds)."""
+    return ransac_table(source, target, samples, threshold, method)["counts"]
+
+
+def ransac_fit_batched(source, target, samples, threshold, min_inlier_ratio=-1.0, method="umeyama"):
+    """ransac_fit on the batched counts, and without its error: dict(counts, margin, cond, winner, count, mask, iterations)
+    always, and R, t, s (the fit over the winner's inliers) when the winner has at least 3."""
+    p = np.asarray(source, dtype=np.float64)
+    q = np.asarray(target, dtype=np.float64)
+    out = ransac_table(p, q, samples, threshold, method)
+    w, out["iterations"] = select_winner(out["counts"], len(p), min_inlier_ratio)
+    with np.errstate(all="ignore"):
+        mask = residuals(p, q, out["R"][w], out["t"][w], out["s"][w]) < threshold
+    out.update(winner=w, count=int(out["counts"][w]), mask=mask, R=None, t=None, s=None)
+    if out["count"] >= 3:
+        out["R"], out["t"], out["s"] = similarity_fit(p[mask], q[mask], method)
+    return out
 
 
 def draw_triples(n, count):
@@ -106,11 +182,17 @@ def start_scale(init_scale, scale_min, scale_max):
 
 
 def adam_9dof(source_points, target_points, iterations=1000, lr=1e-3, lambda_reg_scale=2e-5, lambda_reg_rot=1e-4, scale_max=1.5,
-              scale_min=0.75, init_scale=1.0, device="cpu", dtype=torch.float64, loss_every=0):
+              scale_min=0.75, init_scale=1.0, device="cpu", dtype=torch.float64, loss_every=0, centred=False,
+              reg_factors=(1.0, 1.0, 1.0)):
     """dict(rotation, translation, scale, rotation_orthogonal, M, losses) in float64 numpy: `iterations` steps of
     torch.optim.Adam on t, q, qo and the scale logits l with M = R(q) Ro(qo)^T diag(s) Ro(qo), s = scale_min + (scale_max -
     scale_min) sigmoid(l) and the loss  mean |M p + t - q|^2 + lambda_reg_scale (mean (l - 1)^2 + mean (s - mean s)^2) +
-    lambda_reg_rot arccos(clamp((tr R - 1) / 2, -1, 1))^2.  One small torch kernel per operation: the reference's pattern."""
+    lambda_reg_rot arccos(clamp((tr R - 1) / 2, -1, 1))^2.  One small torch kernel per operation: the reference's pattern.
+    centred=True states the data term a second way, mean |M pc + (M pm + t - qm) - qc|^2 about the two centroids: the same
+    function of the parameters, so the distance between the two runs is the yardstick's own formulation error.
+    reg_factors scales the three regulariser contributions (logit term, scale-spread term, rotation term) so that a test
+    can show that a case would see one of them wrong.  Also returned: grad0 [14], the gradient at the start (t, q, qo,
+    logits), and loss, the last step's loss."""
     P = torch.tensor(np.asarray(source_points), dtype=dtype, device=device)
     Q = torch.tensor(np.asarray(target_points), dtype=dtype, device=device)
     s0 = start_scale(init_scale, scale_min, scale_max)
@@ -122,17 +204,27 @@ def adam_9dof(source_points, target_points, iterations=1000, lr=1e-3, lambda_reg
         logit = torch.nn.Parameter(torch.logit((torch.tensor(s0, dtype=dtype, device=device) - scale_min) / (scale_max - scale_min)))
     opt = torch.optim.Adam([{"params": x, "lr": lr} for x in (t, q, qo, logit)])
     span = scale_max - scale_min
-    losses = []
+    f_logit, f_spread, f_rot = reg_factors
+    pm, qm = P.mean(dim=0), Q.mean(dim=0)
+    Pc, Qc = P - pm, Q - qm
+    losses, grad0, last = [], None, 0.0
     for it in range(iterations):
         s = scale_min + span * torch.sigmoid(logit)
         R, Ro = quaternion_to_matrix(q), quaternion_to_matrix(qo)
-        pred = (R @ Ro.T @ (s[:, None] * (Ro @ P.T))).T + t
-        data = torch.mean((pred - Q) ** 2)
-        reg = torch.mean((logit - 1) ** 2) + torch.mean((s - torch.mean(s)) ** 2)
-        rot = torch.arccos(torch.clamp((torch.trace(R) - 1) / 2, -1, 1)) ** 2
+        if centred:
+            M = R @ Ro.T @ (s[:, None] * Ro)
+            data = torch.mean(((M @ Pc.T).T + (M @ pm + t - qm) - Qc) ** 2)
+        else:
+            pred = (R @ Ro.T @ (s[:, None] * (Ro @ P.T))).T + t
+            data = torch.mean((pred - Q) ** 2)
+        reg = f_logit * torch.mean((logit - 1) ** 2) + f_spread * torch.mean((s - torch.mean(s)) ** 2)
+        rot = f_rot * torch.arccos(torch.clamp((torch.trace(R) - 1) / 2, -1, 1)) ** 2
         loss = data + lambda_reg_scale * reg + lambda_reg_rot * rot
         opt.zero_grad()
         loss.backward()
+        if it == 0:
+            grad0 = torch.cat([x.grad.detach().reshape(-1) for x in (t, q, qo, logit)]).cpu().double().numpy()
+        last = float(loss.detach())
         opt.step()
         if loss_every > 0 and (it + 1) % loss_every == 0:
             losses.append(float(loss.detach()))
@@ -143,6 +235,8 @@ def adam_9dof(source_points, target_points, iterations=1000, lr=1e-3, lambda_reg
         out = {k: v.detach().cpu().double().numpy() for k, v in out.items()}
     out["M"] = compose(out["rotation"], out["scale"], out["rotation_orthogonal"])
     out["losses"] = np.array(losses)
+    out["grad0"] = grad0
+    out["loss"] = last
     return out
 
 
