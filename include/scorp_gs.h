@@ -115,7 +115,9 @@ size_t scorp_gs3d_state_bytes(int32_t num_gaussians, int32_t image_width, int32_
  * footprint reaches the block.  The backward replays exactly those entries, so it must get the SAME pair buffer the
  * render filled (it only reads it). */
 size_t scorp_gs3d_pairs_bytes(uint64_t capacity);
-/* Scratch of one backward call (per-Gaussian screen-space gradient accumulators). */
+/* Scratch of one backward call (per-Gaussian screen-space gradient accumulators), plus the nine planes of
+ * ceil(num_gaussians / 256) * 256 floats in which scorp_gs3d_train_view hands d(colour)/d(view direction) from its
+ * forward to its backward (see scorp_gs3d_backward_scratch_bytes_ex). */
 size_t scorp_gs3d_backward_scratch_bytes(int32_t num_gaussians);
 
 /* ---- forward, in three steps so the caller owns every allocation ---- */
@@ -174,7 +176,11 @@ int scorp_gs3d_backward(const ScorpGs3dInputs *in, const void *state, const void
  * zero.  Needs the larger scratch of scorp_gs3d_backward_scratch_bytes_ex. */
 #define SCORP_BACKWARD_DETERMINISTIC 4u
 /* scratch size for scorp_gs3d_backward_ex with `flags`: the accumulator rows (num_gaussians * 64 bytes), plus, for
- * SCORP_BACKWARD_DETERMINISTIC, num_gaussians + 1 pair ordinals, 4 * capacity flag bytes and 4 * capacity rows of 64 bytes */
+ * SCORP_BACKWARD_DETERMINISTIC, num_gaussians + 1 pair ordinals, 4 * capacity flag bytes and 4 * capacity rows of 64 bytes.
+ * Behind that, 9 * ceil(num_gaussians / 256) * 256 floats that only scorp_gs3d_train_view[_ex] uses: with the training
+ * layout at SH degree 3 its per-Gaussian forward leaves d(colour)/d(view direction) there and its backward reads these
+ * nine floats per Gaussian instead of the SH rows.  Every call accepts a buffer without that tail (this size minus
+ * 36 * ceil(num_gaussians / 256) * 256 bytes); the view then reads the rows a second time, with the same results. */
 size_t scorp_gs3d_backward_scratch_bytes_ex(int32_t num_gaussians, int32_t image_width, int32_t image_height, uint64_t capacity,
                                             uint32_t flags);
 int scorp_gs3d_backward_ex(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,

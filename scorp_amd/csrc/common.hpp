@@ -404,6 +404,17 @@ inline size_t backward_scratch_bytes(int N, uint64_t capacity, uint32_t flags, i
   if (flags & SCORP_BACKWARD_DETERMINISTIC) return DetLayout(N, capacity, row_floats).total;
   return align_up((size_t)(N > 0 ? N : 1) * row_floats * sizeof(float), 256);
 }
+// The one-call 3DGS view carries d(rgb)/d(view direction) from its per-Gaussian forward to its per-Gaussian backward, so
+// that the backward does not read the SH rows a second time: nine planes of sh_jacobian_plane(N) floats BEHIND the layout
+// above (at offset backward_scratch_bytes(...)).  scorp_gs3d_backward_scratch_bytes[_ex] include them; a smaller buffer
+// that still holds the layout above is valid everywhere, the view then reads the rows as the separate calls do.
+__host__ __device__ inline size_t sh_jacobian_plane(int N) { return ((size_t)(N > 0 ? N : 1) + 255) / 256 * 256; }
+inline size_t sh_jacobian_bytes(int N) { return 9 * sh_jacobian_plane(N) * sizeof(float); }
+// The layout whose kernels know the Jacobian: the training layout at SH degree 3, one view
+inline bool sh_jacobian_layout_ok(const ScorpGs3dInputs *in) {
+  return in->num_gaussians > 0 && in->shs && in->shs_rest && in->sh_degree == 3 && in->sh_coeffs == 16 && in->scales &&
+         in->rotations && !in->cov3D_precomp && in->num_views <= 1;
+}
 // The deterministic rows of the backward and the mask vote in a scratch block laid out by DetLayout(N, capacity,
 // row_floats): the row flags cleared and pair_base[N + 1] formed from the binning's tile rectangles and masks (binning.hip).
 // The caller's blend then writes the rows of pair ordinal pair_base[i] + pair_rank and launch_reduce_pair_rows adds them.
@@ -447,12 +458,13 @@ __device__ __forceinline__ float nan_to_num00(float x) {
 // ---- per-Gaussian kernels (gs3d_pergaussian.hip) ----
 // out_visible (optional): radii > 0 as bytes, what scorp_gs3d_render_tail would write
 void launch_preprocess(const ScorpGs3dInputs *in, const StateLayout &L, SplatRec *rec, BinRec *bin, uint64_t *tile_mask,
-                       int32_t *radii, uint32_t *tile_count, uint8_t *out_visible, hipStream_t stream);
+                       int32_t *radii, uint32_t *tile_count, uint8_t *out_visible, hipStream_t stream, float *jac = nullptr);
 // ---- the public preprocess / render with the outputs of scorp_gs3d_render_tail produced on the way (gs3d_forward.hip):
 // out_visible by the per-Gaussian kernel, out_depth_norm = nan_to_num(depth / alpha) by the blend forward's epilogue;
 // either may be NULL.  scorp_gs3d_train_view uses them instead of a tail launch.
+// jac (optional; sh_jacobian_layout_ok(in) and sh_jacobian_bytes(N) bytes): the per-Gaussian kernel also stores d(rgb)/d(dir).
 int preprocess3d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, uint8_t *out_visible, void *state, size_t state_bytes,
-                      scorp_stream_t stream);
+                      scorp_stream_t stream, float *jac = nullptr);
 // zero_buf / zero_bytes (optional, a multiple of 16 bytes): memory the blend forward's waves clear on the way (the
 // backward's accumulator rows: the forward is VALU-bound and its stores are free, a separate fill is 9 us per view).
 // header_copy (optional, 16 bytes): {num_pairs, overflow, capacity, long_tiles} of this render, written by the scatter
@@ -477,11 +489,13 @@ struct AdamEpi {
 // added to every Gaussian's scaling gradient - a separate instantiation, the plain one is the kernel it always was
 void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L, const BinRec *bin, const float *acc,
                                 const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam = nullptr,
-                                float lambda_isotropic = 0.0f);
+                                float lambda_isotropic = 0.0f, const float *jac = nullptr);
 int backward3d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity, const float *dL_dcolor,
                     const float *dL_ddepth, const float *dL_dalpha, const ScorpGs3dGrads *grads, void *scratch,
                     size_t scratch_bytes, uint32_t flags, scorp_stream_t stream, const AdamEpi *adam,
-                    float lambda_isotropic = 0.0f);
+                    float lambda_isotropic = 0.0f, const float *jac = nullptr);
+// jac: what preprocess3d_impl stored for THIS state in the same host call (scorp_gs3d_train_view_ex); the per-Gaussian
+// kernel then reads it instead of the SH rows.  Not for an `adam` that updates the SH leaves: that path reads the rows anyway.
 // ---- the late iterations' loss terms (depth_terms.hip): checked arguments in, launches out; `scales` NULL: no isotropic value
 int view_terms_impl(int W, int H, const float *depth_raw, const float *alpha, const float *sensor, const float *est,
                     float w_sensor, float w_est, const float *scales, int N, int raw, float lambda_iso, float *out_terms4,

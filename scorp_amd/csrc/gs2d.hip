@@ -1087,8 +1087,7 @@ __device__ __forceinline__ void preprocess2d_backward_body(const Pg2Args &a, flo
   if (visible && a.shs) {
     float gdir[3] = {0, 0, 0};
     sh_row_backward<DEG>(row, shx, shy, shz, gr3, want_sh_grad, gdir);
-    const float dot = shx * gdir[0] + shy * gdir[1] + shz * gdir[2];
-    gm[0] += (gdir[0] - shx * dot) * shinv; gm[1] += (gdir[1] - shy * dot) * shinv; gm[2] += (gdir[2] - shz * dot) * shinv;
+    sh_dir_to_mean(shx, shy, shz, shinv, gdir, gm);
   } else if (want_sh_grad && active) {
     sh_row_zero(row);
   }

@@ -579,10 +579,12 @@ using namespace scorp;
 
 extern "C" size_t scorp_gs3d_backward_scratch_bytes_ex(int32_t N, int32_t W, int32_t H, uint64_t capacity, uint32_t flags) {
   (void)W; (void)H;
-  return backward_scratch_bytes(N, capacity, flags, kAccStride);
+  return backward_scratch_bytes(N, capacity, flags, kAccStride) + sh_jacobian_bytes(N);
 }
 
-extern "C" size_t scorp_gs3d_backward_scratch_bytes(int32_t N) { return backward_scratch_bytes(N, 0, 0u, kAccStride); }
+extern "C" size_t scorp_gs3d_backward_scratch_bytes(int32_t N) {
+  return backward_scratch_bytes(N, 0, 0u, kAccStride) + sh_jacobian_bytes(N);
+}
 
 extern "C" int scorp_gs3d_backward(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                                    const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
@@ -604,7 +606,7 @@ extern "C" int scorp_gs3d_backward_ex(const ScorpGs3dInputs *in, const void *sta
 int scorp::backward3d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                            const float *dL_dcolor, const float *dL_ddepth, const float *dL_dalpha,
                            const ScorpGs3dGrads *grads, void *scratch, size_t scratch_bytes, uint32_t flags,
-                           scorp_stream_t stream_, const AdamEpi *adam, float lambda_isotropic) {
+                           scorp_stream_t stream_, const AdamEpi *adam, float lambda_isotropic, const float *jac) {
   hipStream_t stream = (hipStream_t)stream_;
   const char *base = (const char *)state, *pb = (const char *)pairs;
   auto blend = [&](const StateLayout &L, const PairLayout &P, float *acc, float *partial, uint8_t *row_flags, uint32_t *pair_base) {
@@ -627,7 +629,7 @@ int scorp::backward3d_impl(const ScorpGs3dInputs *in, const void *state, const v
         (const BinRec *)(base + L.bin), (const uint64_t *)(base + L.tile_mask));
   };
   auto per_gaussian = [&](const StateLayout &L, const float *acc) {
-    launch_preprocess_backward(in, L, (const BinRec *)(base + L.bin), acc, grads, stream, adam, lambda_isotropic);
+    launch_preprocess_backward(in, L, (const BinRec *)(base + L.bin), acc, grads, stream, adam, lambda_isotropic, jac);
   };
   return backward_pass(kGs3d, in, state, pairs, capacity, dL_dcolor, grads, scratch, scratch_bytes, flags, stream, blend,
                        per_gaussian);

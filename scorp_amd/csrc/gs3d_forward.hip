@@ -294,11 +294,11 @@ extern "C" int scorp_gs3d_preprocess(const ScorpGs3dInputs *in, int32_t *out_rad
 }
 
 int scorp::preprocess3d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, uint8_t *out_visible, void *state,
-                             size_t state_bytes, scorp_stream_t stream_) {
+                             size_t state_bytes, scorp_stream_t stream_, float *jac) {
   hipStream_t stream = (hipStream_t)stream_;
   return preprocess_pass(kGs3d, in, out_radii, state, state_bytes, stream, [&](const StateLayout &L, char *base) {
     launch_preprocess(in, L, (SplatRec *)(base + L.rec), (BinRec *)(base + L.bin), (uint64_t *)(base + L.tile_mask), out_radii,
-                      (uint32_t *)(base + L.tile_count), out_visible, stream);
+                      (uint32_t *)(base + L.tile_count), out_visible, stream, jac);
   });
 }
 

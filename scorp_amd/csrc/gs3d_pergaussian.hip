@@ -28,6 +28,8 @@ struct PgArgs {
   const float *view, *proj, *campos;
   const float *means3D, *shs, *shs_rest, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
   uint8_t *visible;   // optional: radii > 0 as bytes (render()'s visibility_filter)
+  float *jac;         // the one-call view: d(rgb)/d(dir) of the visible Gaussians of FULL workgroups, nine planes of
+                      // sh_jacobian_plane(N) floats (written by the forward's JAC instantiation, read by the backward's)
   int views;          // > 1: blockIdx.y = view; N, H, tiles_y are those of ONE view, the outputs those of the stacked image
 };
 
@@ -172,11 +174,19 @@ __device__ __forceinline__ void emit_splat(const PgArgs &a, int i, const SplatGe
   if (a.visible) a.visible[i] = radius_out > 0 ? 1 : 0;
 }
 
+// The workgroups that take the LIN bodies below: full ones of the training layout.  ONE predicate for the forward and the
+// backward: the forward's LIN workgroups are the ones that store the Jacobian, the backward's the ones that read it.
+__device__ __forceinline__ bool lin_block(const PgArgs &a) {
+  return a.shs != nullptr && a.K == 16 && !a.cov3D_precomp && a.N - (int)blockIdx.x * 256 >= 256;
+}
+
 // LIN: a full block of the split K = 16 layout, whose SH rows go to LDS with direct global -> LDS loads.  It is a
 // separate instantiation so that the compiler sees ONE straight path "parameter loads, 12 LDS loads per wave, maths":
 // its wait for the parameters then is vmcnt(12) and the 48 KiB stream overlaps the projection maths (with the runtime
 // flag the paths merged and the wait was vmcnt(0): the maths started only after the whole stream had landed).
-template <int DEG, bool SPLIT, bool LIN>
+// JAC (LIN only): the visible Gaussians also store d(rgb)/d(dir) - the rows are in LDS and the direction in registers
+// here; the backward of the same view then never reads the rows (sh_dir_jacobian, pergaussian.hpp).
+template <int DEG, bool SPLIT, bool LIN, bool JAC = false>
 __device__ __forceinline__ void preprocess_body(const PgArgs &a, float *s_sh, SplatRec *__restrict__ rec,
                                                 BinRec *__restrict__ bin, uint64_t *__restrict__ tile_mask,
                                                 int32_t *__restrict__ radii, uint32_t *__restrict__ tile_count) {
@@ -261,6 +271,24 @@ __device__ __forceinline__ void preprocess_body(const PgArgs &a, float *s_sh, Sp
           if (rgb[q] < 0.0f) clamp_bits |= 1 << q;  // remembered for the backward (zero gradient where clamped)
           rgb[q] = fmaxf(rgb[q], 0.0f);
         }
+        if constexpr (JAC) {
+          static_assert(LIN, "the Jacobian is stored by full workgroups only");
+          // sh_row_to_rgb above is contracted by the compiler, and which of its products it fuses depends on who else uses
+          // them: the Jacobian gets opaque copies of the position, so that it shares no product with the colour and the
+          // colour keeps the bits it has in preprocess_kernel
+          // ... and the direction is formed again the way the backward forms it (sh_view_dir: its sum of squares is fused,
+          // the one above is not), so that the Jacobian is the backward's own to the bit
+          float jp0 = px_, jp1 = py_, jp2 = pz_, jx, jy, jz, jinv;
+          asm volatile("" : "+v"(jp0), "+v"(jp1), "+v"(jp2));
+          sh_view_dir(jp0, jp1, jp2, cc[0], cc[1], cc[2], jx, jy, jz, jinv);
+          float J[9];
+          sh_dir_jacobian<DEG>(sh_row(s_sh, threadIdx.x, lin), jx, jy, jz, J);
+          // one dword per lane and plane: coalesced; written once, read once by the backward > 1 GB of traffic later
+          float *jp = a.jac + i;
+          const size_t plane = sh_jacobian_plane(a.N);
+#pragma unroll
+          for (int q = 0; q < 9; q++) __builtin_nontemporal_store(J[q], jp + q * plane);
+        }
       }
     }
   } else if (vis) {
@@ -277,12 +305,25 @@ preprocess_kernel(PgArgs a, SplatRec *__restrict__ rec, BinRec *__restrict__ bin
                   int32_t *__restrict__ radii, uint32_t *__restrict__ tile_count) {
   __shared__ __attribute__((aligned(16))) float s_sh[DEG == 0 ? 4 : 256 * kShStride];   // direct global->LDS loads land 16-byte words
   if constexpr (SPLIT && DEG == 3) {
-    if (a.shs != nullptr && a.K == 16 && !a.cov3D_precomp && a.N - (int)blockIdx.x * 256 >= 256) {
+    if (lin_block(a)) {
       preprocess_body<DEG, SPLIT, true>(a, s_sh, rec, bin, tile_mask, radii, tile_count);
       return;
     }
   }
   preprocess_body<DEG, SPLIT, false>(a, s_sh, rec, bin, tile_mask, radii, tile_count);
+}
+
+// preprocess_kernel<3, true> of the one-call view: its full workgroups also store d(rgb)/d(dir) into a.jac.  A kernel of
+// its own, so that every other caller runs the code it always ran.
+__global__ void __launch_bounds__(256)
+preprocess_jac_kernel(PgArgs a, SplatRec *__restrict__ rec, BinRec *__restrict__ bin, uint64_t *__restrict__ tile_mask,
+                      int32_t *__restrict__ radii, uint32_t *__restrict__ tile_count) {
+  __shared__ __attribute__((aligned(16))) float s_sh[256 * kShStride];
+  if (lin_block(a)) {
+    preprocess_body<3, true, true, true>(a, s_sh, rec, bin, tile_mask, radii, tile_count);
+    return;
+  }
+  preprocess_body<3, true, false>(a, s_sh, rec, bin, tile_mask, radii, tile_count);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -292,7 +333,9 @@ preprocess_kernel(PgArgs a, SplatRec *__restrict__ rec, BinRec *__restrict__ bin
 // would sit behind the 48 KiB stream (the compiler waits with vmcnt(0) while LDS-DMA loads are pending).
 // ISO: the isotropic regulariser's gradient (train_3dgs.py:146-148) joins the scaling gradient of EVERY Gaussian of the
 // block, visible or not; iso_k = lambda_isotropic / (9 N).  The plain instantiations do not know it exists.
-template <int DEG, bool SPLIT, bool LIN, bool ISO = false>
+// JAC (LIN only; the one-call view, whose forward stored d(rgb)/d(dir)): no SH row is read at all - the nine floats come
+// with the other per-Gaussian loads, and since no LDS-DMA stream is pending the loads are ordinary, compiler-tracked ones.
+template <int DEG, bool SPLIT, bool LIN, bool ISO = false, bool JAC = false>
 __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float *s_sh, const BinRec *__restrict__ bin,
                                                          const float *__restrict__ acc, const ScorpGs3dGrads &g, const AdamEpi &ad,
                                                          float iso_k = 0.0f) {
@@ -303,7 +346,25 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
   constexpr int NFL = 3 * (DEG + 1) * (DEG + 1);
   float pre[11], pre_acc[11];   // LIN: means 0-2, rotation 3-6, scale 7-9, opacity 10 | accumulators 0-9, radius word 10
   int32_t rad_bits = 0;
-  if constexpr (LIN) {
+  float jac[9];
+  if constexpr (JAC) {
+    static_assert(LIN, "the Jacobian is read by full workgroups only");
+    const float4 *ap = reinterpret_cast<const float4 *>(acc + (size_t)i * kAccStride);
+    const float4 a0 = ap[0], a1 = ap[1];
+    const float2 a2 = *reinterpret_cast<const float2 *>(ap + 2);
+    const float4 q_in = reinterpret_cast<const float4 *>(a.rotations)[i];
+    rad_bits = bin[i].radius;
+    const float *jp = a.jac + i;
+    const size_t plane = sh_jacobian_plane(a.N);
+#pragma unroll
+    for (int q = 0; q < 9; q++) jac[q] = __builtin_nontemporal_load(jp + q * plane);
+#pragma unroll
+    for (int q = 0; q < 3; q++) { pre[q] = a.means3D[3 * (size_t)i + q]; pre[7 + q] = a.scales[3 * (size_t)i + q]; }
+    pre[3] = q_in.x; pre[4] = q_in.y; pre[5] = q_in.z; pre[6] = q_in.w;
+    pre[10] = a.opacities[i];
+    pre_acc[0] = a0.x; pre_acc[1] = a0.y; pre_acc[2] = a0.z; pre_acc[3] = a0.w; pre_acc[4] = a1.x; pre_acc[5] = a1.y;
+    pre_acc[6] = a1.z; pre_acc[7] = a1.w; pre_acc[8] = a2.x; pre_acc[9] = a2.y; pre_acc[10] = 0.0f;
+  } else if constexpr (LIN) {
     RawParams r, ra;
     raw_issue_params(r, a.means3D + 3 * (size_t)i, a.rotations + 4 * (size_t)i, a.scales + 3 * (size_t)i, a.opacities + i);
     static_assert(kAccStride >= 10, "accumulator row: 10 floats used here");
@@ -357,9 +418,7 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
     if (a.shs) {
       const float p0 = LIN ? pre[0] : a.means3D[3 * (size_t)i], p1 = LIN ? pre[1] : a.means3D[3 * (size_t)i + 1],
                   p2 = LIN ? pre[2] : a.means3D[3 * (size_t)i + 2];
-      const float d0 = p0 - ((const CFloat *)a.campos)[0], d1 = p1 - ((const CFloat *)a.campos)[1], d2_ = p2 - ((const CFloat *)a.campos)[2];
-      shinv = 1.0f / sqrtf(d0 * d0 + d1 * d1 + d2_ * d2_);
-      shx = d0 * shinv; shy = d1 * shinv; shz = d2_ * shinv;
+      sh_view_dir(p0, p1, p2, ((const CFloat *)a.campos)[0], ((const CFloat *)a.campos)[1], ((const CFloat *)a.campos)[2], shx, shy, shz, shinv);
 #pragma unroll
       for (int ch = 0; ch < 3; ch++) gr3[ch] = ((rad_bits >> (kClampShift + ch)) & 1) ? 0.0f : a_[6 + ch];
     }
@@ -485,9 +544,7 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
       g_op *= o * (1.0f - o);
     }
     if (a.shs) {   // the SH part itself runs after the rows have landed in LDS (below)
-      const float d0 = p0 - ((const CFloat *)a.campos)[0], d1 = p1 - ((const CFloat *)a.campos)[1], d2_ = p2 - ((const CFloat *)a.campos)[2];
-      shinv = 1.0f / sqrtf(d0 * d0 + d1 * d1 + d2_ * d2_);
-      shx = d0 * shinv; shy = d1 * shinv; shz = d2_ * shinv;
+      sh_view_dir(p0, p1, p2, ((const CFloat *)a.campos)[0], ((const CFloat *)a.campos)[1], ((const CFloat *)a.campos)[2], shx, shy, shz, shinv);
 #pragma unroll
       for (int ch = 0; ch < 3; ch++) gr3[ch] = ((rad_bits >> (kClampShift + ch)) & 1) ? 0.0f : a_[6 + ch];
     }
@@ -545,7 +602,9 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
       }
     }
   }
-  if (a.shs && lin) { stage_sh_wait(); __syncthreads(); }
+  if constexpr (!JAC) {
+    if (a.shs && lin) { stage_sh_wait(); __syncthreads(); }
+  }
   AdamGeomMoments am;   // asked for here, used in the epilogue: the SH phase in between hides the latency
   const bool adam_pre = SPLIT && adam_on && active;
   if (adam_pre) {
@@ -556,9 +615,9 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
   }
   if (visible && a.shs) {
     float gdir[3] = {0, 0, 0};
-    sh_row_backward<DEG>(row, shx, shy, shz, gr3, want_sh_grad, gdir);
-    const float dot = shx * gdir[0] + shy * gdir[1] + shz * gdir[2];
-    gm[0] += (gdir[0] - shx * dot) * shinv; gm[1] += (gdir[1] - shy * dot) * shinv; gm[2] += (gdir[2] - shz * dot) * shinv;
+    if constexpr (JAC) sh_row_backward_jac<DEG>(row, shx, shy, shz, gr3, jac, want_sh_grad, gdir);
+    else sh_row_backward<DEG>(row, shx, shy, shz, gr3, want_sh_grad, gdir);
+    sh_dir_to_mean(shx, shy, shz, shinv, gdir, gm);
   } else if (want_sh_grad && active) {
     sh_row_zero(row);
   }
@@ -626,7 +685,7 @@ preprocess_backward_kernel(PgArgs a, const BinRec *__restrict__ bin, const float
                            ScorpGs3dGrads g, AdamEpi ad) {
   __shared__ __attribute__((aligned(16))) float s_sh[256 * kShStride];   // direct global->LDS loads land 16-byte words
   if constexpr (SPLIT && DEG == 3) {
-    if (a.shs != nullptr && a.K == 16 && !a.cov3D_precomp && a.N - (int)blockIdx.x * 256 >= 256) {
+    if (lin_block(a)) {
       preprocess_backward_body<DEG, SPLIT, true>(a, s_sh, bin, acc, g, ad);
       return;
     }
@@ -641,12 +700,26 @@ preprocess_backward_iso_kernel(PgArgs a, const BinRec *__restrict__ bin, const f
                                AdamEpi ad, float iso_k) {
   __shared__ __attribute__((aligned(16))) float s_sh[256 * kShStride];
   if constexpr (DEG == 3) {
-    if (a.K == 16 && a.N - (int)blockIdx.x * 256 >= 256) {
+    if (lin_block(a)) {   // (shs given, no cov3D_precomp: the launcher checked)
       preprocess_backward_body<DEG, true, true, true>(a, s_sh, bin, acc, g, ad, iso_k);
       return;
     }
   }
   preprocess_backward_body<DEG, true, false, true>(a, s_sh, bin, acc, g, ad, iso_k);
+}
+
+// preprocess_backward_kernel<3, true> / preprocess_backward_iso_kernel<3> of the one-call view whose forward was
+// preprocess_jac_kernel: the full workgroups read a.jac and no SH row, the last, partial one reads its rows as ever.
+template <bool ISO>
+__global__ void __launch_bounds__(256)
+preprocess_backward_jac_kernel(PgArgs a, const BinRec *__restrict__ bin, const float *__restrict__ acc, ScorpGs3dGrads g,
+                               AdamEpi ad, float iso_k) {
+  __shared__ __attribute__((aligned(16))) float s_sh[256 * kShStride];
+  if (lin_block(a)) {
+    preprocess_backward_body<3, true, true, ISO, true>(a, s_sh, bin, acc, g, ad, iso_k);
+    return;
+  }
+  preprocess_backward_body<3, true, false, ISO>(a, s_sh, bin, acc, g, ad, iso_k);
 }
 
 PgArgs make_args(const ScorpGs3dInputs *in, const StateLayout &L) {
@@ -658,6 +731,7 @@ PgArgs make_args(const ScorpGs3dInputs *in, const StateLayout &L) {
   a.means3D = in->means3D; a.shs = in->shs; a.shs_rest = in->shs_rest; a.colors_precomp = in->colors_precomp;
   a.opacities = in->opacities; a.scales = in->scales; a.rotations = in->rotations; a.cov3D_precomp = in->cov3D_precomp;
   a.visible = nullptr;
+  a.jac = nullptr;
   a.views = in->num_views > 1 ? in->num_views : 1;
   if (a.views > 1) a.tiles_y = L.tiles_y / a.views;   // (L describes the stacked image)
   return a;
@@ -666,20 +740,27 @@ PgArgs make_args(const ScorpGs3dInputs *in, const StateLayout &L) {
 }  // namespace
 
 void launch_preprocess(const ScorpGs3dInputs *in, const StateLayout &L, SplatRec *rec, BinRec *bin, uint64_t *tile_mask,
-                       int32_t *radii, uint32_t *tile_count, uint8_t *out_visible, hipStream_t stream) {
+                       int32_t *radii, uint32_t *tile_count, uint8_t *out_visible, hipStream_t stream, float *jac) {
   PgArgs a = make_args(in, L);
   a.visible = out_visible;
   const dim3 grid((a.N + 255) / 256, a.views), block(256);
   const int deg = in->shs ? in->sh_degree : 0;
   const bool split = in->shs_rest != nullptr;
+  if (jac) {   // (the caller checked the layout: sh_jacobian_layout_ok)
+    a.jac = jac;
+    preprocess_jac_kernel<<<grid, block, 0, stream>>>(a, rec, bin, tile_mask, radii, tile_count);
+    return;
+  }
   dispatch_sh_degree(deg, split, [&](auto D, auto S) {
     preprocess_kernel<D, S><<<grid, block, 0, stream>>>(a, rec, bin, tile_mask, radii, tile_count);
   });
 }
 
 void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L, const BinRec *bin, const float *acc,
-                                const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam, float lambda_isotropic) {
-  const PgArgs a = make_args(in, L);
+                                const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam, float lambda_isotropic,
+                                const float *jac) {
+  PgArgs a = make_args(in, L);
+  a.jac = const_cast<float *>(jac);   // (given only for the layout of sh_jacobian_layout_ok)
   const dim3 grid((a.N + 255) / 256), block(256);
   const int deg = in->shs ? in->sh_degree : 0;
   const bool split = in->shs_rest != nullptr;
@@ -689,9 +770,17 @@ void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L,
   if (adam && split) ad = *adam;   // (the fused step is defined for the training layout: dc / rest split leaves)
   if (lambda_isotropic != 0.0f && split && in->shs && in->scales && !in->cov3D_precomp) {   // (the caller checked the layout)
     const float iso_k = (float)((double)lambda_isotropic / (9.0 * (double)a.N));
+    if (jac) {
+      preprocess_backward_jac_kernel<true><<<grid, block, 0, stream>>>(a, bin, acc, g, ad, iso_k);
+      return;
+    }
     dispatch_sh_degree(deg, true, [&](auto D, auto) {
       preprocess_backward_iso_kernel<D><<<grid, block, 0, stream>>>(a, bin, acc, g, ad, iso_k);
     });
+    return;
+  }
+  if (jac) {
+    preprocess_backward_jac_kernel<false><<<grid, block, 0, stream>>>(a, bin, acc, g, ad, 0.0f);
     return;
   }
   dispatch_sh_degree(deg, split, [&](auto D, auto S) {

@@ -226,59 +226,119 @@ __device__ __forceinline__ void sh_row_to_rgb(ShRow row, float x, float y, float
 }
 
 
-// Backward of sh_row_to_rgb for one staged row: gr[ch] = dL/d(colour ch) after the clamp mask.  Accumulates
-// dL/d(unit direction) into gdir and, if write_grad, overwrites the row IN PLACE with dL/d(coefficients)
-// (each channel's coefficients are consumed before they are overwritten).
+// d(colour)/d(unit direction) of sh_row_to_rgb for one staged row: J[3 * ch + 0..2] = (rx, ry, rz) of channel ch.
+// ONE definition for every kernel that forms it - the per-Gaussian forward of the one-call view stores it, the backward
+// either reads that or forms it here again - and the two must agree to the bit, so nothing is left to the compiler's
+// contraction: it is off, and every fused step is an explicit fma.  The steps are the ones the compiler chose for the
+// backward while it still formed rx, ry, rz in place (a sum t1 + t2 + ... + tn becomes fma(tn, ... fma(t3, fma(t1, t2)))
+// with t2 rounded as a product, the degree-1 product takes the degree-2 sum as its addend, the degree-3 sum is added).
 template <int DEG>
-__device__ __forceinline__ void sh_row_backward(ShRow srow, float x, float y, float z, const float *gr3,
-                                                bool write_grad, float *gdir) {
+__device__ __forceinline__ void sh_dir_jacobian(ShRow srow, float x, float y, float z, float *J) {
+#pragma clang fp contract(off)
+  const float *row = srow.pr;
+  const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+  const float xx_yy = __builtin_fmaf(x, x, -yy);   // xx - yy
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    float rx = 0, ry = 0, rz = 0;
+    if constexpr (DEG == 1) {
+      rx = -SH_C1 * row[9 + ch]; ry = -SH_C1 * row[3 + ch]; rz = SH_C1 * row[6 + ch];
+    }
+    if constexpr (DEG > 1) {
+      const float s1_ = row[3 + ch], s2_ = row[6 + ch], s3_ = row[9 + ch];
+      const float s4 = row[12 + ch], s5 = row[15 + ch], s6 = row[18 + ch], s7 = row[21 + ch], s8 = row[24 + ch];
+      float ax = SH_C2[2] * 2 * -x * s6, ay = SH_C2[1] * z * s5, az = SH_C2[2] * 4 * z * s6;
+      ax = __builtin_fmaf(SH_C2[0] * y, s4, ax); ax = __builtin_fmaf(SH_C2[3] * z, s7, ax); ax = __builtin_fmaf(SH_C2[4] * 2 * x, s8, ax);
+      ay = __builtin_fmaf(SH_C2[0] * x, s4, ay); ay = __builtin_fmaf(SH_C2[2] * 2 * -y, s6, ay); ay = __builtin_fmaf(SH_C2[4] * 2 * -y, s8, ay);
+      az = __builtin_fmaf(SH_C2[1] * y, s5, az); az = __builtin_fmaf(SH_C2[3] * x, s7, az);
+      rx = __builtin_fmaf(-SH_C1, s3_, ax); ry = __builtin_fmaf(-SH_C1, s1_, ay); rz = __builtin_fmaf(SH_C1, s2_, az);
+    }
+    if constexpr (DEG > 2) {
+      const float s9 = row[27 + ch], s10 = row[30 + ch], s11 = row[33 + ch], s12 = row[36 + ch], s13 = row[39 + ch],
+                  s14 = row[42 + ch], s15 = row[45 + ch];
+      float bx = SH_C3[1] * s10 * yz, by = SH_C3[1] * s10 * xz, bz = SH_C3[2] * s11 * 8 * yz;
+      bx = __builtin_fmaf(SH_C3[0] * s9 * 6, xy, bx); bx = __builtin_fmaf(SH_C3[2] * s11 * -2, xy, bx);
+      bx = __builtin_fmaf(SH_C3[3] * s12 * -6, xz, bx);
+      bx = __builtin_fmaf(SH_C3[4] * s13, __builtin_fmaf(-y, y, __builtin_fmaf(4.0f, zz, -3 * xx)), bx);   // -3 xx + 4 zz - yy
+      bx = __builtin_fmaf(SH_C3[5] * s14 * 2, xz, bx); bx = __builtin_fmaf(SH_C3[6] * s15 * 3, xx_yy, bx);
+      by = __builtin_fmaf(SH_C3[0] * s9 * 3, xx_yy, by);
+      by = __builtin_fmaf(SH_C3[2] * s11, __builtin_fmaf(-x, x, __builtin_fmaf(4.0f, zz, -3 * yy)), by);   // -3 yy + 4 zz - xx
+      by = __builtin_fmaf(SH_C3[3] * s12 * -6, yz, by); by = __builtin_fmaf(SH_C3[4] * s13 * -2, xy, by);
+      by = __builtin_fmaf(SH_C3[5] * s14 * -2, yz, by); by = __builtin_fmaf(SH_C3[6] * s15 * -6, xy, by);
+      bz = __builtin_fmaf(SH_C3[1] * s10, xy, bz);
+      bz = __builtin_fmaf(SH_C3[3] * s12 * 3, __builtin_fmaf(-y, y, __builtin_fmaf(2.0f, zz, -xx)), bz);   // 2 zz - xx - yy
+      bz = __builtin_fmaf(SH_C3[4] * s13 * 8, xz, bz); bz = __builtin_fmaf(SH_C3[5] * s14, xx_yy, bz);
+      rx = rx + bx; ry = ry + by; rz = rz + bz;
+    }
+    J[3 * ch] = rx; J[3 * ch + 1] = ry; J[3 * ch + 2] = rz;
+  }
+}
+
+// Backward of sh_row_to_rgb with the Jacobian at hand: gr[ch] = dL/d(colour ch) after the clamp mask.  Accumulates
+// dL/d(unit direction) into gdir and, if write_grad, writes dL/d(coefficients) = basis * gr into the row (no coefficient
+// is read).
+template <int DEG>
+__device__ __forceinline__ void sh_row_backward_jac(ShRow srow, float x, float y, float z, const float *gr3, const float *J,
+                                                    bool write_grad, float *gdir) {
+#pragma clang fp contract(off)   // (the basis too: which of its sums the compiler fuses depended on what else used xx, yy, zz)
         float *row = srow.pr;
         const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
         float basis[16];
         basis[0] = SH_C0;
         if constexpr (DEG > 0) { basis[1] = -SH_C1 * y; basis[2] = SH_C1 * z; basis[3] = -SH_C1 * x; }
         if constexpr (DEG > 1) {
-          basis[4] = SH_C2[0] * xy; basis[5] = SH_C2[1] * yz; basis[6] = SH_C2[2] * (2 * zz - xx - yy);
-          basis[7] = SH_C2[3] * xz; basis[8] = SH_C2[4] * (xx - yy);
+          basis[4] = SH_C2[0] * xy; basis[5] = SH_C2[1] * yz;
+          basis[6] = SH_C2[2] * __builtin_fmaf(-y, y, __builtin_fmaf(2.0f, zz, -xx));   // 2 zz - xx - yy
+          basis[7] = SH_C2[3] * xz; basis[8] = SH_C2[4] * __builtin_fmaf(x, x, -yy);
         }
         if constexpr (DEG > 2) {
-          basis[9] = SH_C3[0] * y * (3 * xx - yy); basis[10] = SH_C3[1] * xy * z;
-          basis[11] = SH_C3[2] * y * (4 * zz - xx - yy); basis[12] = SH_C3[3] * z * (2 * zz - 3 * xx - 3 * yy);
-          basis[13] = SH_C3[4] * x * (4 * zz - xx - yy); basis[14] = SH_C3[5] * z * (xx - yy);
-          basis[15] = SH_C3[6] * x * (xx - 3 * yy);
+          const float w4 = __builtin_fmaf(-y, y, __builtin_fmaf(4.0f, zz, -xx));        // 4 zz - xx - yy
+          basis[9] = SH_C3[0] * y * __builtin_fmaf(3.0f, xx, -yy); basis[10] = SH_C3[1] * xy * z;
+          basis[11] = SH_C3[2] * y * w4;
+          basis[12] = SH_C3[3] * z * __builtin_fmaf(-3.0f, yy, __builtin_fmaf(2.0f, zz, -3 * xx));   // 2 zz - 3 xx - 3 yy
+          basis[13] = SH_C3[4] * x * w4; basis[14] = SH_C3[5] * z * __builtin_fmaf(x, x, -yy);
+          basis[15] = SH_C3[6] * x * __builtin_fmaf(-3.0f, yy, xx);
         }
   #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
           const float gr = gr3[ch];
-          float rx = 0, ry = 0, rz = 0;
-          if constexpr (DEG > 0) {
-            const float s1_ = row[3 + ch], s2_ = row[6 + ch], s3_ = row[9 + ch];
-            rx = -SH_C1 * s3_; ry = -SH_C1 * s1_; rz = SH_C1 * s2_;
-          }
-          if constexpr (DEG > 1) {
-            const float s4 = row[12 + ch], s5 = row[15 + ch], s6 = row[18 + ch], s7 = row[21 + ch], s8 = row[24 + ch];
-            rx += SH_C2[0] * y * s4 + SH_C2[2] * 2 * -x * s6 + SH_C2[3] * z * s7 + SH_C2[4] * 2 * x * s8;
-            ry += SH_C2[0] * x * s4 + SH_C2[1] * z * s5 + SH_C2[2] * 2 * -y * s6 + SH_C2[4] * 2 * -y * s8;
-            rz += SH_C2[1] * y * s5 + SH_C2[2] * 4 * z * s6 + SH_C2[3] * x * s7;
-          }
-          if constexpr (DEG > 2) {
-            const float s9 = row[27 + ch], s10 = row[30 + ch], s11 = row[33 + ch], s12 = row[36 + ch], s13 = row[39 + ch],
-                        s14 = row[42 + ch], s15 = row[45 + ch];
-            rx += SH_C3[0] * s9 * 6 * xy + SH_C3[1] * s10 * yz + SH_C3[2] * s11 * -2 * xy + SH_C3[3] * s12 * -6 * xz +
-                  SH_C3[4] * s13 * (-3 * xx + 4 * zz - yy) + SH_C3[5] * s14 * 2 * xz + SH_C3[6] * s15 * 3 * (xx - yy);
-            ry += SH_C3[0] * s9 * 3 * (xx - yy) + SH_C3[1] * s10 * xz + SH_C3[2] * s11 * (-3 * yy + 4 * zz - xx) +
-                  SH_C3[3] * s12 * -6 * yz + SH_C3[4] * s13 * -2 * xy + SH_C3[5] * s14 * -2 * yz + SH_C3[6] * s15 * -6 * xy;
-            rz += SH_C3[1] * s10 * xy + SH_C3[2] * s11 * 8 * yz + SH_C3[3] * s12 * 3 * (2 * zz - xx - yy) +
-                  SH_C3[4] * s13 * 8 * xz + SH_C3[5] * s14 * (xx - yy);
-          }
-          gdir[0] += rx * gr; gdir[1] += ry * gr; gdir[2] += rz * gr;
-          // the coefficients of this channel are consumed: overwrite them in place with their gradients
+          gdir[0] = __builtin_fmaf(J[3 * ch], gr, gdir[0]); gdir[1] = __builtin_fmaf(J[3 * ch + 1], gr, gdir[1]);
+          gdir[2] = __builtin_fmaf(J[3 * ch + 2], gr, gdir[2]);
           if (write_grad) {
   #pragma unroll
             for (int k = 1; k < 16; k++) row[3 * k + ch] = k < (DEG + 1) * (DEG + 1) ? basis[k] * gr : 0.0f;
             srow.p0[ch] = basis[0] * gr;
           }
         }
+}
+// ... and from the staged row itself: the Jacobian is formed first, then the row is overwritten IN PLACE with its gradient.
+template <int DEG>
+__device__ __forceinline__ void sh_row_backward(ShRow srow, float x, float y, float z, const float *gr3,
+                                                bool write_grad, float *gdir) {
+  float J[9];
+  sh_dir_jacobian<DEG>(srow, x, y, z, J);
+  sh_row_backward_jac<DEG>(srow, x, y, z, gr3, J, write_grad, gdir);
+}
+
+// The unit view direction the SH backward differentiates at, (p - campos) / |p - campos|, and inv = 1 / |p - campos|.  Pinned
+// (the sum of squares as the backward has always fused it): the forward of the one-call view forms the Jacobian at exactly
+// the direction its backward would have formed it at.  (sqrtf and the division are correctly rounded wherever they stand.)
+__device__ __forceinline__ void sh_view_dir(float p0, float p1, float p2, float c0, float c1, float c2, float &x, float &y,
+                                            float &z, float &inv) {
+#pragma clang fp contract(off)
+  const float d0 = p0 - c0, d1 = p1 - c1, d2 = p2 - c2;
+  inv = 1.0f / sqrtf(__builtin_fmaf(d2, d2, __builtin_fmaf(d0, d0, d1 * d1)));
+  x = d0 * inv; y = d1 * inv; z = d2 * inv;
+}
+
+// dL/d(unit direction) -> dL/d(mean) through d = (p - campos) / |p - campos| (inv = 1 / |p - campos|), added to gm.  Pinned like the
+// functions above: the callers (3DGS with the rows or with the stored Jacobian, 2DGS) give the same bits.
+__device__ __forceinline__ void sh_dir_to_mean(float x, float y, float z, float inv, const float *gdir, float *gm) {
+#pragma clang fp contract(off)
+  const float dot = __builtin_fmaf(z, gdir[2], __builtin_fmaf(x, gdir[0], y * gdir[1]));
+  gm[0] = __builtin_fmaf(__builtin_fmaf(-x, dot, gdir[0]), inv, gm[0]);
+  gm[1] = __builtin_fmaf(__builtin_fmaf(-y, dot, gdir[1]), inv, gm[1]);
+  gm[2] = __builtin_fmaf(__builtin_fmaf(-z, dot, gdir[2]), inv, gm[2]);
 }
 
 // ---- the optimizer step inside the per-Gaussian backward kernels (ScorpFusedAdam; 3-D and 2-D) ----

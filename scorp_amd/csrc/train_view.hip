@@ -87,7 +87,17 @@ extern "C" int scorp_gs3d_train_view_ex(const ScorpGs3dTrainView *v, const Scorp
   // render()'s tail (normalised depth, visibility filter) comes out of the per-Gaussian kernel and the blend forward's
   // epilogue: same values as scorp_gs3d_render_tail, one launch less per view
   const bool tail = v->out_depth && v->out_visible;
-  if (int e = preprocess3d_impl(in, v->out_radii, tail ? v->out_visible : nullptr, v->state, v->state_bytes, stream)) return e;
+  // d(rgb)/d(dir) goes from the per-Gaussian forward to the per-Gaussian backward behind the backward's own scratch layout,
+  // where this call owns both ends: the scratch holds the nine planes (a buffer sized by
+  // scorp_gs3d_backward_scratch_bytes[_ex] does), the layout is the training layout, and the optimizer step does not
+  // update the SH leaves inside the backward (that path reads the rows anyway).  Otherwise the backward reads the rows.
+  const size_t jac_off = scorp::backward_scratch_bytes(in->num_gaussians, v->capacity, v->backward_flags, kAccStride);
+  const bool adam_sh = v->adam && (v->adam->exp_avg[1] || v->adam->exp_avg[2]);
+  const bool jac_here = sh_jacobian_layout_ok(in) && v->backward_scratch && ((uintptr_t)v->backward_scratch & 15) == 0 &&
+                        v->backward_scratch_bytes >= jac_off && v->backward_scratch_bytes - jac_off >= sh_jacobian_bytes(in->num_gaussians) &&
+                        !adam_sh;
+  float *jac = jac_here ? reinterpret_cast<float *>((char *)v->backward_scratch + jac_off) : nullptr;
+  if (int e = preprocess3d_impl(in, v->out_radii, tail ? v->out_visible : nullptr, v->state, v->state_bytes, stream, jac)) return e;
   // ... and so do the zeros of the backward's accumulator rows (N x 64 bytes at the head of its scratch)
   const size_t acc_bytes = (size_t)(in->num_gaussians > 0 ? in->num_gaussians : 0) * kAccStride * sizeof(float);
   const bool zero_here = v->backward_scratch && acc_bytes > 0 && acc_bytes <= v->backward_scratch_bytes &&
@@ -114,7 +124,7 @@ extern "C" int scorp_gs3d_train_view_ex(const ScorpGs3dTrainView *v, const Scorp
   return backward3d_impl(in, v->state, v->pairs, v->capacity, v->grad_color, depth_terms ? terms->grad_depth_raw : nullptr,
                          depth_terms ? terms->grad_alpha : nullptr, v->grads, v->backward_scratch, v->backward_scratch_bytes,
                          (v->backward_flags & ~SCORP_BACKWARD_SCRATCH_ZEROED) | (zero_here ? SCORP_BACKWARD_SCRATCH_ZEROED : 0u),
-                         stream, v->adam ? &ad : nullptr, lambda_iso);
+                         stream, v->adam ? &ad : nullptr, lambda_iso, jac);
 }
 
 extern "C" int scorp_gs2d_train_view(const ScorpGs2dTrainView *v, scorp_stream_t stream) {
