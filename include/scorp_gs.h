@@ -83,8 +83,12 @@ typedef struct ScorpGs3dInputs {
    * entries ([V,16], [V,16], [V,3]), image_height is the height of ONE view (a multiple of 16) and every per-view size
    * is multiplied by V: the V images are rendered as one image of V * image_height rows (view v = rows
    * [v * image_height, (v + 1) * image_height)), Gaussian i of view v is "virtual Gaussian" v * N + i.  So
-   * out_radii is [V * N], color [3, V * H, W], depth / alpha [V * H, W]; state / pairs are sized with
-   * scorp_gs3d_state_bytes(V * N, W, V * H).  Forward only: scorp_gs3d_backward* refuse such inputs. */
+   * out_radii is [V * N], color [3, V * H, W], the 3DGS depth / alpha [V * H, W] and the 2DGS allmap [7, V * H, W];
+   * state / pairs are sized with scorp_gs3d_state_bytes / scorp_gs2d_state_bytes(V * N, W, V * H).  Both kinds read the
+   * field, with the same limits: V * N <= 2^31 - 1, V * H <= 16 * 65535, and the stacked image must stay on the LDS
+   * binning.  2DGS additionally refuses V > 1 with cov3D_precomp (a given splat->pixel transform belongs to one view).
+   * Forward only: scorp_gs3d_render / scorp_gs2d_render and scorp_gs3d_backward* / scorp_gs2d_backward* refuse such
+   * inputs; *_preprocess, *_render_image and *_render_score take them. */
   int32_t num_views;
 } ScorpGs3dInputs;
 
@@ -737,6 +741,15 @@ int scorp_gs2d_render(const ScorpGs3dInputs *in, void *state, void *pairs, uint6
 /* As scorp_gs3d_render_image: the same images with nothing left behind for scorp_gs2d_backward. */
 int scorp_gs2d_render_image(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, float *out_color,
                             float *out_allmap, scorp_stream_t stream);
+/* As scorp_gs3d_render_score (same bands, same argument checks, same fixed-order sums), with the surface depth the 2DGS
+ * renderer returns (gs2dgs/gaussian_renderer/__init__.py:139-154) in place of depth / alpha:
+ *   alpha = allmap[1],  depth = (1 - depth_ratio) * nan_to_num(allmap[0] / alpha, 0, 0) + depth_ratio * nan_to_num(allmap[5], 0, 0),
+ *   acc[j] += scale * sum over band j of |alpha - tgt_alpha| + |depth - tgt_depth|,
+ * each pixel's term formed with the fp32 operations of that expression in torch.  No colour, normal or distortion is
+ * accumulated and no image written.  depth_ratio (PipelineParams.depth_ratio) must be finite and in [0, 1]. */
+int scorp_gs2d_render_score(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, const float *tgt_depth,
+                            const float *tgt_alpha, int32_t rows_per_score, float depth_ratio, float scale, float *acc,
+                            scorp_stream_t stream);
 int scorp_gs2d_backward(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity,
                         const float *dL_dcolor, const float *dL_dallmap, const ScorpGs3dGrads *grads, void *scratch,
                         size_t scratch_bytes, scorp_stream_t stream);

@@ -12,7 +12,7 @@ import logging
 
 import torch
 
-from .rasterizer3d import PairPolicy
+from .rasterizer3d import PairOverflow, PairPolicy
 from .renderer import render
 from .transforms import gaussians_rotate
 
@@ -24,25 +24,98 @@ class _Pipe:
     fused_activations = True
 
 
+DEPTH_RATIO = 1.0   # the reference's PipelineParams.depth_ratio (gs2dgs/arguments/__init__.py): surfel renders only
+
+
+def _pipe(depth_ratio=DEPTH_RATIO, base=_Pipe):
+    p = base()
+    p.depth_ratio = float(depth_ratio)   # (read by renderer2d.render; the 3DGS renderer has no such setting)
+    return p
+
+
 @torch.no_grad()
-def render_views(model, cameras, bg, render_fn=render):
-    return [render_fn(c, model, _Pipe(), bg) for c in cameras]
+def render_views(model, cameras, bg, render_fn=render, depth_ratio=DEPTH_RATIO):
+    return [render_fn(c, model, _pipe(depth_ratio), bg) for c in cameras]
 
 
 class _RawPipe(_Pipe):
     raw_outputs = True      # renderer.render returns the un-normalised depth and skips the per-view tail launch
 
 
+def _is_surfel_model(model):
+    """segment._model_kind's test; anything that is neither model class (a test's stand-in) is not a surfel model."""
+    from .rasterizer3d import _GS2D
+    from .segment import _model_kind
+    try:
+        return _model_kind(model) is _GS2D
+    except TypeError:
+        return False
+
+
+def _is_surfel_render(model, render_fn):
+    """A surfel model rendered by the HIP 2DGS renderer."""
+    from . import renderer2d
+    return render_fn is renderer2d.render and _is_surfel_model(model)
+
+
+def _render_of(model, render_fn):
+    """The renderer of a sweep: a surfel model left at the default (the 3DGS `render`, which cannot draw it) gets
+    renderer2d.render, so that a caller hands over a GaussianModel2D without choosing anything."""
+    if render_fn is render and _is_surfel_model(model):
+        from . import renderer2d
+        return renderer2d.render
+    return render_fn
+
+
+def _one_stack(cameras):
+    """Cameras that can share a stacked image: one resolution and field of view, height a multiple of the tile."""
+    c0 = cameras[0]
+    return all(tuple(c.resolution) == tuple(c0.resolution) and c.FoVx == c0.FoVx and c.FoVy == c0.FoVy for c in cameras) \
+        and int(c0.resolution[1]) % 16 == 0
+
+
+class _StackedTargets:
+    """The cameras of a sweep as one ViewStack and its target renders in the stacked layout (normalised depth, alpha)."""
+
+    def __init__(self, cameras, targets, dev):
+        from .multiview import ViewStack
+        self.stack = ViewStack(cameras, dev)
+        H, W = self.stack.H, self.stack.W
+        self.t_depth = torch.cat([t["render_depth"].reshape(H, W) for t in targets]).contiguous()
+        self.t_alpha = torch.cat([t["render_alpha"].reshape(H, W) for t in targets]).contiguous()
+
+
 @torch.no_grad()
-def hypothesis_fitness(model, R, cameras, targets, bg, render_fn=render):
+def hypothesis_fitness(model, R, cameras, targets, bg, render_fn=render, depth_ratio=DEPTH_RATIO, stacked_targets=None):
     """Higher is better: minus the mean |alpha - alpha*| + |depth - depth*| over the cameras.  With the HIP
     rasterizer the comparison of a view is ONE launch on the rasterizer's raw outputs (`scorp_gs3d_pose_score_accumulate`:
     depth normalisation, both differences, both means and the running sum) instead of a tail launch and ~11 torch
-    kernels, which were 40 % of a 100k-Gaussian 800x800 view's time."""
+    kernels, which were 40 % of a 100k-Gaussian 800x800 view's time.  A surfel model on the GPU (renderer2d.render, cameras
+    of one resolution) is rotated the same way and then scored by ONE stacked launch set whose blend compares where it
+    forms depth and alpha (multiview.score_stacked -> scorp_gs2d_render_score; `stacked_targets`: a _StackedTargets built
+    once by the caller)."""
     m = copy.copy(model)
     m._xyz, m._rotation = model._xyz.detach().clone(), model._rotation.detach().clone()
     m._features_rest = model._features_rest.detach().clone()
     gaussians_rotate(m, R, fix_center=True)
+    if m._xyz.is_cuda and _is_surfel_render(m, render_fn) and _one_stack(cameras):
+        from .multiview import score_stacked
+        st = stacked_targets or _StackedTargets(cameras, targets, m._xyz.device)
+        s = st.stack
+        acc = torch.zeros(1, dtype=torch.float32, device=m._xyz.device)
+        args = (m, s, bg, s.view, s.proj, s.campos, st.t_depth, st.t_alpha, acc, s.V * s.H, 1.0 / st.t_alpha.numel())
+        if PairPolicy.mode != "exact":
+            score_stacked(*args, depth_ratio=depth_ratio)   # (the caller drains)
+            return -acc[0]
+        # score_stacked sizes its pair buffer from the reservation: verified here, once more after drain() has grown it
+        try:
+            score_stacked(*args, depth_ratio=depth_ratio)
+            PairPolicy.drain()
+        except PairOverflow:
+            acc.zero_()
+            score_stacked(*args, depth_ratio=depth_ratio)
+            PairPolicy.drain()
+        return -acc[0]
     if render_fn is render and m._xyz.is_cuda:
         import ctypes
         from . import _C
@@ -60,7 +133,7 @@ def hypothesis_fitness(model, R, cameras, targets, bg, render_fn=render):
         return -acc[0]
     err = 0.0
     for cam, tgt in zip(cameras, targets):
-        out = render_fn(cam, m, _Pipe(), bg)
+        out = render_fn(cam, m, _pipe(depth_ratio), bg)
         err = err + (out["render_alpha"] - tgt["render_alpha"]).abs().mean() + \
             (out["render_depth"] - tgt["render_depth"]).abs().mean()
     return -(err / len(cameras))
@@ -71,12 +144,15 @@ log = logging.getLogger("scorp_amd.align")
 
 def _stacked_ok(model, cameras, render_fn):
     """The camera-side form applies to SH-0 objects (view-independent colour: what align loads as `gaussian_generated`,
-    align_3dgs_clpe_9dof.py:307-308) rendered by the HIP rasterizer from cameras of one resolution."""
-    if render_fn is not render or not model._xyz.is_cuda or getattr(model, "max_sh_degree", 1) != 0:
+    align_3dgs_clpe_9dof.py:307-308, align_2dgs_clpe_9dof.py likewise) rendered by the HIP rasterizer of their kind -
+    `renderer.render`, or `renderer2d.render` for a GaussianModel2D - from cameras of one resolution."""
+    if not model._xyz.is_cuda or getattr(model, "max_sh_degree", 1) != 0:
         return False
-    c0 = cameras[0]
-    return all(tuple(c.resolution) == tuple(c0.resolution) and c.FoVx == c0.FoVx and c.FoVy == c0.FoVy for c in cameras) \
-        and int(c0.resolution[1]) % 16 == 0
+    if _is_surfel_render(model, render_fn):
+        return _one_stack(cameras)
+    if render_fn is not render or _is_surfel_model(model):   # (a surfel model under the 3DGS renderer: nothing to stack)
+        return False
+    return _one_stack(cameras)
 
 
 class StackedSweep:
@@ -93,11 +169,17 @@ class StackedSweep:
     from the doubled launch, the blend, which is 300 of the 567 us and bound by its own arithmetic, 4 %.  The sweep is not a
     chain of latency-bound launches any more; it costs what its 5.9 M (tile, splat) pairs per hypothesis cost.  With the
     scoring form of the blend (scorp_gs3d_render_score: no colour, no images, no score launch) a whole sweep of 128 runs at
-    1 830 / 1 965 / 2 001 hypotheses per second for batch = 1 / 2 / 3 (scripts/dev/prof_sweep.py; round 5: 1 580)."""
+    1 830 / 1 965 / 2 001 hypotheses per second for batch = 1 / 2 / 3 (scripts/dev/prof_sweep.py; round 5: 1 580).
 
-    def __init__(self, model, cameras, targets, bg, batch=None):
+    Surfel objects (GaussianModel2D) take the same path through the 2DGS kernels (`self.kind`; scorp_gs2d_render_score,
+    which compares the renderer's surface depth: `depth_ratio` mixes expected and median depth and must be the one the
+    targets were rendered with); scripts/time_sweep2d.py measures it against the per-view form."""
+
+    def __init__(self, model, cameras, targets, bg, batch=None, depth_ratio=DEPTH_RATIO):
         from .multiview import ViewStack
+        from .segment import _model_kind
         self.model, self.bg = model, bg
+        self.kind, self.depth_ratio = _model_kind(model), float(depth_ratio)
         self.dev = model._xyz.device
         self.stack = ViewStack(cameras, self.dev)
         # targets in the stacked layout (normalised depth, alpha), 16-byte aligned rows of the score kernel
@@ -140,7 +222,8 @@ class StackedSweep:
         while k < nh:
             h = min(self.batch, nh - k)
             score_stacked(self.model, self._stack_of(h), self.bg, view[k:k + h].reshape(h * V, 4, 4), proj[k:k + h].reshape(h * V, 4, 4),
-                          campos[k:k + h].reshape(h * V, 3), self.t_depth, self.t_alpha, acc[k:k + h], V * self.stack.H, 1.0 / n)
+                          campos[k:k + h].reshape(h * V, 3), self.t_depth, self.t_alpha, acc[k:k + h], V * self.stack.H, 1.0 / n,
+                          depth_ratio=self.depth_ratio)
             k += h
 
     def score(self, rotations, ids):
@@ -176,8 +259,11 @@ class SweepPlan:
     into a device-side maximum and checked once per `score()`.  With `use_graph=False` (CPU stand-in renderers, capture
     failures) hypotheses are scored with eager launches, each verified by PairPolicy.drain()."""
 
-    def __init__(self, model, cameras, targets, bg, use_graph=None, render_fn=render, stacked=None):
+    def __init__(self, model, cameras, targets, bg, use_graph=None, render_fn=render, stacked=None, depth_ratio=DEPTH_RATIO):
+        render_fn = _render_of(model, render_fn)
         self.model, self.cameras, self.targets, self.bg, self.render_fn = model, cameras, targets, bg, render_fn
+        self.depth_ratio = float(depth_ratio)   # surfel renders: the mix the targets were rendered with
+        self._stacked_targets = None            # the eager surfel form's ViewStack and stacked targets, built on first use
         self.dev = model._xyz.device
         self.graph = None
         # SH-0 object on the GPU: cameras are moved, not the object, and the views render as one stacked image
@@ -187,7 +273,7 @@ class SweepPlan:
         if stacked:
             if not _stacked_ok(model, cameras, render_fn):
                 raise ValueError("the stacked sweep needs an SH-0 GPU model and cameras of one resolution (height % 16 == 0)")
-            self.stacked = StackedSweep(model, cameras, targets, bg)
+            self.stacked = StackedSweep(model, cameras, targets, bg, depth_ratio=self.depth_ratio)
             self.reserve, self.fallback_reason = 0, None
             return
         self.reserve = 0        # this plan's pair-reservation floor: applied only inside its own calls (_reserved)
@@ -273,17 +359,20 @@ class SweepPlan:
         whose reservation overflowed is re-scored with exact sizing."""
         out = []
         on_gpu = self.dev.type == "cuda"
+        if on_gpu and self._stacked_targets is None and _is_surfel_render(self.model, self.render_fn) and _one_stack(self.cameras):
+            self._stacked_targets = _StackedTargets(self.cameras, self.targets, self.dev)
+        kw = dict(depth_ratio=self.depth_ratio, stacked_targets=self._stacked_targets)
         for i in ids:
             R = torch.as_tensor(rotations[i], dtype=torch.float32, device=self.dev)
             prev = PairPolicy.mode
             PairPolicy.mode = "reserve" if on_gpu else prev
             try:
-                f = hypothesis_fitness(self.model, R, self.cameras, self.targets, self.bg, self.render_fn)
+                f = hypothesis_fitness(self.model, R, self.cameras, self.targets, self.bg, self.render_fn, **kw)
                 if on_gpu:
                     PairPolicy.drain()
             except RuntimeError:
                 PairPolicy.mode = "exact"
-                f = hypothesis_fitness(self.model, R, self.cameras, self.targets, self.bg, self.render_fn)
+                f = hypothesis_fitness(self.model, R, self.cameras, self.targets, self.bg, self.render_fn, **kw)
             finally:
                 PairPolicy.mode = prev
             out.append(f.reshape(1).float())
@@ -309,7 +398,7 @@ def _to_device_or_reraise(rows, dev, err):
         raise err
 
 
-def align_objects(models, rotations, cameras, targets_per_object, bg, render_fn=render):
+def align_objects(models, rotations, cameras, targets_per_object, bg, render_fn=render, depth_ratio=DEPTH_RATIO):
     """The rotation sweep with the OBJECT as the unit of sharding (align_3dgs_clpe_9dof.py:489-499 loops over objects
     serially; they share no mutable state): object j -> rank j mod G, every rank sweeps all hypotheses of its objects
     locally, and ONE fixed-size all-gather of (object, best id, best fitness) tells every rank every result.
@@ -320,7 +409,8 @@ def align_objects(models, rotations, cameras, targets_per_object, bg, render_fn=
     rows, err = [], None
     try:
         for j in mine:
-            _, fit, best = rotation_sweep(models[j], rotations, cameras, targets_per_object[j], bg, render_fn=render_fn, shard=False)
+            _, fit, best = rotation_sweep(models[j], rotations, cameras, targets_per_object[j], bg, render_fn=render_fn, shard=False,
+                                          depth_ratio=depth_ratio)
             rows.append(torch.stack([torch.tensor(float(best), device=fit.device), fit[best, 0].float()]))
     except Exception as e:   # noqa: BLE001   (raised below, on every rank, behind the exchange)
         err, rows = e, None
@@ -335,7 +425,8 @@ def align_objects(models, rotations, cameras, targets_per_object, bg, render_fn=
     return [(int(vals[j, 0]), float(vals[j, 1])) for j in range(len(models))]
 
 
-def rotation_sweep(model, rotations, cameras, targets, bg, use_graph=None, plan=None, render_fn=render, shard=True):
+def rotation_sweep(model, rotations, cameras, targets, bg, use_graph=None, plan=None, render_fn=render, shard=True,
+                   depth_ratio=DEPTH_RATIO):
     """Score every rotation hypothesis (hypothesis j -> rank j mod world, one all-gather of (id, fitness) at the end);
     returns (ids, fitness[n,1], best id) on every rank.  `plan`: a SweepPlan built earlier (its graph capture is then
     outside the caller's timed region).  `shard=False`: this rank scores every hypothesis itself (align_objects)."""
@@ -343,7 +434,7 @@ def rotation_sweep(model, rotations, cameras, targets, bg, use_graph=None, plan=
     dev = model._xyz.device
     if not shard:
         if plan is None:
-            plan = SweepPlan(model, cameras, targets, bg, use_graph=use_graph, render_fn=render_fn)
+            plan = SweepPlan(model, cameras, targets, bg, use_graph=use_graph, render_fn=render_fn, depth_ratio=depth_ratio)
         ids = list(range(len(rotations)))
         scores = torch.stack(plan.score(rotations, ids)) if ids else torch.zeros((0, 1), dtype=torch.float32, device=dev)
         return torch.arange(len(ids), device=scores.device), scores, (int(torch.argmax(scores[:, 0])) if ids else -1)
@@ -351,7 +442,7 @@ def rotation_sweep(model, rotations, cameras, targets, bg, use_graph=None, plan=
     err = None
     try:
         if plan is None:
-            plan = SweepPlan(model, cameras, targets, bg, use_graph=use_graph, render_fn=render_fn)
+            plan = SweepPlan(model, cameras, targets, bg, use_graph=use_graph, render_fn=render_fn, depth_ratio=depth_ratio)
         vals = plan.score(rotations, mine) if mine else []
     except Exception as e:   # noqa: BLE001   (raised below, on every rank, behind the exchange)
         err, vals = e, None

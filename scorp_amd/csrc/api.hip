@@ -142,6 +142,9 @@ int validate(const GsKind &K, const ScorpGs3dInputs *in, int *views) {
       const long long nt = (long long)in->num_views * in->num_gaussians, ht = (long long)in->num_views * in->image_height;
       if (in->image_height % kTile != 0) { set_error("num_views > 1 needs image_height to be a multiple of %d", kTile); return SCORP_ERR_INVALID; }
       if (nt > 0x7FFFFFFFll || ht > 16 * 65535ll) { set_error("num_views x N or num_views x H too large"); return SCORP_ERR_INVALID; }
+      if (K.mode2d && in->cov3D_precomp) {   // (a surfel's given transform maps to ONE view's pixels)
+        set_error("num_views > 1 with cov3D_precomp: a given 2DGS transform is view dependent"); return SCORP_ERR_INVALID;
+      }
       *views = in->num_views;
     }
   }
@@ -170,7 +173,10 @@ int render_frame(const GsKind &K, const ScorpGs3dInputs *in, void *state, void *
                  RenderFrame *f) {
   int V;
   if (int e = validate(K, in, &V)) return e;
-  if (V > 1 && for_backward) { set_error("num_views > 1 is forward only: use scorp_gs3d_render_image"); return SCORP_ERR_INVALID; }
+  if (V > 1 && for_backward) {
+    set_error("num_views > 1 is forward only: use %s", K.mode2d ? "scorp_gs2d_render_image" : "scorp_gs3d_render_image");
+    return SCORP_ERR_INVALID;
+  }
   if (int e = check_buffers(state, pairs, capacity)) return e;
   const int N = V * in->num_gaussians, W = in->image_width, H = V * in->image_height;
   *f = {V, N, W, H, (uint32_t)capacity, StateLayout(N, W, H, K.mode2d, V), PairLayout(capacity), (char *)state, (char *)pairs};

@@ -500,6 +500,13 @@ int backward3d_impl(const ScorpGs3dInputs *in, const void *state, const void *pa
 int view_terms_impl(int W, int H, const float *depth_raw, const float *alpha, const float *sensor, const float *est,
                     float w_sensor, float w_est, const float *scales, int N, int raw, float lambda_iso, float *out_terms4,
                     float *g_depth_raw, float *g_alpha, void *workspace, hipStream_t stream);
+// ---- the band sums of the scoring renders (scorp_gs3d_render_score, scorp_gs2d_render_score; gs3d_forward.hip):
+// acc[j] += scale * (block_terms[j * blocks_per_score .. (j + 1) * blocks_per_score) added in a fixed order), j < scores, in
+// two launches; `partial` holds scores x 128 floats, which the W x H floats of a state's final_T region do unless
+// score_bands_too_many(scores, W, H)
+bool score_bands_too_many(int scores, int W, int H);
+void launch_score_bands(const float *block_terms, int scores, int blocks_per_score, float *partial, float scale, float *acc,
+                        hipStream_t stream);
 int preprocess2d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, void *state, size_t state_bytes, scorp_stream_t stream);
 int render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity, float *out_color, float *out_allmap,
                   scorp_stream_t stream, bool for_backward);
@@ -586,7 +593,7 @@ void set_error(const char *fmt, ...);
 // What differs between the two kinds, apart from the launches each passes in.
 struct GsKind {
   bool mode2d;          // StateLayout of the 2DGS records and per-pixel state
-  bool stacked_views;   // reads ScorpGs3dInputs.num_views (3DGS); 2DGS ignores the field: one view
+  bool stacked_views;   // reads ScorpGs3dInputs.num_views (both kinds; false: the field is ignored, one view)
   bool acc_offsets32;   // the blend backward addresses accumulator and partial rows by 32-bit float offsets (else size_t)
   int acc_stride;       // floats per accumulator row
   int prof_preprocess, prof_blend_backward, prof_preprocess_backward;

@@ -37,7 +37,8 @@ __device__ __forceinline__ bool surfel_reaches_box(float cx, float cy, const flo
 }
 
 struct Pg2Args {
-  int N, K, W, H, tiles_x, tiles_y, raw, count_with_atomics;
+  int N, K, W, H, tiles_x, tiles_y, raw, count_with_atomics;   // (H, tiles_y: of ONE view)
+  int views;   // stacked views (ScorpGs3dInputs.num_views): blockIdx.y = view, records of virtual surfel view * N + i
   float scale_mod;
   const float *view, *proj, *campos;
   const float *means3D, *shs, *shs_rest, *colors_precomp, *opacities, *scales, *rotations, *transmat;
@@ -80,12 +81,16 @@ __device__ __forceinline__ void preprocess2d_body(const Pg2Args &a, float *s_sh,
   if constexpr (LIN) {
     RawParams r;
     raw_issue_params<2>(r, a.means3D + 3 * (size_t)i, a.rotations + 4 * (size_t)i, a.scales + 2 * (size_t)i, a.opacities + i);
-    stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);   // (nontemporal: see preprocess_body, gs3d_pergaussian.hip)
+    // (nontemporal for one view; a stacked launch re-reads the rows once per view, from L2: see preprocess_body, gs3d_pergaussian.hip)
+    if (a.views <= 1) stage_sh_linear_async<2>(s_sh, a.shs, a.shs_rest, i0);
+    else stage_sh_linear_async<0>(s_sh, a.shs, a.shs_rest, i0);
     raw_take_params(r, pre);
   }
+  const int view = a.views > 1 ? (int)blockIdx.y : 0;   // workgroup-uniform: the matrices stay scalar loads
+  const CFloat *cv = (const CFloat *)a.view + 16 * view, *cp = (const CFloat *)a.proj + 16 * view;
   float vm[16], pm[16];
 #pragma unroll
-  for (int q = 0; q < 16; q++) { vm[q] = ((const CFloat *)a.view)[q]; pm[q] = ((const CFloat *)a.proj)[q]; }   // scalar cache
+  for (int q = 0; q < 16; q++) { vm[q] = cv[q]; pm[q] = cp[q]; }   // scalar cache
   BinRec br;
   br.x0 = br.y0 = br.x1 = br.y1 = 0; br.depth_bits = 0; br.radius = 0;
   bool vis = false;
@@ -205,7 +210,8 @@ __device__ __forceinline__ void preprocess2d_body(const Pg2Args &a, float *s_sh,
         __syncthreads();
       }
       if (vis) {
-        const float dx = p[0] - ((const CFloat *)a.campos)[0], dy = p[1] - ((const CFloat *)a.campos)[1], dz = p[2] - ((const CFloat *)a.campos)[2];
+        const CFloat *cc = (const CFloat *)a.campos + 3 * view;
+        const float dx = p[0] - cc[0], dy = p[1] - cc[1], dz = p[2] - cc[2];
         const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
         sh_row_to_rgb<DEG>(sh_row(s_sh, threadIdx.x, lin), dx * inv, dy * inv, dz * inv, rgb);
 #pragma unroll
@@ -220,9 +226,15 @@ __device__ __forceinline__ void preprocess2d_body(const Pg2Args &a, float *s_sh,
     for (int q = 0; q < 3; q++) rgb[q] = a.colors_precomp[3 * (size_t)i + q];
   }
   if (!active) return;
+  const int row = view * a.N + i;   // the virtual surfel of the stacked image (validate: views x N < 2^31)
+  if (view > 0) {   // into the view's band of the stacked image: only the TILE rectangle moves (the tile mask is relative to
+                    // it); the record keeps the view's own pixel coordinates and the blend kernel works band-locally
+                    // (see preprocess_body, gs3d_pergaussian.hip)
+    y0 += view * a.tiles_y; y1 += view * a.tiles_y;
+  }
   int radius_out = 0;
   if (vis) {
-    float4 *dst = reinterpret_cast<float4 *>(rec + i);
+    float4 *dst = reinterpret_cast<float4 *>(rec + row);
     dst[0] = make_float4(T[0], T[1], T[2], T[3]);
     dst[1] = make_float4(T[4], T[5], T[6], T[7]);
     dst[2] = make_float4(T[8], cx, cy, op);
@@ -236,9 +248,9 @@ __device__ __forceinline__ void preprocess2d_body(const Pg2Args &a, float *s_sh,
     if (a.count_with_atomics)
       for_each_tile(x0, y0, x1, y1, mask, a.tiles_x, [&](int t) { atomicAdd(&tile_count[t], 1u); });
   }
-  reinterpret_cast<uint4 *>(bin)[i] = *reinterpret_cast<const uint4 *>(&br);
-  tile_mask[i] = mask;
-  radii[i] = radius_out;
+  reinterpret_cast<uint4 *>(bin)[row] = *reinterpret_cast<const uint4 *>(&br);
+  tile_mask[row] = mask;
+  radii[row] = radius_out;
 }
 
 template <int DEG, bool SPLIT>
@@ -279,12 +291,30 @@ constexpr int k2FRing = (k2FChunk + k2FGroup - 1 + k2FGroup - 1) / k2FGroup * k2
 
 // kForBackward = false (scorp_gs2d_render_image): no cull verdicts, per-pixel state or contributor bookkeeping is left
 // behind for a backward pass.
-template <bool kForBackward>
+//
+// Stacked views (ScorpGs3dInputs.num_views; H = the stacked height): the records hold each view's OWN pixel coordinates, so
+// everything that places the block in pixel space uses the row inside its band (band_h = rows per view, a multiple of the
+// tile; 0 = one view); only the output addresses and the `inside` test use the stacked row.  The band of a tile row comes
+// from a scalar multiply, no division: band = ty * band_magic >> 32, band_magic = ceil(2^32 / d) for d tile rows per band
+// (0 = one view; 2^32 itself for d = 1, hence 64 bits) - exact because tile rows stay below 2^16 and, with two or more
+// views, d below 2^15 (ty * (band_magic * d - 2^32) < 2^31).
+//
+// kScore (scorp_gs2d_render_score; never with kForBackward): the twin of the 3-D kernel's scoring form.  The pose sweep
+// compares alpha and the surface depth with a target and reads nothing else, so no colour, normal or distortion is
+// accumulated (and their ring arrays are not filled), nothing is written to out_color / allmap, and the epilogue forms
+// this pixel's |alpha - alpha*| + |surf_depth - depth*| with surf_depth = (1 - r) nan_to_num(D / alpha) + r
+// nan_to_num(median) (gs2dgs/gaussian_renderer/__init__.py:139-154, r = depth_ratio), sums it over the block and leaves ONE
+// float per block in block_terms[tile * 4 + quad] - plain stores, added up in a fixed order by launch_score_bands.
+template <bool kForBackward, bool kScore = false>
 __global__ void __launch_bounds__(64, SCORP_2D_FWAVES)
 blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ point_list,
                             const Surfel *__restrict__ rec, uint32_t capacity, int W, int H, int tiles_x, int tiles,
                             const float *__restrict__ bg, float *__restrict__ out_color, float *__restrict__ allmap,
-                            float *__restrict__ final_T, uint32_t *__restrict__ n_contrib, uint32_t *__restrict__ hits) {
+                            float *__restrict__ final_T, uint32_t *__restrict__ n_contrib, uint32_t *__restrict__ hits,
+                            int band_h, uint64_t band_magic, const float *__restrict__ tgt_depth = nullptr,
+                            const float *__restrict__ tgt_alpha = nullptr, int score_rows = 0, float depth_ratio = 0.0f,
+                            float *__restrict__ block_terms = nullptr) {
+  static_assert(!(kForBackward && kScore), "the scoring form leaves nothing behind for a backward pass");
   __shared__ float4 q0[k2FRing], q1[k2FRing], q2[k2FRing], q3[k2FRing], q4[k2FRing];   // SurfelLin + (normal, r)
   __shared__ float2 q5[k2FRing];                                                          // (g, b)
   __shared__ __attribute__((aligned(16))) uint32_t q_pos[k2FRing];
@@ -292,11 +322,12 @@ blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint3
   BlockWave blk;
   if (!block_wave(tiles, tiles_x, blk)) return;
   const int tile = blk.tile, quad = blk.quad, bx = blk.bx, by = blk.by;
+  const int byl = by - (int)(((uint64_t)(uint32_t)blk.ty * band_magic) >> 32) * band_h;   // the block's first row inside its band (scalar)
   const int px = bx + (lane & 7), py = by + (lane >> 3);
   const bool inside = px < W && py < H;
-  const float pxf = (float)px, pyf = (float)py;
-  const float bx0 = (float)bx, bx1 = (float)(bx + 7), by0 = (float)by, by1 = (float)(by + 7);
-  const float bxc = (float)bx + 3.5f, byc = (float)by + 3.5f;                    // the linear form's expansion point (surfel_lin)
+  const float pxf = (float)px, pyf = (float)(byl + (lane >> 3));
+  const float bx0 = (float)bx, bx1 = (float)(bx + 7), by0 = (float)byl, by1 = (float)(byl + 7);
+  const float bxc = (float)bx + 3.5f, byc = (float)byl + 3.5f;                   // the linear form's expansion point (surfel_lin)
   const float qxb = (float)(lane & 7) - 3.5f, qyb = (float)(lane >> 3) - 3.5f;   // this pixel about it
   const TileRange tr = tile_range(tile_start, tile, capacity);
   const uint32_t beg = tr.beg, n = tr.end - tr.beg;
@@ -314,7 +345,9 @@ blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint3
   auto fetch_rec = [&](uint32_t id_, float4 &a0_, float4 &a1_, float4 &a2_, float4 &a3_, float4 &a4_, float4 &a5_) {
     if (id_ != 0xFFFFFFFFu) {
       const float4 *src = reinterpret_cast<const float4 *>(rec + id_);
-      a0_ = src[0]; a1_ = src[1]; a2_ = src[2]; a3_ = src[3]; a4_ = src[4]; a5_ = src[5];
+      a0_ = src[0]; a1_ = src[1]; a2_ = src[2];
+      if constexpr (!kScore) a3_ = src[3];   // (normal, r): the score reads neither
+      a4_ = src[4]; a5_ = src[5];
     }
   };
   float4 r0, r1, r2, r3, r4, r5;
@@ -334,8 +367,8 @@ blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint3
       int qi = head + count + (int)(rank - nh);
       qi = qi >= k2FRing ? qi - k2FRing : qi;
       const SurfelLin L = surfel_lin(r0, r1, r2, bxc, byc);
-      q0[qi] = L.e0; q1[qi] = L.e1; q2[qi] = L.e2; q3[qi] = L.e3; q4[qi] = r3; q5[qi] = make_float2(r4.x, r4.y);
-      q_pos[qi] = rank + 1u;
+      q0[qi] = L.e0; q1[qi] = L.e1; q2[qi] = L.e2; q3[qi] = L.e3;
+      if constexpr (!kScore) { q4[qi] = r3; q5[qi] = make_float2(r4.x, r4.y); q_pos[qi] = rank + 1u; }
       if constexpr (kForBackward) my_hits[rank] = id0;   // (rank < n: inside this tile's slice of the region)
     }
     count += __builtin_popcountll(m);
@@ -354,7 +387,8 @@ blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint3
       const uint32_t *gp = q_pos + hv;
       static_assert(k2FGroup == 8 || k2FGroup == 4 || k2FGroup == 2, "positions are fetched as 16- or 8-byte LDS reads");
       uint32_t pos[k2FGroup];
-      if constexpr (k2FGroup == 2) {
+      if constexpr (kScore) {   // (no positions: nothing is left for a backward)
+      } else if constexpr (k2FGroup == 2) {
         const uint2 pl = *reinterpret_cast<const uint2 *>(gp);
         pos[0] = pl.x; pos[1] = pl.y;
       } else {
@@ -374,30 +408,40 @@ blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint3
         okv[i] = ok;
         al[i] = ok ? h.alpha : 0.0f;
         dz[i] = ok ? h.depth : 1.0f;
-        mm[i] = __builtin_fmaf(-fn * kNearZ, ok ? h.rdepth : 1.0f, fn);   // the backward's m_d, to the bit
+        if constexpr (!kScore) mm[i] = __builtin_fmaf(-fn * kNearZ, ok ? h.rdepth : 1.0f, fn);   // the backward's m_d, to the bit
       }
 #pragma unroll
       for (int i = 0; i < k2FGroup; i++) {
         if (kFull || i < nslots) {  // wave-uniform
-          const float4 nr = g4[i];
-          const float2 gb = g5[i];
           // saturation is latched by the sign of T (see blend_forward_wave_kernel)
-          const float alpha = al[i];
-          const float test_T = T * (1.0f - alpha);
-          const bool ok = test_T >= kTMin;
-          const float ae = ok ? alpha : 0.0f;
-          const float w = ae * T;
-          const float A = 1.0f - T, mz = mm[i];
-          dist += (mz * mz * A + M2 - 2.0f * mz * M1) * w;
-          Dp += dz[i] * w; M1 += mz * w; M2 += mz * mz * w;
-          const bool contributes = okv[i] & ok;   // = (ae > 0): a hit that passed eval_surfel has alpha >= 1 / 255 (two scalar masks)
-          const bool is_med = contributes & (T > 0.5f);
-          med = is_med ? dz[i] : med;
-          if constexpr (kForBackward) med_c = is_med ? pos[i] : med_c;
-          N0 += nr.x * w; N1 += nr.y * w; N2 += nr.z * w;
-          C0 += nr.w * w; C1 += gb.x * w; C2 += gb.y * w;
-          T = ok ? test_T : -fabsf(T);
-          if constexpr (kForBackward) last = contributes ? pos[i] : last;
+          if constexpr (kScore) {   // the same T, Dp and median as below, to the bit; nothing else
+            const float alpha = al[i];
+            const float test_T = T * (1.0f - alpha);
+            const bool ok = test_T >= kTMin;
+            const float w = (ok ? alpha : 0.0f) * T;
+            Dp += dz[i] * w;
+            med = (okv[i] & ok & (T > 0.5f)) ? dz[i] : med;
+            T = ok ? test_T : -fabsf(T);
+          } else {
+            const float4 nr = g4[i];
+            const float2 gb = g5[i];
+            const float alpha = al[i];
+            const float test_T = T * (1.0f - alpha);
+            const bool ok = test_T >= kTMin;
+            const float ae = ok ? alpha : 0.0f;
+            const float w = ae * T;
+            const float A = 1.0f - T, mz = mm[i];
+            dist += (mz * mz * A + M2 - 2.0f * mz * M1) * w;
+            Dp += dz[i] * w; M1 += mz * w; M2 += mz * mz * w;
+            const bool contributes = okv[i] & ok;   // = (ae > 0): a hit that passed eval_surfel has alpha >= 1 / 255 (two scalar masks)
+            const bool is_med = contributes & (T > 0.5f);
+            med = is_med ? dz[i] : med;
+            if constexpr (kForBackward) med_c = is_med ? pos[i] : med_c;
+            N0 += nr.x * w; N1 += nr.y * w; N2 += nr.z * w;
+            C0 += nr.w * w; C1 += gb.x * w; C2 += gb.y * w;
+            T = ok ? test_T : -fabsf(T);
+            if constexpr (kForBackward) last = contributes ? pos[i] : last;
+          }
         }
       }
       head = head + k2FGroup == k2FRing ? 0 : head + k2FGroup;
@@ -406,6 +450,22 @@ blend2d_forward_wave_kernel(const uint32_t *__restrict__ tile_start, const uint3
     while (count >= k2FGroup) blend_group(std::true_type{}, k2FGroup);
     if (last_chunk && count > 0) blend_group(std::false_type{}, count);
     id0 = id1; r0 = nx0; r1 = nx1; r2 = nx2; r3 = nx3; r4 = nx4; r5 = nx5; id1 = id2;
+  }
+  if constexpr (kScore) {
+#pragma clang fp contract(off)   // divide, the two products, their sum: the roundings of the expression in torch
+    float term = 0.0f;
+    if (inside) {
+      const float a_ = 1.0f - fabsf(T);   // = allmap[1]
+      // (the target is ONE hypothesis' stack of views; score_rows is a multiple of the tile, so the block lies in one of them)
+      const size_t tp = (size_t)(by % score_rows + (lane >> 3)) * W + px;
+      const float e = nan_to_num00(Dp / a_), m = nan_to_num00(med);
+      const float sd = e * (1.0f - depth_ratio) + depth_ratio * m;
+      term = fabsf(a_ - tgt_alpha[tp]) + fabsf(sd - tgt_depth[tp]);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) term += __shfl_xor(term, off, 64);
+    if (lane == 0) block_terms[tile * 4 + quad] = term;
+    return;
   }
   if (inside) {
     const size_t HW = (size_t)H * W, pix = (size_t)py * W + px;
@@ -1183,10 +1243,20 @@ Pg2Args make_args2(const ScorpGs3dInputs *in, const StateLayout &L) {
   a.view = in->viewmatrix; a.proj = in->projmatrix; a.campos = in->campos;
   a.means3D = in->means3D; a.shs = in->shs; a.shs_rest = in->shs_rest; a.colors_precomp = in->colors_precomp;
   a.opacities = in->opacities; a.scales = in->scales; a.rotations = in->rotations; a.transmat = in->cov3D_precomp;
+  a.views = in->num_views > 1 ? in->num_views : 1;
+  if (a.views > 1) a.tiles_y = L.tiles_y / a.views;   // (L describes the stacked image)
   return a;
 }
 
-constexpr GsKind kGs2d = {true, false, false, kAcc2Stride, kKPreprocess2d, kKBlendBackward2d, kKPreprocessBackward2d,
+// band_h / band_magic of blend2d_forward_wave_kernel for V views of H rows each
+struct Bands { int band_h; uint64_t magic; };
+Bands bands_of(int V, int H) {
+  if (V <= 1) return {0, 0ull};
+  const uint64_t d = (uint64_t)(H / kTile);
+  return {H, ((1ull << 32) + d - 1) / d};
+}
+
+constexpr GsKind kGs2d = {true, true, false, kAcc2Stride, kKPreprocess2d, kKBlendBackward2d, kKPreprocessBackward2d,
                           launch_reduce_pair_rows<kAcc2Stride, kAcc2Stride, 32>};
 
 }  // namespace
@@ -1210,7 +1280,7 @@ int scorp::preprocess2d_impl(const ScorpGs3dInputs *in, int32_t *out_radii, void
   hipStream_t stream = (hipStream_t)stream_;
   return preprocess_pass(kGs2d, in, out_radii, state, state_bytes, stream, [&](const StateLayout &L, char *base) {
     const Pg2Args a = make_args2(in, L);
-    const dim3 grid((in->num_gaussians + 255) / 256), block(256);
+    const dim3 grid((in->num_gaussians + 255) / 256, a.views), block(256);
     dispatch_sh_degree(in->shs ? in->sh_degree : 0, in->shs_rest != nullptr, [&](auto D, auto S) {
       preprocess2d_kernel<D, S><<<grid, block, 0, stream>>>(a, (Surfel *)(base + L.rec), (BinRec *)(base + L.bin),
                                                             (uint64_t *)(base + L.tile_mask), out_radii, (uint32_t *)(base + L.tile_count));
@@ -1229,12 +1299,49 @@ int scorp::render2d_impl(const ScorpGs3dInputs *in, void *state, void *pairs, ui
   {
     ProfScope prof(kKBlendForward2d, stream);
     auto bk = for_backward ? blend2d_forward_wave_kernel<true> : blend2d_forward_wave_kernel<false>;
+    const Bands b = bands_of(f.V, in->image_height);
     bk<<<block_wave_grid(L.tiles), 64, 0, stream>>>(
         (const uint32_t *)(f.base + L.tile_start), (const uint32_t *)(f.pb + f.P.list), (const Surfel *)(f.base + L.rec),
         f.capacity, f.W, f.H, L.tiles_x, L.tiles, in->bg, out_color, out_allmap, (float *)(f.base + L.final_T),
-        (uint32_t *)(f.base + L.n_contrib), (uint32_t *)(f.pb + f.P.hits));
+        (uint32_t *)(f.base + L.n_contrib), (uint32_t *)(f.pb + f.P.hits), b.band_h, b.magic, nullptr, nullptr, 0, 0.0f, nullptr);
   }
   SCORP_KERNEL_CHECK("blend_forward_2d", in->debug, stream);
+  return SCORP_OK;
+}
+
+// The render-and-compare scoring of pose hypotheses (align.StackedSweep): the argument checks and the band sums of
+// scorp_gs3d_render_score, the surface depth of the 2DGS renderer (depth_ratio) in place of depth / alpha.
+extern "C" int scorp_gs2d_render_score(const ScorpGs3dInputs *in, void *state, void *pairs, uint64_t capacity,
+                                       const float *tgt_depth, const float *tgt_alpha, int32_t rows_per_score, float depth_ratio,
+                                       float scale, float *acc, scorp_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RenderFrame f;
+  if (int e = render_frame(kGs2d, in, state, pairs, capacity, false, &f)) return e;
+  const int W = f.W, H = f.H;
+  if (!tgt_depth || !tgt_alpha || !acc || rows_per_score <= 0 || rows_per_score % kTile != 0 || H % rows_per_score != 0) {
+    set_error("scorp_gs2d_render_score: targets / acc NULL, or rows_per_score (%d) not a multiple of 16 dividing the %d rows", rows_per_score, H);
+    return SCORP_ERR_INVALID;
+  }
+  if (!(depth_ratio >= 0.0f && depth_ratio <= 1.0f)) {   // (NaN fails both comparisons)
+    set_error("scorp_gs2d_render_score: depth_ratio %g is not in [0, 1]", (double)depth_ratio); return SCORP_ERR_INVALID;
+  }
+  const StateLayout &L = f.L;
+  const int scores = H / rows_per_score, blocks_per_score = (rows_per_score / kTile) * L.tiles_x * 4;
+  if (score_bands_too_many(scores, W, H)) { set_error("scorp_gs2d_render_score: too many bands for the image"); return SCORP_ERR_INVALID; }
+  if (int e = bin_scatter_and_sort(L, f.P, f.base, f.pb, f.N, f.capacity, in->debug, stream)) return e;
+  {
+    ProfScope prof(kKBlendForward2d, stream);
+    const Bands b = bands_of(f.V, in->image_height);
+    float *block_terms = (float *)(f.base + L.block_hits);
+    blend2d_forward_wave_kernel<false, true><<<block_wave_grid(L.tiles), 64, 0, stream>>>(
+        (const uint32_t *)(f.base + L.tile_start), (const uint32_t *)(f.pb + f.P.list), (const Surfel *)(f.base + L.rec),
+        f.capacity, W, H, L.tiles_x, L.tiles, in->bg, nullptr, nullptr, nullptr, nullptr, (uint32_t *)(f.pb + f.P.hits),
+        b.band_h, b.magic, tgt_depth, tgt_alpha, rows_per_score, depth_ratio, block_terms);
+    // the blocks of score j are the tiles of rows [j, j + 1) * rows_per_score: contiguous tile ids, four blocks each;
+    // the partial sums go to the per-pixel state of a backward pass, which this form does not use
+    launch_score_bands(block_terms, scores, blocks_per_score, (float *)(f.base + L.final_T), scale, acc, stream);
+  }
+  SCORP_KERNEL_CHECK("blend_forward_2d_score", in->debug, stream);
   return SCORP_OK;
 }
 

@@ -281,6 +281,14 @@ score_reduce_kernel(const float *__restrict__ partial, float scale, float *__res
 }
 
 }  // namespace
+
+bool score_bands_too_many(int scores, int W, int H) { return (size_t)scores * kScoreSlices > (size_t)W * H; }
+
+void launch_score_bands(const float *block_terms, int scores, int blocks_per_score, float *partial, float scale, float *acc,
+                        hipStream_t stream) {
+  score_slices_kernel<<<scores * kScoreSlices, 256, 0, stream>>>(block_terms, blocks_per_score, partial);
+  score_reduce_kernel<<<scores, 256, 0, stream>>>(partial, scale, acc);
+}
 }  // namespace scorp
 
 using namespace scorp;
@@ -384,9 +392,8 @@ extern "C" int scorp_gs3d_render_score(const ScorpGs3dInputs *in, void *state, v
     // the blocks of score j are the tiles of rows [j, j + 1) * rows_per_score: contiguous tile ids, four blocks each
     const int scores = H / rows_per_score, blocks_per_score = (rows_per_score / kTile) * L.tiles_x * 4;
     float *partial = (float *)(base + L.final_T);   // (the per-pixel state of a backward pass: unused by this form)
-    if ((size_t)scores * kScoreSlices > (size_t)W * H) { set_error("scorp_gs3d_render_score: too many bands for the image"); return SCORP_ERR_INVALID; }
-    score_slices_kernel<<<scores * kScoreSlices, 256, 0, stream>>>((const float *)(base + L.block_hits), blocks_per_score, partial);
-    score_reduce_kernel<<<scores, 256, 0, stream>>>(partial, scale, acc);
+    if (score_bands_too_many(scores, W, H)) { set_error("scorp_gs3d_render_score: too many bands for the image"); return SCORP_ERR_INVALID; }
+    launch_score_bands((const float *)(base + L.block_hits), scores, blocks_per_score, partial, scale, acc, stream);
   }
   SCORP_KERNEL_CHECK("blend_forward_score", in->debug, stream);
   return SCORP_OK;

@@ -174,6 +174,9 @@ extern "C" int scorp_gs2d_train_view_ex(const ScorpGs2dTrainView *v, const Scorp
     return SCORP_ERR_INVALID;
   }
   const ScorpGs3dInputs *in = v->in;
+  if (in->num_views > 1) {   // (refused before the preprocess, which would take them for stacked views and write V x N radii)
+    set_error("scorp_gs2d_train_view: num_views > 1 is forward only"); return SCORP_ERR_INVALID;
+  }
   const int W = in->image_width, H = in->image_height;
   const bool reg = v->lambda_normal != 0.0f || v->lambda_dist != 0.0f;
   if (reg && (!v->rays_d || !v->rays_o || !v->grad_allmap || !v->reg_workspace)) {
