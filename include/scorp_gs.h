@@ -485,7 +485,7 @@ int scorp_mesh_cluster_stats(const int32_t *faces, const float *vertices, int64_
  *               device) is set to 0 by the call and to 1 when a cell index falls outside [0, 2^21) (or a coordinate is not
  *               finite); that vertex gets slot -1 and the outputs of the later calls are then meaningless (never out of
  *               bounds).  A caller that knows the bounds on the host checks the extent itself and reports SCORP_ERR_INVALID's
- *               meaning there, as scorp_amd/mesh.py does.
+ *               meaning there, as scorp_amd/mesh/simplify.py does.
  *   roots:      out_rep[v] = the smallest vertex index of v's cell, out_is_root[v] = (out_rep[v] == v) as one byte.
  *   accumulate: rep_scan[num_vertices] = the INCLUSIVE int32 prefix sum of the bytes, num_cells its last entry.
  *               out_vertex_cell[v] = rep_scan[rep[v]] - 1; out_cell_ijk[num_cells, 3] (int32) the cells' indices;

@@ -331,3 +331,11 @@ def check(code, what):
     if code != 0:
         msg = lib().scorp_last_error()
         raise RuntimeError(f"{what} failed ({code}): {msg.decode(errors='replace') if msg else ''}")
+
+
+def call(name, *args):
+    """lib().<name>(*args, current stream), checked under its name: a tensor goes as its data_ptr(), a ctypes.Structure by
+    reference, None and everything else as given.  For the callers that are not per-iteration hot paths (scorp_amd/mesh)."""
+    import torch
+    check(getattr(lib(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+                                 for a in args], current_stream_ptr()), name)

@@ -1,6 +1,6 @@
 """Yardstick of the bounded TSDF route (csrc/tsdf_blocks.hip, csrc/isosurface_blocks.hip, scorp_amd.mesh.tsdf_blocks_fuse /
 extract_surface_blocks): the rules of include/scorp_gs.h restated in plain numpy with a dtype argument (float64 is the
-reference, float32 measures what the statements' own rounding costs), written independently of scorp_amd/mesh.py - touch
+reference, float32 measures what the statements' own rounding costs), written independently of scorp_amd/mesh/blocks.py - touch
 as loops over the pixels into a dictionary, integration block by block, the surface as surface nets over the dense box
 gathered from a dictionary of blocks - plus the analytic scene the tests fuse and the rule that leaves out the voxels
 whose decisions are too close to call."""
