@@ -886,7 +886,7 @@ void launch_reduce_pair_rows(int N, const uint32_t *pair_base, uint32_t capacity
   reduce_pair_rows_kernel<kStride, kUsed, kLanes><<<(N + per_block - 1) / per_block, 256, 0, stream>>>(
       N, pair_base, capacity, row_flags, partial, acc);
 }
-// 3DGS: ten floats of a 16-float row; 2DGS: the whole 20-float row (kAcc2Stride, gs2d.hip)
+// 3DGS: ten floats of a 16-float row; 2DGS: the whole 20-float row (kAcc2Stride, surfel.hpp)
 template void launch_reduce_pair_rows<kAccStride, 10, 16>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,
                                                           hipStream_t);
 template void launch_reduce_pair_rows<20, 20, 32>(int, const uint32_t *, uint32_t, const uint8_t *, const float *, float *,

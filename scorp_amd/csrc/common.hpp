@@ -121,7 +121,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t k) {
 // occupying VMEM slots.  Only for data no kernel of the same launch writes (camera matrices).
 typedef __attribute__((address_space(4))) float CFloat;
 
-// v + (v moved across lanes by the DPP control CTRL): the building block of the in-row reductions (gs2d.hip).
+// v + (v moved across lanes by the DPP control CTRL): the building block of the in-row reductions (gs2d_backward.hip).
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
   return v + __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), CTRL, 0xF, 0xF, false));
@@ -148,7 +148,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-// fp16 pairs of the blend backwards' split form (gs3d_backward.hip, gs2d.hip)
+// fp16 pairs of the blend backwards' split form (gs3d_backward.hip, gs2d_backward.hip)
 __device__ __forceinline__ uint32_t pack_rtz16(float lo, float hi) {   // (fp16 rtz(lo)) | (fp16 rtz(hi)) << 16
   return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lo, hi));
 }
@@ -490,6 +490,13 @@ struct AdamEpi {
 void launch_preprocess_backward(const ScorpGs3dInputs *in, const StateLayout &L, const BinRec *bin, const float *acc,
                                 const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam = nullptr,
                                 float lambda_isotropic = 0.0f, const float *jac = nullptr);
+// ---- per-surfel kernels (gs2d_pergaussian.hip): the 2DGS twins of the two launchers above
+struct Surfel;
+void launch_preprocess2d(const ScorpGs3dInputs *in, const StateLayout &L, Surfel *rec, BinRec *bin, uint64_t *tile_mask,
+                         int32_t *radii, uint32_t *tile_count, hipStream_t stream);
+void launch_preprocess2d_backward(const ScorpGs3dInputs *in, const StateLayout &L, const Surfel *rec, const BinRec *bin,
+                                  const float *acc, const ScorpGs3dGrads *grads, hipStream_t stream, const AdamEpi *adam = nullptr,
+                                  float lambda_isotropic = 0.0f);
 int backward3d_impl(const ScorpGs3dInputs *in, const void *state, const void *pairs, uint64_t capacity, const float *dL_dcolor,
                     const float *dL_ddepth, const float *dL_dalpha, const ScorpGs3dGrads *grads, void *scratch,
                     size_t scratch_bytes, uint32_t flags, scorp_stream_t stream, const AdamEpi *adam,

@@ -549,7 +549,6 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
       for (int ch = 0; ch < 3; ch++) gr3[ch] = ((rad_bits >> (kClampShift + ch)) & 1) ? 0.0f : a_[6 + ch];
     }
     if (!a.cov3D_precomp) {
-      const float r = qn.x, x = qn.y, y = qn.z, z = qn.w;
       const float Gs[9] = {gc6[0], 0.5f * gc6[1], 0.5f * gc6[2], 0.5f * gc6[1], gc6[3], 0.5f * gc6[4],
                            0.5f * gc6[2], 0.5f * gc6[4], gc6[5]};
       float gL[9], gR[9];
@@ -569,38 +568,12 @@ __device__ __forceinline__ void preprocess_backward_body(const PgArgs &a, float 
 #pragma unroll
         for (int r_ = 0; r_ < 3; r_++) gR[r_ * 3 + k] = gL[r_ * 3 + k] * sm[k];
       }
-      gq[0] = 2 * (-z * gR[1] + y * gR[2] + z * gR[3] - x * gR[5] - y * gR[6] + x * gR[7]);
-      gq[1] = 2 * (y * gR[1] + z * gR[2] + y * gR[3] - 2 * x * gR[4] - r * gR[5] + z * gR[6] + r * gR[7] - 2 * x * gR[8]);
-      gq[2] = 2 * (-2 * y * gR[0] + x * gR[1] + r * gR[2] + x * gR[3] + z * gR[5] - r * gR[6] + z * gR[7] - 2 * y * gR[8]);
-      gq[3] = 2 * (-2 * z * gR[0] - r * gR[1] + x * gR[2] + r * gR[3] - 2 * z * gR[4] + y * gR[5] + x * gR[6] + y * gR[7]);
-      if (a.raw & 4) {  // through q / |q|
-        const float dotq = r * gq[0] + x * gq[1] + y * gq[2] + z * gq[3];
-        gq[0] = (gq[0] - r * dotq) * inv_qn; gq[1] = (gq[1] - x * dotq) * inv_qn;
-        gq[2] = (gq[2] - y * dotq) * inv_qn; gq[3] = (gq[3] - z * dotq) * inv_qn;
-      }
+      quat_grad(qn, gR, a.raw, inv_qn, gq);
     }
   }
-  if constexpr (ISO) {
-    // d/d(raw scale j) of lambda * mean_{n,i} |s_ni - m_n| = lambda / (3 N) * (sgn_j - (sgn_0 + sgn_1 + sgn_2) / 3) * ds_j/draw_j.
-    // The mean and the signs are taken in double (three equal scales then have the signs 0, as in exact arithmetic);
-    // 3 sgn_j - sum sgn is a small integer, so the gradient carries three fp32 roundings.  Contraction off where it joins
-    // the rasterizer's gradient: the written-gradient form and the step inside the view give the same bits.
-    if (active && (g.scales != nullptr || (adam_on && ad.m[4] != nullptr))) {
-#pragma clang fp contract(off)
-      float sv[3], sg[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) sv[k] = act_scale(LIN ? pre[7 + k] : a.scales[3 * (size_t)i + k], a.raw);
-      const double m = ((double)sv[0] + (double)sv[1] + (double)sv[2]) / 3.0;
-#pragma unroll
-      for (int k = 0; k < 3; k++) sg[k] = (double)sv[k] > m ? 1.0f : (double)sv[k] < m ? -1.0f : 0.0f;
-      const float sgsum = sg[0] + sg[1] + sg[2];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        float gi = iso_k * (3.0f * sg[k] - sgsum);
-        if (a.raw & 2) gi = gi * sv[k];   // d exp(v) / dv
-        gs[k] = gs[k] + gi;
-      }
-    }
+  if constexpr (ISO) {   // (pergaussian.hpp: iso_scale_grad)
+    if (active && (g.scales != nullptr || (adam_on && ad.m[4] != nullptr)))
+      iso_scale_grad<3>(LIN ? pre + 7 : a.scales + 3 * (size_t)i, a.raw, iso_k, gs);
   }
   if constexpr (!JAC) {
     if (a.shs && lin) { stage_sh_wait(); __syncthreads(); }

@@ -460,5 +460,52 @@ __device__ __forceinline__ float4 act_quat(float4 q, int raw, float *inv_norm) {
   return make_float4(q.x * inv, q.y * inv, q.z * inv, q.w * inv);
 }
 
+// ---- arithmetic the two per-primitive backward bodies share (preprocess_backward_body, gs3d_pergaussian.hip;
+// preprocess2d_backward_body, gs2d_pergaussian.hip): one definition, so that a fix reaches both kinds.  The rest of
+// their common epilogue (SH staging, the fused Adam step, the SH tail) stays written out in each body: moved into
+// helpers it changed the block layout of every backward kernel. ----
+// dL/dq from dL/dR (row-major, nine entries) at the normalised quaternion qn = (r, x, y, z); raw & 4: through q / |q|
+__device__ __forceinline__ void quat_grad(float4 qn, const float *gR, int raw, float inv_qn, float *gq) {
+  const float r = qn.x, x = qn.y, y = qn.z, z = qn.w;
+  gq[0] = 2 * (-z * gR[1] + y * gR[2] + z * gR[3] - x * gR[5] - y * gR[6] + x * gR[7]);
+  gq[1] = 2 * (y * gR[1] + z * gR[2] + y * gR[3] - 2 * x * gR[4] - r * gR[5] + z * gR[6] + r * gR[7] - 2 * x * gR[8]);
+  gq[2] = 2 * (-2 * y * gR[0] + x * gR[1] + r * gR[2] + x * gR[3] + z * gR[5] - r * gR[6] + z * gR[7] - 2 * y * gR[8]);
+  gq[3] = 2 * (-2 * z * gR[0] - r * gR[1] + x * gR[2] + r * gR[3] - 2 * z * gR[4] + y * gR[5] + x * gR[6] + y * gR[7]);
+  if (raw & 4) {
+    const float dotq = r * gq[0] + x * gq[1] + y * gq[2] + z * gq[3];
+    gq[0] = (gq[0] - r * dotq) * inv_qn; gq[1] = (gq[1] - x * dotq) * inv_qn;
+    gq[2] = (gq[2] - y * dotq) * inv_qn; gq[3] = (gq[3] - z * dotq) * inv_qn;
+  }
+}
+
+// The isotropic regulariser's gradient, added to the scaling gradient gs (train_3dgs.py:146-148 over [N,3] scales,
+// train_2dgs.py:136-139 over [N,2]; iso_k = lambda_isotropic / (NS^2 N)):
+// d/d(raw scale j) of lambda * mean_{n,i} |s_ni - m_n| = lambda / (NS N) * (sgn_j - (sum_k sgn_k) / NS) * ds_j/draw_j.
+// The mean and the signs are taken in double (equal scales then have the signs 0, as in exact arithmetic);
+// NS sgn_j - sum sgn is a small integer, so the gradient carries three fp32 roundings.  Contraction off where it joins
+// the rasterizer's gradient: the written-gradient form and the step inside the view give the same bits.
+template <int NS>
+__device__ __forceinline__ void iso_scale_grad(const float *s_raw, int raw, float iso_k, float *gs) {
+#pragma clang fp contract(off)
+  float sv[NS], sg[NS];
+#pragma unroll
+  for (int k = 0; k < NS; k++) sv[k] = act_scale(s_raw[k], raw);
+  double sum = (double)sv[0];
+#pragma unroll
+  for (int k = 1; k < NS; k++) sum = sum + (double)sv[k];
+  const double m = sum / (double)NS;
+#pragma unroll
+  for (int k = 0; k < NS; k++) sg[k] = (double)sv[k] > m ? 1.0f : (double)sv[k] < m ? -1.0f : 0.0f;
+  float sgsum = sg[0];
+#pragma unroll
+  for (int k = 1; k < NS; k++) sgsum = sgsum + sg[k];
+#pragma unroll
+  for (int k = 0; k < NS; k++) {
+    float gi = iso_k * ((float)NS * sg[k] - sgsum);
+    if (raw & 2) gi = gi * sv[k];   // d exp(v) / dv
+    gs[k] = gs[k] + gi;
+  }
+}
+
 }  // namespace
 }  // namespace scorp

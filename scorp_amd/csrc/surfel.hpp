@@ -1,12 +1,22 @@
 // surfel.hpp — the 2DGS surfel record and the per-pixel ray-surfel intersection, shared by the blend kernels of
-// gs2d.hip and the mask vote (mask_vote.hip): every kernel that replays a 2-D render evaluates alpha with these
-// functions, so all of them see the forward's alpha bit for bit.
+// gs2d_forward.hip / gs2d_backward.hip and the mask vote (mask_vote.hip): every kernel that replays a 2-D render evaluates
+// alpha with these functions, so all of them see the forward's alpha bit for bit.  Also what more than one of the three
+// surfel files (gs2d_pergaussian.hip, gs2d_forward.hip, gs2d_backward.hip) needs: the constants, the accumulator row,
+// the exact footprint test and the kind's entry of the shared host pipeline.
 #pragma once
 #include "common.hpp"
 
 namespace scorp {
 
 constexpr float kFilterInvSq = 2.0f;
+constexpr float kFarZ = 100.0f;
+constexpr float kCutoff = 3.0f;
+constexpr float kFilterSize = 0.707106f;
+constexpr float kExtentFloor = 0.0001f;
+constexpr int kAcc2Stride = 20;  // d/d(pa, pb, pc)[9], d/dD, d/dTw.z, gxy[2], gnormal[3], gopacity, grgb[3]
+
+constexpr GsKind kGs2d = {true, true, false, kAcc2Stride, kKPreprocess2d, kKBlendBackward2d, kKPreprocessBackward2d,
+                          launch_reduce_pair_rows<kAcc2Stride, kAcc2Stride, 32>};
 
 struct alignas(16) Surfel {  // 96 bytes, gathered as six 16-byte loads
   float4 r0;  // Tu.x Tu.y Tu.z Tv.x
@@ -17,6 +27,20 @@ struct alignas(16) Surfel {  // 96 bytes, gathered as six 16-byte loads
   float4 r5;  // ex ey A B   | united with the disc |p - (cx,cy)|^2 <= lp2; A == 0: unknown, never cull
 };
 static_assert(sizeof(Surfel) == 96, "Surfel must be 96 bytes");
+
+// Exact culling for surfels.  alpha >= 1/255 needs min(rho3d, rho2d) <= kk = 2 ln(255 o).  {rho3d <= kk} is the
+// projection of the surfel's uv-disc of radius sqrt(kk): with p = (x Tw - Tu) x (y Tw - Tv) linear in the pixel,
+// rho3d = (p0^2 + p1^2) / p2^2, so the region is the conic p0^2 + p1^2 - kk p2^2 <= 0 — an ellipse whenever the disc
+// stays in front of the camera; preprocess2d_kernel normalises it (with 1% + 0.02 of slack on kk).  {rho2d <= kk} is
+// a disc about the low-pass centre.  A pixel box that neither reaches cannot hold a contributing pixel, so dropping
+// the (box, surfel) pair changes no output bit.
+__device__ __forceinline__ bool surfel_reaches_box(float cx, float cy, const float4 r4, const float4 r5, float bx0, float bx1,
+                                                   float by0, float by1) {
+  if (r5.z == 0.0f) return true;
+  const float ddx = fmaxf(fmaxf(bx0 - cx, cx - bx1), 0.0f), ddy = fmaxf(fmaxf(by0 - cy, cy - by1), 0.0f);
+  if (ddx * ddx + ddy * ddy <= r4.w) return true;
+  return conic_min_over_box(r5.x, r5.y, r5.z, r5.w, r4.z, bx0, bx1, by0, by1) <= 1.0f;
+}
 
 // The ray-surfel intersection in linear form.  With k = x Tw - Tu, l = y Tw - Tv the reference intersects with
 // p = k x l and s = (p0, p1) / p2.  p is LINEAR in the pixel, and p . Tw = det[Tu; Tv; Tw] =: D for every pixel, so

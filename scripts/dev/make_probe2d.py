@@ -1,8 +1,8 @@
-"""Timing-only probe builds of blend2d_backward_wave_kernel (WRONG gradients; never shipped): a copy of gs2d.hip with sections of the
+"""Timing-only probe builds of blend2d_backward_wave_kernel (WRONG gradients; never shipped): a copy of gs2d_backward.hip with sections of the
 hit loop switchable off by -D flags, to see what each section adds to the launch time at four waves per SIMD.
 
     python scripts/dev/make_probe2d.py            -> build/variants/gs2d_probe.hip
-    bash scripts/build_file_variant.sh p2d_noatomic build/variants/gs2d_probe.hip gs2d.hip "-DPROBE_NO_ATOMIC"
+    bash scripts/build_file_variant.sh p2d_noatomic build/variants/gs2d_probe.hip gs2d_backward.hip "-DPROBE_NO_ATOMIC"
     gpurun -- 'AB_BENCH_ARGS="--scene S6" bash scripts/ab_kernel.sh TAG blend2d_backward default build/variants/libp2d_noatomic.so ...'
 
 Flags: PROBE_NO_ATOMIC (the read-out lanes keep their value, no atomic), PROBE_NO_READOUT (no result-tile write / read-out /
@@ -15,7 +15,7 @@ import os
 import sys
 
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
-src = open(os.path.join(root, "scorp_amd/csrc/gs2d.hip")).read()
+src = open(os.path.join(root, "scorp_amd/csrc/gs2d_backward.hip")).read()
 
 
 def rep(old, new, count=1):

@@ -55,7 +55,7 @@ CASES = {
     "tiny_surfels": dict(N=20000, W=256, H=192, deg=1, seed=5, log_scale=math.log(0.006)),   # low-pass branch
     "scale_mod": dict(N=2000, W=96, H=96, deg=1, seed=8, scale_modifier=1.4),
     # large surfels near the far plane (depth ~70 of kFarZ = 100) under depth / alpha / normal upstream gradients: the products
-    # depth x 1 / p.z x r^2 of the backward's fp16-split values are at their largest here (gs2d.hip, k2TargetExp)
+    # depth x 1 / p.z x r^2 of the backward's fp16-split values are at their largest here (gs2d_backward.hip, k2TargetExp)
     "far_depth": dict(N=1500, W=160, H=120, deg=1, seed=21, radius=70.0, log_scale=math.log(2.0)),
 }
 
@@ -139,7 +139,7 @@ FUZZ_2D = fuzz_cases("2d", int(os.environ.get("SCORP_FUZZ_N", "32")), _FUZZ_SEED
 # No named exceptions any more.  Round 1's linear form of the ray-surfel intersection, expanded about the image
 # origin, needed two here (surfel 1322 of case 2 seen almost edge-on, surfel 3836 of case 7 far out on its long axis:
 # scripts/dev/diag2d_single.py) and missed the tolerance in 7 of 300 differently seeded draws; expanded about the block
-# centre, with the gradients gathered about the surfel's own centre (gs2d.hip, surfel_lin), all 32 pass as they are.  Of
+# centre, with the gradients gathered about the surfel's own centre (surfel.hpp, surfel_lin), all 32 pass as they are.  Of
 # 4 320 differently seeded draws (SCORP_FUZZ_N=160, 27 seeds) fourteen miss, by one surfel each; of the first six:
 # in five it is the fp32 ORACLE that is off, the sixth is a tie: CONDITIONING_PICKS and the test below them.
 FUZZ_2D_EXCEPTIONS = {}
@@ -158,7 +158,7 @@ def test_fuzz_parity_2d(k, precision, dev):
 def test_faint_hits_keep_their_bits(seed, k, precision, dev):
     """Two fuzz scenes whose means2D gradient is carried by a few low-pass pixels of faint or deeply covered surfels
     (alpha ~ 0.01, T down to 1e-4): the largest row of the tensor was 1e-3 / 1e-2 off while the backward's fp16 pairs rode on
-    one power of two per wave, under their absolute floor of 2^-24; with the hit's own power of two (gs2d.hip, `sg`) it is
+    one power of two per wave, under their absolute floor of 2^-24; with the hit's own power of two (gs2d_backward.hip, `sg`) it is
     within 1e-5 (scripts/dev/diag2d_rows.py prints the rows).  The all-fp32 form has no such floor to begin with."""
     _parity_2d(fuzz_cases("2d", 160, seed)[k], dev, precision=precision)
 
@@ -203,7 +203,7 @@ CONDITIONING_PICKS = [(62, 82, 250), (1, 115, 5145), (64, 159, 418), (63, 68, 66
 def test_fuzz_outliers_are_the_fp32_oracles_rounding_not_the_hip_paths(pick, precision, dev):
     """Each of those surfels alone, its transform given: against the EXACT answer for the same fp32 T (the float64 build) the
     HIP path's alpha map and gradients are closer than the fp32 oracle's - the reference's own order of operations in fp32
-    (k = x Tw - Tu, p = k x l) loses 1e-4 .. 3e-2 there, the block-centred linear form (gs2d.hip, surfel_lin) 1e-6 .. 1e-4."""
+    (k = x Tw - Tu, p = k x l) loses 1e-4 .. 3e-2 there, the block-centred linear form (surfel.hpp, surfel_lin) 1e-6 .. 1e-4."""
     from oracle.gs_oracle import OracleRender2D
     seed, k, gid = pick
     case = fuzz_cases("2d", 160, seed)[k]

@@ -6,6 +6,7 @@ registers (512 per lane per SIMD, granularity 8) and by its LDS (160 KB per CU, 
 change that pushes a kernel over its budget costs that silently; this test says so.  It compiles the sources with the
 library's own flags to assembly and reads the resource summary the compiler prints per kernel.
 """
+import functools
 import os
 import re
 import subprocess
@@ -19,18 +20,25 @@ from scorp_amd.build import ARCH, CSRC, HIPCC, ROOT
 BUDGETS = {
     "gs3d_forward.hip": {"blend_forward_wave_kernelILb1E": (80, 16, 160 * 1024 // 24, 6), "blend_forward_wave_kernelILb0E": (80, 16, 160 * 1024 // 24, 6)},
     "gs3d_backward.hip": {"blend_backward_wave_kernel": (128, 32, 160 * 1024 // 16, 4)},
-    "gs2d.hip": {"blend2d_forward_wave_kernel": (96, 16, 160 * 1024 // 20, 5), "blend2d_backward_wave_kernel": (128, 0, 160 * 1024 // 16, 4)},
+    "gs2d_forward.hip": {"blend2d_forward_wave_kernel": (96, 16, 160 * 1024 // 20, 5)},
+    "gs2d_backward.hip": {"blend2d_backward_wave_kernel": (128, 0, 160 * 1024 // 16, 4)},
     # (256-thread workgroups: the LDS figure is per workgroup; the unmasked backward is the one every training view runs)
     "loss.hip": {"ssim_l1_forward_strip_kernel": (128, 0, 5120, 4), "ssim_l1_backward_kernelILb0E": (80, 0, 13312, 6)},
 }
 
 
+def asm_command(src, out, root=ROOT):
+    """The library's flags plus --cuda-device-only -S (scripts/isa_compare.py compiles two trees with it)."""
+    csrc = os.path.join(root, "scorp_amd", "csrc")
+    return [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fno-slp-vectorize", f"-I{os.path.join(root, 'include')}", f"-I{csrc}",
+            "--cuda-device-only", "-S", os.path.join(csrc, src), "-o", out]
+
+
+@functools.lru_cache(maxsize=None)   # the *_resources.py modules together compile each source once
 def _resources(src):
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
-        cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fno-slp-vectorize", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}",
-               "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out]
-        subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        subprocess.run(asm_command(src, out), check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         text = open(out).read()
     res, cur = {}, None
     for line in text.splitlines():

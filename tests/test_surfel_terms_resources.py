@@ -51,7 +51,7 @@ def test_the_two_earlier_maps_backward_instantiations_keep_their_resources():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_isotropic_per_surfel_backward_uses_no_scratch_and_keeps_the_plain_kernels_budget():
-    res = _resources("gs2d.hip")
+    res = _resources("gs2d_pergaussian.hip")
     iso = {k: r for k, r in res.items() if "preprocess2d_backward_iso_kernel" in k}
     assert len(iso) == 4, sorted(res)
     for deg in range(4):
