@@ -83,9 +83,11 @@ __device__ __forceinline__ void maps_backward_tiled_body(const MapsDev &dev, con
   const int x0 = blockIdx.x * kRT_W, y0 = blockIdx.y * kRT_H;
   const size_t HW = (size_t)a.W * a.H;
   if (kReg) {
-    const float inv_hw = 1.0f / (float)HW;
-    Gr.kn = lambda_normal * (g_out2 ? g_out2[0] : 1.0f) * inv_hw;
-    Gr.kd = lambda_dist * (g_out2 ? g_out2[1] : 1.0f) * inv_hw;
+    // lambda g / HW with one division, as the mean's backward forms it: two roundings where a reciprocal of HW takes three,
+    // and the bits of the float32 restatement (tests/test_surfel_maps_edges_gpu.py holds each element to a few ulps)
+    const float hw = (float)HW;
+    Gr.kn = lambda_normal * (g_out2 ? g_out2[0] : 1.0f) / hw;
+    Gr.kd = lambda_dist * (g_out2 ? g_out2[1] : 1.0f) / hw;
   }
   const bool want_frames = kReg || Gr.g_sn;
   if (want_frames) {
