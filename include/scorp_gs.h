@@ -246,6 +246,46 @@ int scorp_icp_point_to_point(const float *source, int32_t n_source, const float 
                              double *out_inlier_rmse, int32_t *out_iterations, void *workspace, size_t workspace_bytes,
                              scorp_stream_t stream);
 
+/* ---- multi-start point-to-plane ICP (Open3D registration_icp with TransformationEstimationPointToPlane, no robust
+ * kernel, from every init of a batch) ----
+ * Inputs, outputs, pass(T), the loop, the stop rule, the precision of the search (fp32 relative to c_t, the centre of the
+ * target's bounding box; everything after it float64), the determinism and the error codes are those of
+ * scorp_icp_point_to_point; inlier_rmse stays the Euclidean sqrt(sum |x - q|^2 / c).  target_normals[n_target, 3] fp32
+ * (device) is added: the normal n of target point q.  Normals are used as given, not normalised; a zero normal adds
+ * nothing to the update (its pair still counts in fitness and inlier_rmse).  A NULL target_normals is SCORP_ERR_INVALID.
+ *   update:    from the c pairs (x, q, n) of a pass, every coordinate relative to c_t, with s = half the largest edge of
+ *              the target's bounding box (1 if that is 0):
+ *                J = [(x cross n) / s ; n] in R^6, rho = n . (x - q), A = sum J J^T, b = sum J rho;
+ *                A = V L V^T (cyclic Jacobi, float64);
+ *                xi = - sum over { l_i > 1e-12 l_max } of v_i (v_i . b) / l_i   (the minimum-norm step: a rank-deficient
+ *                     system - a planar target, one pair - moves only along the directions it constrains);
+ *                xi = 0, the identity, when c = 0 or l_max = 0;
+ *                omega = xi[0:3] / s, tau = xi[3:6], R = Rz(omega_z) Ry(omega_y) Rx(omega_x);
+ *              the update is x' -> R x' + tau about c_t, in absolute terms [R | tau + c_t - R c_t], composed onto T.
+ * workspace: scorp_icp_point_to_plane_workspace_bytes, 256-byte aligned. */
+size_t scorp_icp_point_to_plane_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init);
+int scorp_icp_point_to_plane(const float *source, int32_t n_source, const float *target, const float *target_normals,
+                             int32_t n_target, const double *inits, int32_t n_init, double max_correspondence_distance,
+                             int32_t max_iteration, double relative_fitness, double relative_rmse,
+                             double *out_transformation, double *out_fitness, double *out_inlier_rmse,
+                             int32_t *out_iterations, void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+
+/* Normals of a cloud that brings none (3DGS centres).  points[n, 3] fp32, out_normals[n, 3] fp32 and the optional
+ * out_neighbors[n, knn] int32 (NULL: skipped) are device pointers.  Per point:
+ *   neighbours: its k = min(knn, n) exact nearest points, itself included, ordered by (d^2, index): ties go to the lower
+ *               index.  The search runs on the uniform grid of the ICP calls, in fp32 relative to the centre of the
+ *               cloud's bounding box.  out_neighbors holds them in that order, padded with -1 when knn > n;
+ *   normal:     the float64 covariance of the k neighbours about their mean, the eigenvector of its smallest eigenvalue
+ *               (3x3 Jacobi, float64), scaled to unit length, signed so that its component of largest magnitude (the
+ *               first of equal ones) is positive.  n < 3: (0, 0, 1).
+ * The normals are not oriented (inside / outside): point-to-plane ICP does not depend on the sign.  No atomics: two calls
+ * give the same bits.  The input is only read.  workspace: scorp_estimate_normals_workspace_bytes(n), 256-byte aligned.
+ * SCORP_ERR_INVALID: knn outside [3, 32], an empty cloud, a NULL points / out_normals / workspace, a workspace too small
+ * or misaligned. */
+size_t scorp_estimate_normals_workspace_bytes(int32_t n);
+int scorp_estimate_normals(const float *points, int32_t n, int32_t knn, float *out_normals, int32_t *out_neighbors,
+                           void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+
 /* ---- pose fit from matched 3-D point pairs (utils/solution.py: pc_align_ransac :476-557 and adam_algorithm_3d3d_9dof
  * :363-446, called once per round and object by the alignment scripts) ----
  * source[n_pairs, 3] and target[n_pairs, 3] are float64 device pointers, row i of one matched to row i of the other; every

@@ -124,6 +124,8 @@ EXPORTS = [
     "scorp_prof_enable", "scorp_prof_select", "scorp_prof_num_kernels", "scorp_prof_kernel_name", "scorp_prof_collect",
     "scorp_mask_vote_scratch_bytes", "scorp_gs3d_mask_vote", "scorp_gs2d_mask_vote",
     "scorp_icp_workspace_bytes", "scorp_icp_point_to_point",
+    "scorp_icp_point_to_plane_workspace_bytes", "scorp_icp_point_to_plane",
+    "scorp_estimate_normals_workspace_bytes", "scorp_estimate_normals",
     "scorp_pose_fit_workspace_bytes", "scorp_pose_ransac", "scorp_pose_adam_9dof",
     "scorp_tsdf_fuse", "scorp_isosurface_count_cells", "scorp_isosurface_emit_vertices", "scorp_isosurface_count_faces",
     "scorp_isosurface_emit_faces",
@@ -245,6 +247,12 @@ def lib():
     L.scorp_icp_workspace_bytes.argtypes = [i32, i32, i32]
     f64 = ctypes.c_double
     L.scorp_icp_point_to_point.argtypes = [vp, i32, vp, i32, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
+    L.scorp_icp_point_to_plane_workspace_bytes.restype = sz
+    L.scorp_icp_point_to_plane_workspace_bytes.argtypes = [i32, i32, i32]
+    L.scorp_icp_point_to_plane.argtypes = [vp, i32, vp, vp, i32, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
+    L.scorp_estimate_normals_workspace_bytes.restype = sz
+    L.scorp_estimate_normals_workspace_bytes.argtypes = [i32]
+    L.scorp_estimate_normals.argtypes = [vp, i32, i32, vp, vp, vp, sz, vp]
     L.scorp_pose_fit_workspace_bytes.restype = sz
     L.scorp_pose_fit_workspace_bytes.argtypes = [i32, i32]
     L.scorp_pose_ransac.argtypes = [vp, vp, i32, vp, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]

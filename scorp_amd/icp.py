@@ -1,9 +1,11 @@
-"""Multi-start point-to-point ICP on the GPU: the alignment scripts' get_ICP_fitting_transformation_best
+"""Multi-start ICP on the GPU, point-to-point or point-to-plane: the alignment scripts' get_ICP_fitting_transformation_best
 (align_3dgs_clpe_9dof.py:42-115, align_2dgs_clpe_9dof.py:48-121) without Open3D.
 
 The reference runs Open3D's registration_icp (TransformationEstimationPointToPoint, no scaling, max_iteration=400) once
 per initial pose, 67 poses by default.  Here every init runs in one batch through scorp_icp_point_to_point
-(csrc/icp.hip): one launch per iteration covers all inits still running.  Swap it in with one import:
+(csrc/icp.hip): one launch per iteration covers all inits still running.  estimation="point_to_plane" runs the same
+batch through scorp_icp_point_to_plane (csrc/icp_plane.hip) on the target's normals: model_normals(gaussians) for a
+trained model, estimate_normals(points) for a bare cloud.  Swap it in with one import:
 
     from scorp_amd.icp import get_ICP_fitting_transformation_best
 """
@@ -37,14 +39,19 @@ def _check_finite(name, a):
         raise ValueError(f"{name} contains Inf values")
 
 
-def _points(name, a, device):
-    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"{name} must be [n, 3]; got {tuple(t.shape)}")
-    if t.shape[0] == 0:
+def _check_shape(name, a):
+    shape = tuple(np.shape(a))
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{name} must be [n, 3]; got {shape}")
+    if shape[0] == 0:
         raise ValueError(f"{name} is empty")
-    if t.shape[0] >= 2 ** 31:
+    if shape[0] >= 2 ** 31:
         raise ValueError(f"{name} has more than 2^31 - 1 points")
+
+
+def _points(name, a, device):
+    _check_shape(name, a)
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
@@ -55,12 +62,67 @@ def _device(*arrays):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+ESTIMATIONS = ("point_to_point", "point_to_plane")
+
+
+def _check_estimation(estimation):
+    if estimation not in ESTIMATIONS:
+        raise ValueError(f"unknown estimation {estimation!r}: expected one of {list(ESTIMATIONS)}")
+
+
+def _workspace(nbytes, dev):
+    """(the tensor that owns it, a 256-byte aligned pointer into it, the bytes from there)."""
+    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    ptr = (ws.data_ptr() + 255) // 256 * 256
+    return ws, ptr, ws.numel() - (ptr - ws.data_ptr())
+
+
+def estimate_normals(points, knn=30, return_neighbors=False):
+    """Unit normals [n, 3] fp32 (a device tensor) of a cloud that brings none, such as 3DGS centres: per point the
+    eigenvector of the smallest eigenvalue of the float64 covariance of its min(knn, n) exact nearest neighbours (itself
+    included), signed so that its largest component is positive (scorp_estimate_normals).  With return_neighbors also
+    the neighbour indices [n, knn] int32, sorted by (d^2, index) and padded with -1."""
+    if not 3 <= int(knn) <= 32:
+        raise ValueError(f"knn must be in [3, 32]; got {knn}")
+    _check_shape("points", points)
+    _check_finite("points", points)
+    dev = _device(points)
+    P = _points("points", points, dev)
+    n, knn = P.shape[0], int(knn)
+    L = _C.lib()
+    ws, ws_ptr, ws_bytes = _workspace(L.scorp_estimate_normals_workspace_bytes(n), dev)
+    normals = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    nb = torch.empty(n, knn, dtype=torch.int32, device=dev) if return_neighbors else None
+    with torch.cuda.device(dev):
+        _C.check(L.scorp_estimate_normals(P.data_ptr(), n, knn, normals.data_ptr(), nb.data_ptr() if return_neighbors else None,
+                                          ws_ptr, ws_bytes, _C.current_stream_ptr()), "scorp_estimate_normals")
+    return (normals, nb) if return_neighbors else normals
+
+
+def model_normals(gaussians):
+    """Per-Gaussian normals [N, 3] of a trained model, for target_normals: a GaussianModel2D's surfel normal is the third
+    axis of its rotation; a GaussianModel's is the rotation axis of its smallest scale.  Plain torch, once per object."""
+    from .gaussian_model import build_rotation
+    from .rasterizer3d import _GS2D
+    from .segment import _model_kind
+    kind = _model_kind(gaussians)
+    with torch.no_grad():
+        R = build_rotation(gaussians._rotation)
+        if kind is _GS2D:
+            return R[:, :, 2].contiguous()
+        axis = gaussians._scaling.argmin(dim=1)       # (the activation is monotonic: the smallest raw scale)
+        return torch.gather(R, 2, axis[:, None, None].expand(-1, 3, 1))[:, :, 0].contiguous()
+
+
 def registration_icp(source, target, max_correspondence_distance, inits, max_iteration=30, relative_fitness=1e-6,
-                     relative_rmse=1e-6):
+                     relative_rmse=1e-6, estimation="point_to_point", target_normals=None):
     """Open3D's registration_icp(source, target, r, init, TransformationEstimationPointToPoint(),
     ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)) from every init of `inits` ([4, 4] or
     [n_init, 4, 4]) at once.  source [n, 3] and target [m, 3]: numpy arrays or torch tensors (searched in fp32; pair
-    distances, moments and transforms in float64).  Returns an ICPResult of numpy arrays."""
+    distances, moments and transforms in float64).  estimation="point_to_plane" is TransformationEstimationPointToPlane
+    (no robust kernel) on target_normals [m, 3]; without them the normals are estimate_normals(target, knn=30).
+    Returns an ICPResult of numpy arrays."""
+    _check_estimation(estimation)
     r = float(max_correspondence_distance)
     if not np.isfinite(r) or r <= 0.0:
         raise ValueError(f"max_correspondence_distance must be positive and finite; got {max_correspondence_distance}")
@@ -68,6 +130,12 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
         raise ValueError(f"max_iteration must be >= 0; got {max_iteration}")
     _check_finite("source", source)
     _check_finite("target", target)
+    plane = estimation == "point_to_plane"
+    if plane and target_normals is not None:
+        if tuple(np.shape(target_normals)) != tuple(np.shape(target)):
+            raise ValueError(f"target_normals must have the target's shape {tuple(np.shape(target))}; "
+                             f"got {tuple(np.shape(target_normals))}")
+        _check_finite("target_normals", target_normals)
     T0 = np.asarray(inits.detach().cpu() if isinstance(inits, torch.Tensor) else inits, dtype=np.float64)
     if T0.shape == (4, 4):
         T0 = T0[None]
@@ -79,19 +147,25 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     Q = _points("target", target, dev)
     ni = T0.shape[0]
     L = _C.lib()
-    ws = torch.empty(int(L.scorp_icp_workspace_bytes(P.shape[0], Q.shape[0], ni)) + 256, dtype=torch.uint8, device=dev)
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+    if plane:
+        Nq = estimate_normals(Q, knn=30) if target_normals is None else _points("target_normals", target_normals, dev)
+    size = L.scorp_icp_point_to_plane_workspace_bytes if plane else L.scorp_icp_workspace_bytes
+    ws, ws_ptr, ws_bytes = _workspace(size(P.shape[0], Q.shape[0], ni), dev)
     T_in = torch.as_tensor(np.ascontiguousarray(T0), device=dev)
     T_out = torch.empty_like(T_in)
     fit = torch.empty(ni, dtype=torch.float64, device=dev)
     rmse = torch.empty(ni, dtype=torch.float64, device=dev)
     iters = torch.empty(ni, dtype=torch.int32, device=dev)
+    tail = (T_in.data_ptr(), ni, ctypes.c_double(r), int(max_iteration), ctypes.c_double(float(relative_fitness)),
+            ctypes.c_double(float(relative_rmse)), T_out.data_ptr(), fit.data_ptr(), rmse.data_ptr(), iters.data_ptr(), ws_ptr,
+            ws_bytes, _C.current_stream_ptr())
     with torch.cuda.device(dev):
-        _C.check(L.scorp_icp_point_to_point(
-            P.data_ptr(), P.shape[0], Q.data_ptr(), Q.shape[0], T_in.data_ptr(), ni, ctypes.c_double(r), int(max_iteration),
-            ctypes.c_double(float(relative_fitness)), ctypes.c_double(float(relative_rmse)), T_out.data_ptr(),
-            fit.data_ptr(), rmse.data_ptr(), iters.data_ptr(), ws_ptr, ws.numel() - (ws_ptr - ws.data_ptr()),
-            _C.current_stream_ptr()), "scorp_icp_point_to_point")
+        if plane:
+            _C.check(L.scorp_icp_point_to_plane(P.data_ptr(), P.shape[0], Q.data_ptr(), Nq.data_ptr(), Q.shape[0], *tail),
+                     "scorp_icp_point_to_plane")
+        else:
+            _C.check(L.scorp_icp_point_to_point(P.data_ptr(), P.shape[0], Q.data_ptr(), Q.shape[0], *tail),
+                     "scorp_icp_point_to_point")
     return ICPResult(T_out.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy())
 
 
@@ -118,9 +192,13 @@ def icp_inits(rotations, center_original, center_refined):
 
 
 def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refined: np.ndarray, rotations: np.ndarray,
-                                        threshold: float) -> np.ndarray:
+                                        threshold: float, *, estimation="point_to_point", target_normals=None,
+                                        max_iteration=400) -> np.ndarray:
     """The reference's function of the same name, statement for statement, with every ICP run on the GPU in one batch:
-    the 4x4 float64 transform (refined -> original) of the FIRST init with the highest fitness."""
+    the 4x4 float64 transform (refined -> original) of the FIRST init with the highest fitness.  The keyword-only
+    arguments are this project's: estimation="point_to_plane" with target_normals [len(pc_xyz_original), 3] (a surfel
+    model's come from model_normals; None estimates them from the cloud) normally needs far fewer updates."""
+    _check_estimation(estimation)
     if np.any(np.isnan(pc_xyz_original)) or np.any(np.isnan(pc_xyz_refined)):
         raise ValueError("Point clouds contain NaN values")
     if np.any(np.isinf(pc_xyz_original)) or np.any(np.isinf(pc_xyz_refined)):
@@ -131,6 +209,10 @@ def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refi
     center_refined = ref.mean(axis=0)
     src = ref[downsample_indices(len(orig), len(ref))]
     inits = icp_inits(rotations, center_original, center_refined)
-    res = registration_icp(src, orig, threshold, inits, max_iteration=400)
+    if estimation == "point_to_point":
+        res = registration_icp(src, orig, threshold, inits, max_iteration=max_iteration)
+    else:
+        res = registration_icp(src, orig, threshold, inits, max_iteration=max_iteration, estimation=estimation,
+                               target_normals=target_normals)
     best = int(np.argmax(res.fitness))   # the first maximum: the reference keeps a pose only on a strictly higher fitness
     return res.transformation[best].copy()

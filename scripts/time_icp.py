@@ -1,8 +1,11 @@
 """Time the multi-start ICP (scorp_amd.icp) at the reference's size: a 100 k-point target, a 200 k-point source, the
 67 inits of rotations_64.npz, max_iteration = 400, r = 0.16 x the mean bounding-box edge (the alignment script's
 threshold).  Prints one JSON line: total ms per call (median of --reps after a warm-up call), iterations per init, and
-the 16-thread scipy cKDTree correspondence pass of the yardstick on the same machine.  The per-pass kernel time comes
-from a run under `rocprofv3 --kernel-trace --stats` (icp_pass_kernel / icp_solve_kernel)."""
+the 16-thread scipy cKDTree correspondence pass of the yardstick on the same machine.  --estimation point_to_plane runs
+the same fixture through scorp_icp_point_to_plane on normals estimated from the target (knn 30), and times that
+estimation too.  The per-pass kernel time comes from a run under `rocprofv3 --kernel-trace` (icp_pass_kernel /
+icp_solve_kernel, icp_plane_pass_kernel / icp_plane_solve_kernel: the first launch has every init active, the last ones
+a single init)."""
 import argparse
 import json
 import os
@@ -22,6 +25,7 @@ def main():
     ap.add_argument("--max-iteration", type=int, default=400)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--scipy-passes", type=int, default=5, help="yardstick passes to time (0: skip)")
+    ap.add_argument("--estimation", choices=["point_to_point", "point_to_plane"], default="point_to_point")
     a = ap.parse_args()
     import torch
     from scipy.spatial import cKDTree
@@ -38,18 +42,36 @@ def main():
     r = float(np.ptp(tgt, axis=0).mean() * 0.16)
     dev = torch.device("cuda:0")
     S, Q = torch.tensor(src, device=dev), torch.tensor(tgt, device=dev)
-    res = icp.registration_icp(S, Q, r, inits, max_iteration=a.max_iteration)   # warm-up
+    kw = {}
+    normals_ms = None
+    if a.estimation == "point_to_plane":
+        icp.estimate_normals(Q, knn=30)   # warm-up
+        ts = []
+        for _ in range(a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            N = icp.estimate_normals(Q, knn=30)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        normals_ms = float(np.median(ts))
+        kw = {"estimation": "point_to_plane", "target_normals": N}
+    res = icp.registration_icp(S, Q, r, inits, max_iteration=a.max_iteration, **kw)   # warm-up
     times = []
     for _ in range(a.reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        res = icp.registration_icp(S, Q, r, inits, max_iteration=a.max_iteration)
+        res = icp.registration_icp(S, Q, r, inits, max_iteration=a.max_iteration, **kw)
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
-    out = {"target": len(tgt), "source": len(src), "inits": len(inits), "max_iteration": a.max_iteration, "r": r,
+    it = np.sort(res.iterations)
+    out = {"estimation": a.estimation, "target": len(tgt), "source": len(src), "inits": len(inits), "max_iteration": a.max_iteration, "r": r,
            "total_ms": float(np.median(times)), "total_ms_all": [round(t, 2) for t in times],
            "passes": int(res.iterations.max()) + 1, "iterations_per_init": res.iterations.tolist(),
-           "best_fitness": float(res.fitness.max())}
+           "iterations_median": float(np.median(it)), "iterations_max": int(it[-1]),
+           "inits_at_max_iteration": int((it >= a.max_iteration).sum()), "best_fitness": float(res.fitness.max()),
+           "best_rmse": float(res.inlier_rmse[int(np.argmax(res.fitness))])}
+    if normals_ms is not None:
+        out["estimate_normals_ms_knn30"] = normals_ms
     if a.scipy_passes > 0:
         tree = cKDTree(tgt.astype(np.float64))
         src64 = src.astype(np.float64)
