@@ -651,6 +651,83 @@ int scorp_mesh_decimate_apply(const int64_t *edge_keys, int64_t num_edges, const
 int scorp_mesh_decimate_faces(const int32_t *faces, int64_t num_faces, const int32_t *vmap, int64_t num_vertices, int32_t *out_faces,
                               uint8_t *out_keep, scorp_stream_t stream);
 
+/* ---- measuring a mesh: exact point-to-mesh distance, surface sampling, nearest point of a cloud (what Open3D's
+ * RaycastingScene.compute_closest_points, sample_points_uniformly and compute_point_cloud_distance are used for) ----
+ * tests/mesh_distance_reference.py restates the distance by brute force in another formulation (project to the plane, else
+ * the three segments) and the sampler from the same prefix array.
+ *
+ * Inputs: vertices[Nv, 3] float32, finite; faces[F, 3] int32 in [0, Nv); queries[Q, 3] float32; max_distance >= 0 (may be
+ * +inf).  All arithmetic below is float64 on the float32 values, every product, quotient and sum rounded on its own (no fp
+ * contraction), u . w = (u0 w0 + u1 w1) + u2 w2, u x w as in the decimation block.
+ *
+ *  1. Grid.  The grid of the ICP search (icp_search.hpp) over the bounding box of ALL vertices: centre ct, origin lo,
+ *     cell edge h from the density 8 F (about one triangle per cell of a closed surface), at most min(8 F + 64, 2^30) cells
+ *     and 1024 per axis.  Cell i of an axis is [lo + i h, lo + (i + 1) h]; every coordinate below is relative to ct.
+ *  2. Registration.  A triangle is registered in every cell its bounding box overlaps: per axis the cells
+ *     floor((min - lo) / h - 1e-9) .. floor((max - lo) / h + 1e-9), clamped to the grid.  The pad of 1e-9 cells is far above
+ *     the rounding of that quotient (values <= 1024, so 2e-13) and of the bound of rule 6, so a cell the triangle touches is
+ *     never dropped.  The (cell, triangle) pairs are a CSR in raster cell order (x fastest) built by count, exclusive scan
+ *     and fill; the order inside a cell is not defined and nothing depends on it.
+ *  3. Pair cap.  cap = 8 F + 4096.  The pairs are first only counted; while the count exceeds the cap, h *= 1.25, the cell
+ *     counts per axis are taken again (lo and ct stay) and the count is repeated.  A one-cell grid has F pairs, so the loop
+ *     ends; the 65th step forces one cell.  Memory is therefore bounded by F alone, whatever the triangles' sizes.
+ *  4. Closest point on a triangle (A, B, C) to P, with the edges ab = B - A, ac = C - A, bc = C - B taken from the float32
+ *     values themselves and ap = P - A from the centre-relative ones; n = ab x ac.  With d1 = ab . ap, d2 = ac . ap,
+ *     bp = ap - ab, d3 = ab . bp, d4 = ac . bp, cp = ap - ac, d5 = ab . cp, d6 = ac . cp, in this order:
+ *       d1 <= 0 and d2 <= 0: A.     d3 >= 0 and d4 <= d3: A + ab.
+ *       vc = d1 d4 - d3 d2 <= 0, d1 >= 0, d3 <= 0: A + (d1 / (d1 - d3)) ab.
+ *       d6 >= 0 and d5 <= d6: A + ac.
+ *       vb = d5 d2 - d1 d6 <= 0, d2 >= 0, d6 <= 0: A + (d2 / (d2 - d6)) ac.
+ *       va = d3 d6 - d5 d4 <= 0, d4 - d3 >= 0, d5 - d6 >= 0: (A + ab) + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) bc.
+ *       else the face: P - ((n . ap) / (n . n)) n.   (The offset along the normal, not a barycentric sum: on a sliver of
+ *       aspect 1e6 the barycentric weights carry errors of 1e-5, the normal of 1e-10.)
+ *     d^2 = |P - closest|^2.
+ *  5. Degenerate faces.  n = (0, 0, 0) exactly: the closest of the closest points of the segments (A, B), (B, C), (C, A),
+ *     ties in that order.  On a segment from a with e = b - a: t = (p - a) . e; a if not t > 0; a + e if t >= e . e; else
+ *     a + (t / (e . e)) e.  Nothing is divided by an area.
+ *  6. Walk.  Per query: a miss if a coordinate is not finite, or if the squared distance to the vertices' bounding box
+ *     exceeds max_distance^2.  Else rings of cells at Chebyshev distance k = 0, 1, ... around the query's cell (clamped to
+ *     one cell outside the grid), as icp_ring_walk.  After ring k everything outside its box is at least lb away, lb the
+ *     least distance to the box's sides that are still inside the grid, computed in float64 from lo + i h; the walk ends
+ *     when lb^2 > best or no side is left.  best starts at max_distance^2.
+ *  7. Result.  The minimum over the triangles met of (d^2, face index) in lexicographic order, a hit iff d^2 <=
+ *     max_distance^2: out_squared_distance = d^2, out_face, out_closest = float32(closest + ct).  A miss gives +inf, -1 and
+ *     NaNs.  The value of a (query, triangle) pair depends on nothing but the pair and ct, so the result is a function of
+ *     the inputs alone: not of the queries' order or number (ct and the grid come from the mesh only), of the launch shape,
+ *     of the pairs' order, or of how often a triangle is met.
+ *
+ * build fills the workspace (scorp_mesh_distance_workspace_bytes(F, Q), 256-byte aligned) and SYNCHRONISES the stream (the
+ * read-backs of rule 3); out_header, a host array of 8 int64 or NULL, receives the pair count, the cap, the cell count, the
+ * cell cap, the three cell counts per axis and the number of growth steps.  query sorts the queries by the 30-bit Morton
+ * code of the ICP source and runs rules 4 - 7 against a built workspace; num_faces = 0 (an empty mesh: all misses, no
+ * workspace needed) and num_queries = 0 are allowed.  An index that is out of range is never followed.
+ *
+ * Sampler: sample i of n draws t = ((i + u(i, 0)) / n) A_total, A_total = area_prefix[F - 1], and takes the first face f
+ * with area_prefix[f] > t (t = the float64 below A_total if rounding reached it), so a face of zero area is never taken;
+ * area_prefix[F] is the caller's inclusive float64 prefix sum of the triangle areas.  u(i, k) = (mix(mix(mix(seed) ^ i) ^ k)
+ * >> 11) 2^-53, mix the splitmix64 finaliser of decimation rule 7.  With s = sqrt(u(i, 1)), r = u(i, 2): w = (1 - s,
+ * s (1 - r), s r) and the point is (w0 A + w1 B) + w2 C per coordinate, rounded once to float32.
+ *
+ * Nearest point: the grid search of the ICP (fp32 d^2 on centre-relative coordinates, ties to the lower original index,
+ * searched to max_distance^2 (1 + 1e-5)), then the pair's d^2 in float64; a hit iff that is <= max_distance^2, else -1, +inf.
+ *
+ * SCORP_ERR_INVALID: a NULL pointer, num_vertices outside [1, 2^30], num_faces outside [1, 2^28] (query: [0, 2^28]),
+ * num_queries / num_samples outside [0, 2^31 - 1], num_cloud outside [1, 2^30], max_distance negative or NaN, a workspace
+ * that is too small or misaligned. */
+size_t scorp_mesh_distance_workspace_bytes(int64_t num_faces, int64_t num_queries);
+int scorp_mesh_distance_build(const float *vertices, int64_t num_vertices, const int32_t *faces, int64_t num_faces, void *workspace,
+                              size_t workspace_bytes, int64_t *out_header, scorp_stream_t stream);
+int scorp_mesh_distance_query(const float *vertices, int64_t num_vertices, const int32_t *faces, int64_t num_faces,
+                              const float *queries, int64_t num_queries, double max_distance, double *out_squared_distance,
+                              int32_t *out_face, float *out_closest, void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+int scorp_mesh_sample_points(const float *vertices, int64_t num_vertices, const int32_t *faces, int64_t num_faces,
+                             const double *area_prefix, int64_t num_samples, uint64_t seed, float *out_points, int32_t *out_faces,
+                             float *out_barycentric, scorp_stream_t stream);
+size_t scorp_nearest_point_workspace_bytes(int32_t num_points, int32_t num_cloud);
+int scorp_nearest_point_distance(const float *points, int32_t num_points, const float *cloud, int32_t num_cloud, double max_distance,
+                                 double *out_squared_distance, int32_t *out_index, void *workspace, size_t workspace_bytes,
+                                 scorp_stream_t stream);
+
 /* ---- bounded TSDF volume: sparse 16^3-voxel blocks, fused and meshed (the route of gs2dgs/utils/mesh_utils.py:138-180
  * extract_mesh_bounded, which hands the work to Open3D's ScalableTSDFVolume) ----
  * Open3D's volume could be neither read nor run where this was written.  The rules below ARE the specification; nothing

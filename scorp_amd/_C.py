@@ -134,6 +134,8 @@ EXPORTS = [
     "scorp_mesh_simplify_faces",
     "scorp_mesh_decimate_quadrics", "scorp_mesh_decimate_flags", "scorp_mesh_decimate_candidates", "scorp_mesh_decimate_hash",
     "scorp_mesh_decimate_select", "scorp_mesh_decimate_apply", "scorp_mesh_decimate_faces",
+    "scorp_mesh_distance_workspace_bytes", "scorp_mesh_distance_build", "scorp_mesh_distance_query", "scorp_mesh_sample_points",
+    "scorp_nearest_point_workspace_bytes", "scorp_nearest_point_distance",
     "scorp_tsdf_blocks_touch", "scorp_tsdf_blocks_neighbors", "scorp_tsdf_blocks_integrate",
     "scorp_isosurface_blocks_count_cells", "scorp_isosurface_blocks_emit_vertices", "scorp_isosurface_blocks_count_faces",
     "scorp_isosurface_blocks_emit_faces",
@@ -279,6 +281,14 @@ def lib():
     L.scorp_mesh_decimate_select.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp]
     L.scorp_mesh_decimate_apply.argtypes = [vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
     L.scorp_mesh_decimate_faces.argtypes = [vp, i64, vp, i64, vp, vp, vp]
+    L.scorp_mesh_distance_workspace_bytes.restype = sz
+    L.scorp_mesh_distance_workspace_bytes.argtypes = [i64, i64]
+    L.scorp_mesh_distance_build.argtypes = [vp, i64, vp, i64, vp, sz, vp, vp]
+    L.scorp_mesh_distance_query.argtypes = [vp, i64, vp, i64, vp, i64, f64, vp, vp, vp, vp, sz, vp]
+    L.scorp_mesh_sample_points.argtypes = [vp, i64, vp, i64, vp, i64, u64, vp, vp, vp, vp]
+    L.scorp_nearest_point_workspace_bytes.restype = sz
+    L.scorp_nearest_point_workspace_bytes.argtypes = [i32, i32]
+    L.scorp_nearest_point_distance.argtypes = [vp, i32, vp, i32, f64, vp, vp, vp, sz, vp]
     bv, f32 = ctypes.POINTER(ScorpTsdfBlockViews), ctypes.c_float
     L.scorp_tsdf_blocks_touch.argtypes = [bv, f32, f32, i32, vp, vp, u64, vp, vp]
     L.scorp_tsdf_blocks_neighbors.argtypes = [vp, i64, vp, vp]

@@ -24,7 +24,10 @@ available.  `simplify_vertex_clustering` reduces the mesh: the vertices in one c
 or at the minimiser of the cell's plane quadrics (csrc/mesh_simplify.hip; the rules are this project's own, in
 include/scorp_gs.h, uncompared with Open3D's simplify_vertex_clustering).  `simplify_quadric_decimation` reduces it to a
 target triangle count by edge collapses, an independent set of edges per round (csrc/mesh_decimate.hip; again this
-project's own rules, in include/scorp_gs.h).
+project's own rules, in include/scorp_gs.h).  `point_mesh_distance`, `sample_points_uniformly`, `nearest_point_distance`
+and the figures of `mesh_distance` / `mesh_cloud_distance` MEASURE a mesh: the exact distance to the nearest triangle through a
+uniform grid of (cell, triangle) pairs, in float64 (csrc/mesh_distance.hip; held to a float64 brute force of another
+formulation, tests/mesh_distance_reference.py).
 
 CUDA tensors run the HIP kernels; CPU tensors run a torch / numpy form of the same statements.
 
@@ -36,6 +39,7 @@ One module per subsystem, every public name re-exported here:
     cluster.py    cluster_connected_triangles, post_process_mesh
     simplify.py   cluster_vertices, simplify_vertex_clustering
     decimate.py   simplify_quadric_decimation and its host loop _decimate over _DecimateHip / _DecimateNumpy
+    distance.py   point_mesh_distance, sample_points_uniformly, nearest_point_distance, mesh_distance, mesh_cloud_distance
     extractor.py  focus_point, GaussianExtractor (imports the others; nothing imports it)
 Every stream-taking C-ABI call of the package goes through _C.call.  A test that patches a module global (tsdf.LAUNCH_SAMPLES) patches the
 home module: the names below are copies.
@@ -45,6 +49,9 @@ from .blocks import (BLOCK_SIDE, BLOCK_VOXELS, KEY_BIAS, MAX_TABLE_SLOTS, BlockV
                      extract_surface_blocks, tsdf_blocks_fuse)
 from .cluster import MIN_CLUSTER_TRIANGLES, _cluster_numpy, cluster_connected_triangles, post_process_mesh
 from .decimate import DECIMATE_DET_FLOOR, DECIMATE_REACH, _decimate, _DecimateHip, simplify_quadric_decimation
+from .distance import (MAX_CLOUD_POINTS, MAX_QUERIES, PAIR_CAP_FACTOR, PAIR_CAP_FLOOR, MeshDistance, NearestPoint, PointMeshDistance,
+                       SurfaceSamples, mesh_cloud_distance, mesh_distance, nearest_point_distance, point_mesh_distance,
+                       sample_points_uniformly, triangle_area_prefix)
 from .extractor import GaussianExtractor, focus_point
 from .simplify import CELL_SIDE, CONTRACTIONS, QUADRIC_TRUNCATE, cluster_vertices, simplify_vertex_clustering
 from .surface import _scan_counts, _surface_nets_numpy, extract_surface
