@@ -687,9 +687,11 @@ int scorp_mesh_decimate_faces(const int32_t *faces, int64_t num_faces, const int
  *     a + (t / (e . e)) e.  Nothing is divided by an area.
  *  6. Walk.  Per query: a miss if a coordinate is not finite, or if the squared distance to the vertices' bounding box
  *     exceeds max_distance^2.  Else rings of cells at Chebyshev distance k = 0, 1, ... around the query's cell (clamped to
- *     one cell outside the grid), as icp_ring_walk.  After ring k everything outside its box is at least lb away, lb the
- *     least distance to the box's sides that are still inside the grid, computed in float64 from lo + i h; the walk ends
- *     when lb^2 > best or no side is left.  best starts at max_distance^2.
+ *     one cell outside the grid): icp_ring_walk (icp_search.hpp) in float64.  After ring k everything outside its box is at
+ *     least lb away, lb the least distance to the box's sides that are still inside the grid, computed in float64 from
+ *     lo + i h; the walk ends when lb^2 > best or no side is left.  best starts at max_distance^2.  (lb alone is not held
+ *     to "no contraction": lo + i h may be one fused multiply-add.  It decides where the walk ends, never a value, and the
+ *     pad of rule 2 is far above either rounding.)
  *  7. Result.  The minimum over the triangles met of (d^2, face index) in lexicographic order, a hit iff d^2 <=
  *     max_distance^2: out_squared_distance = d^2, out_face, out_closest = float32(closest + ct).  A miss gives +inf, -1 and
  *     NaNs.  The value of a (query, triangle) pair depends on nothing but the pair and ct, so the result is a function of

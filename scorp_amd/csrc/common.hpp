@@ -148,6 +148,13 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// Wave-wide sum of a double in every lane (icp.hip, pose_fit.hip)
+__device__ __forceinline__ double wave_sum_f64(double v) {   // fixed butterfly: the same order on every call
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
 // fp16 pairs of the blend backwards' split form (gs3d_backward.hip, gs2d_backward.hip)
 __device__ __forceinline__ uint32_t pack_rtz16(float lo, float hi) {   // (fp16 rtz(lo)) | (fp16 rtz(hi)) << 16
   return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lo, hi));

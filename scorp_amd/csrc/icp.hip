@@ -1,24 +1,33 @@
-// icp.hip — multi-start point-to-point ICP (Open3D registration_icp with TransformationEstimationPointToPoint, no
-// scaling), every init of a call in one batch.  The reference's alignment scripts run it from 67 initial poses with
+// icp.hip — multi-start ICP (Open3D registration_icp, every init of a call in one batch) with either estimator, and the
+// normal estimation that feeds the second one when the target brings no normals.  The rules are written down in
+// include/scorp_gs.h.  The reference's alignment scripts run the point-to-point form from 67 initial poses with
 // max_iteration = 400 (align_3dgs_clpe_9dof.py:42-115 get_ICP_fitting_transformation_best).
 //
-// Built once per call:
+// Built once per call (icp_search.hpp, shared with mesh_distance.hip):
 //   * the target Q in a uniform grid (cell edge from the point density, not from r), its points sorted by cell (a stable
 //     LSD radix sort on the cell id) as float4 {q - c_t (fp32), original index};
 //   * the source P sorted by a 30-bit Morton code over its own bounding box (same sort), so that the 64 queries of a wave
 //     stay neighbours under every rigid T_i and the target cells they visit are shared through L2.
-// Per iteration (no host synchronisation; the host reads the active flags every kIcpPollEvery iterations):
-//   * icp_pass_kernel, grid (source blocks, inits): x = T_i p in float64 (the cumulative transform on the original point),
-//     exact nearest target point within r by an outward ring search over the grid in fp32, the chosen pair's d^2 and the
-//     moments in float64 relative to c_t; one fixed row of 17 sums per block, no float atomics;
-//   * icp_solve_kernel, one wave per init: the rows reduced in a fixed order, fitness / rmse, the stop rule, the Umeyama
-//     update (3x3 one-sided Jacobi SVD in float64, svd3.hpp, reflection rule) composed onto T in float64.
+// Per iteration (no host synchronisation; the host reads the active flags every kIcpPollEvery iterations), one body each
+// for both estimators (icp_pass, icp_solve) behind two thin kernels each:
+//   * icp_pass_kernel / icp_plane_pass_kernel, grid (source blocks, inits): x = T_i p in float64 (the cumulative transform
+//     on the original point), exact nearest target point q within r by an outward ring search over the grid in fp32, the
+//     chosen pair's d^2 in float64 relative to c_t, then the estimator's sums: one fixed row per block, no float atomics;
+//   * icp_solve_kernel / icp_plane_solve_kernel, one wave per init: the rows reduced in a fixed order, fitness / rmse, the
+//     stop rule, the estimator's update [R | tau] about c_t, composed onto T in float64.
+// The estimators differ in their sums and their update alone:
+//   * PointToPoint (TransformationEstimationPointToPoint, no scaling): 17 sums (c, sum d^2, the first and second moments
+//     of x and q); Umeyama without scale by a 3x3 one-sided Jacobi SVD in float64 (svd3.hpp), reflection rule;
+//   * PointToPlane (TransformationEstimationPointToPlane, no robust kernel): with the normal n of q, J = [(x x n) / s ; n],
+//     rho = n . (x - q), 29 sums (c, sum d^2, the 21 of the upper triangle of J J^T, the 6 of J rho); A = V L V^T by
+//     cyclic Jacobi in float64 (A and V in LDS), the minimum-norm step over the eigenvalues above 1e-12 of the largest,
+//     R = Rz Ry Rx.
 // A block's row depends only on (its source range, its init's T), and the rows are reduced in a fixed order: two calls
 // give the same bits, and init j run alone gives the bits of row j of a batch.
-// The grid, the sorts, the ring search and the host calls that build them are in icp_search.hpp, shared with
-// icp_plane.hip.
+// scorp_estimate_normals, one thread per point: its k exact nearest neighbours by the same outward ring walk, the list of
+// the k best (d^2, index) kept sorted in LDS (one column per lane), their float64 covariance, the eigenvector of its
+// smallest eigenvalue from svd3.hpp.
 #include <cmath>
-#include <vector>
 
 #include "common.hpp"
 #include "icp_search.hpp"
@@ -27,16 +36,180 @@
 namespace scorp {
 namespace {
 
-constexpr int kIcpRow = 18;                              // doubles per partial row: 17 sums + pad
+constexpr int kNormalsThreads = 64;
+constexpr int kNormalsMaxK = 32;
+
+// ---- the estimators: kSums sums per pair in a row of kRow doubles (the sums + pad), sums 0 and 1 are c and sum d^2 ----
+
+// Row layout: [c, sum d^2, sum x (3), sum q (3), sum x_a q_b (9, a-major), pad]
+struct PointToPoint {
+  static constexpr int kSums = 17, kRow = 18;
+  static constexpr bool kNormals = false;
+  static constexpr const char *kWho = "icp";
+  __device__ explicit PointToPoint(const IcpGrid *) {}
+
+  __device__ __forceinline__ void accumulate(double (&acc)[kSums], const double x[3], const double q[3], const double[3], double d2,
+                                             const float *, int) const {
+    acc[0] += 1.0;
+    acc[1] += d2;
+    acc[2] += x[0]; acc[3] += x[1]; acc[4] += x[2];
+    acc[5] += q[0]; acc[6] += q[1]; acc[7] += q[2];
+    acc[8] = fma(x[0], q[0], acc[8]); acc[9] = fma(x[0], q[1], acc[9]); acc[10] = fma(x[0], q[2], acc[10]);
+    acc[11] = fma(x[1], q[0], acc[11]); acc[12] = fma(x[1], q[1], acc[12]); acc[13] = fma(x[1], q[2], acc[13]);
+    acc[14] = fma(x[2], q[0], acc[14]); acc[15] = fma(x[2], q[1], acc[15]); acc[16] = fma(x[2], q[2], acc[16]);
+  }
+
+  // Umeyama without scale: Sigma = (1/c) sum (q - qm)(x - xm)^T = U S V^T, R = U D V^T, tau = qm - R xm (relative to c_t)
+  static __device__ __forceinline__ bool update(const double *S, double c, const IcpGrid *, double R[3][3], double tau[3]) {
+    double xm[3], qm[3], A[3][3];
+    for (int a = 0; a < 3; a++) { xm[a] = S[2 + a] / c; qm[a] = S[5 + a] / c; }
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) A[a][b] = S[8 + b * 3 + a] / c - qm[a] * xm[b];   // S[8 + 3b + a] = sum x_b q_a
+    // A Sigma at the rounding level of its raw moments (one pair; every pair at one point) is exactly zero in the
+    // reference's demeaned form: take it as zero, so that R = I as there, not a rotation of the rounding noise
+    double scale = 0.0, amax = 0.0;
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) {
+        scale = fmax(scale, fabs(S[8 + b * 3 + a] / c) + fabs(qm[a] * xm[b]));
+        amax = fmax(amax, fabs(A[a][b]));
+      }
+    if (amax <= 1e-12 * scale)
+      for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) A[a][b] = 0.0;
+    double U[3][3], V[3][3];
+    svd3(A, U, V);
+    const double dsign = det3(U) * det3(V) < 0.0 ? -1.0 : 1.0;
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) R[a][b] = U[a][0] * V[b][0] + U[a][1] * V[b][1] + dsign * U[a][2] * V[b][2];
+    for (int a = 0; a < 3; a++) {
+      double rx = 0.0;
+      for (int b = 0; b < 3; b++) rx += R[a][b] * xm[b];
+      tau[a] = qm[a] - rx;
+    }
+    return true;
+  }
+};
+
+// Row layout: [c, sum d^2, A_00 A_01 .. A_05 A_11 .. A_55 (21), b (6), pad]
+struct PointToPlane {
+  static constexpr int kSums = 29, kRow = 30;
+  static constexpr bool kNormals = true;
+  static constexpr const char *kWho = "icp point-to-plane";
+  double s;
+  __device__ explicit PointToPlane(const IcpGrid *g) : s(scale(g)) {}
+
+  // s: half the largest edge of the target's bounding box, 1 if that is 0 (it brings the rotational part of J to the
+  // magnitude of the translational one)
+  static __device__ __forceinline__ double scale(const IcpGrid *__restrict__ g) {
+    double e = 0.0;
+    for (int d = 0; d < 3; d++) e = fmax(e, (double)g->thi[d] - (double)g->tlo[d]);
+    return e > 0.0 ? 0.5 * e : 1.0;
+  }
+
+  __device__ __forceinline__ void accumulate(double (&acc)[kSums], const double x[3], const double[3], const double u[3], double d2,
+                                             const float *__restrict__ tn, int id) const {
+    const double n0 = tn[(size_t)id * 3 + 0], n1 = tn[(size_t)id * 3 + 1], n2 = tn[(size_t)id * 3 + 2];
+    double J[6];
+    J[0] = (x[1] * n2 - x[2] * n1) / s;
+    J[1] = (x[2] * n0 - x[0] * n2) / s;
+    J[2] = (x[0] * n1 - x[1] * n0) / s;
+    J[3] = n0; J[4] = n1; J[5] = n2;
+    const double rho = fma(n0, u[0], fma(n1, u[1], n2 * u[2]));
+    acc[0] += 1.0;
+    acc[1] += d2;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+      for (int b = a; b < 6; b++) {
+        const int e = 2 + a * 6 - a * (a - 1) / 2 + (b - a);
+        acc[e] = fma(J[a], J[b], acc[e]);
+      }
+      acc[23 + a] = fma(J[a], rho, acc[23 + a]);
+    }
+  }
+
+  // A = V L V^T, the minimum-norm step xi, R = Rz Ry Rx of xi[0:3] / s, tau = xi[3:6]; false when nothing constrains it
+  static __device__ __forceinline__ bool update(const double *S, double, const IcpGrid *g, double R[3][3], double tau[3]) {
+    __shared__ double A[6][6], V[6][6];   // the one lane that solves indexes them by loop variables: LDS, not registers
+    double b6[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+      for (int b = a; b < 6; b++) {
+        const double v = S[2 + a * 6 - a * (a - 1) / 2 + (b - a)];
+        A[a][b] = v;
+        A[b][a] = v;
+      }
+#pragma unroll
+      for (int b = 0; b < 6; b++) V[a][b] = a == b ? 1.0 : 0.0;
+      b6[a] = S[23 + a];
+    }
+    // cyclic Jacobi: every (p, q) of a sweep in row order, until a sweep rotates nothing
+    for (int sweep = 0; sweep < 64; sweep++) {
+      bool rotated = false;
+      for (int p = 0; p < 5; p++) {
+        for (int q = p + 1; q < 6; q++) {
+          const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
+          if (apq == 0.0 || fabs(apq) <= 1e-17 * sqrt(fabs(app) * fabs(aqq))) continue;
+          rotated = true;
+          const double theta = (aqq - app) / (2.0 * apq);
+          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
+          const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+          A[p][p] = app - t * apq;
+          A[q][q] = aqq + t * apq;
+          A[p][q] = 0.0;
+          A[q][p] = 0.0;
+          for (int r = 0; r < 6; r++) {
+            if (r != p && r != q) {
+              const double arp = A[r][p], arq = A[r][q];
+              const double np_ = cs * arp - sn * arq, nq_ = sn * arp + cs * arq;
+              A[r][p] = np_; A[p][r] = np_;
+              A[r][q] = nq_; A[q][r] = nq_;
+            }
+            const double vp = V[r][p], vq = V[r][q];
+            V[r][p] = cs * vp - sn * vq;
+            V[r][q] = sn * vp + cs * vq;
+          }
+        }
+      }
+      if (!rotated) break;
+    }
+    double lmax = 0.0;
+    for (int i = 0; i < 6; i++) lmax = fmax(lmax, A[i][i]);
+    if (!(lmax > 0.0)) return false;   // no constraint at all (every normal zero): the identity
+    // the minimum-norm step: only along the directions the pairs constrain
+    double xi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < 6; i++) {
+      const double l = A[i][i];
+      if (!(l > 1e-12 * lmax)) continue;
+      double vb = 0.0;
+#pragma unroll
+      for (int a = 0; a < 6; a++) vb += V[a][i] * b6[a];
+      const double f = vb / l;
+#pragma unroll
+      for (int a = 0; a < 6; a++) xi[a] -= V[a][i] * f;
+    }
+    const double s = scale(g);
+    const double wx = xi[0] / s, wy = xi[1] / s, wz = xi[2] / s;
+    const double cx = cos(wx), sx = sin(wx), cy = cos(wy), sy = sin(wy), cz = cos(wz), sz = sin(wz);
+    // R = Rz(wz) Ry(wy) Rx(wx)
+    R[0][0] = cz * cy; R[0][1] = cz * sy * sx - sz * cx; R[0][2] = cz * sy * cx + sz * sx;
+    R[1][0] = sz * cy; R[1][1] = sz * sy * sx + cz * cx; R[1][2] = sz * sy * cx - cz * sx;
+    R[2][0] = -sy; R[2][1] = cy * sx; R[2][2] = cy * cx;
+    for (int a = 0; a < 3; a++) tau[a] = xi[3 + a];
+    return true;
+  }
+};
 
 // ---- the correspondence pass ----
 
-// grid (source blocks, inits).  Row layout: [c, sum d^2, sum x (3), sum q (3), sum x_a q_b (9, a-major), pad]
-__global__ void __launch_bounds__(kIcpThreads) icp_pass_kernel(const float4 *__restrict__ sp, int ns, const float4 *__restrict__ tq,
-                                                               const float *__restrict__ tgt, const uint32_t *__restrict__ cell_start,
-                                                               const IcpGrid *__restrict__ g, const double *__restrict__ T,
-                                                               const int32_t *__restrict__ active, double r2, float r2f,
-                                                               double *__restrict__ rows) {
+// grid (source blocks, inits); tn: the target's normals where Est::kNormals
+template <class Est>
+__device__ __forceinline__ void icp_pass(const float4 *__restrict__ sp, int ns, const float4 *__restrict__ tq,
+                                         const float *__restrict__ tgt, const float *__restrict__ tn,
+                                         const uint32_t *__restrict__ cell_start, const IcpGrid *__restrict__ g,
+                                         const double *__restrict__ T, const int32_t *__restrict__ active, double r2, float r2f,
+                                         double *__restrict__ rows) {
   const int j = blockIdx.y;
   if (!active[j]) return;
   const double *M = T + (size_t)j * 16;
@@ -44,9 +217,10 @@ __global__ void __launch_bounds__(kIcpThreads) icp_pass_kernel(const float4 *__r
   const double m10 = M[4], m11 = M[5], m12 = M[6], m13 = M[7] - g->ct[1];
   const double m20 = M[8], m21 = M[9], m22 = M[10], m23 = M[11] - g->ct[2];
   const double c0 = g->ct[0], c1 = g->ct[1], c2 = g->ct[2];
-  double acc[17];
+  const Est est(g);
+  double acc[Est::kSums];
 #pragma unroll
-  for (int a = 0; a < 17; a++) acc[a] = 0.0;
+  for (int a = 0; a < Est::kSums; a++) acc[a] = 0.0;
   const int base = blockIdx.x * kIcpChunk + threadIdx.x;
   for (int k = 0; k < kIcpPerThread; k++) {
     const int i = base + k * kIcpThreads;
@@ -54,58 +228,69 @@ __global__ void __launch_bounds__(kIcpThreads) icp_pass_kernel(const float4 *__r
     const float4 p = sp[i];
     const double px = p.x, py = p.y, pz = p.z;
     // x - c_t in float64: T applied to the original point
-    const double x0 = fma(m00, px, fma(m01, py, fma(m02, pz, m03)));
-    const double x1 = fma(m10, px, fma(m11, py, fma(m12, pz, m13)));
-    const double x2 = fma(m20, px, fma(m21, py, fma(m22, pz, m23)));
-    const int id = icp_nearest((float)x0, (float)x1, (float)x2, r2f, g, cell_start, tq);
+    const double x[3] = {fma(m00, px, fma(m01, py, fma(m02, pz, m03))), fma(m10, px, fma(m11, py, fma(m12, pz, m13))),
+                         fma(m20, px, fma(m21, py, fma(m22, pz, m23)))};
+    const int id = icp_nearest((float)x[0], (float)x[1], (float)x[2], r2f, g, cell_start, tq);
     if (id < 0) continue;
-    const double q0 = (double)tgt[(size_t)id * 3 + 0] - c0, q1 = (double)tgt[(size_t)id * 3 + 1] - c1,
-                 q2 = (double)tgt[(size_t)id * 3 + 2] - c2;
-    const double u0 = x0 - q0, u1 = x1 - q1, u2 = x2 - q2;
-    const double d2 = fma(u0, u0, fma(u1, u1, u2 * u2));
+    const double q[3] = {(double)tgt[(size_t)id * 3 + 0] - c0, (double)tgt[(size_t)id * 3 + 1] - c1,
+                         (double)tgt[(size_t)id * 3 + 2] - c2};
+    const double u[3] = {x[0] - q[0], x[1] - q[1], x[2] - q[2]};
+    const double d2 = fma(u[0], u[0], fma(u[1], u[1], u[2] * u[2]));
     if (!(d2 <= r2)) continue;
-    acc[0] += 1.0;
-    acc[1] += d2;
-    acc[2] += x0; acc[3] += x1; acc[4] += x2;
-    acc[5] += q0; acc[6] += q1; acc[7] += q2;
-    acc[8] = fma(x0, q0, acc[8]); acc[9] = fma(x0, q1, acc[9]); acc[10] = fma(x0, q2, acc[10]);
-    acc[11] = fma(x1, q0, acc[11]); acc[12] = fma(x1, q1, acc[12]); acc[13] = fma(x1, q2, acc[13]);
-    acc[14] = fma(x2, q0, acc[14]); acc[15] = fma(x2, q1, acc[15]); acc[16] = fma(x2, q2, acc[16]);
+    est.accumulate(acc, x, q, u, d2, tn, id);
   }
-  __shared__ double part[kIcpThreads / 64][17];
+  __shared__ double part[kIcpThreads / 64][Est::kSums];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int a = 0; a < 17; a++) {
+  for (int a = 0; a < Est::kSums; a++) {
     const double v = wave_sum_f64(acc[a]);
     if (lane == 0) part[wave][a] = v;
   }
   __syncthreads();
-  if (threadIdx.x < 17) {
+  if (threadIdx.x < Est::kSums) {
     double s = 0.0;
     for (int w = 0; w < kIcpThreads / 64; w++) s += part[w][threadIdx.x];
-    rows[((size_t)j * gridDim.x + blockIdx.x) * kIcpRow + threadIdx.x] = s;
+    rows[((size_t)j * gridDim.x + blockIdx.x) * Est::kRow + threadIdx.x] = s;
   }
+}
+
+__global__ void __launch_bounds__(kIcpThreads) icp_pass_kernel(const float4 *__restrict__ sp, int ns, const float4 *__restrict__ tq,
+                                                               const float *__restrict__ tgt, const uint32_t *__restrict__ cell_start,
+                                                               const IcpGrid *__restrict__ g, const double *__restrict__ T,
+                                                               const int32_t *__restrict__ active, double r2, float r2f,
+                                                               double *__restrict__ rows) {
+  icp_pass<PointToPoint>(sp, ns, tq, tgt, nullptr, cell_start, g, T, active, r2, r2f, rows);
+}
+
+__global__ void __launch_bounds__(kIcpThreads) icp_plane_pass_kernel(const float4 *__restrict__ sp, int ns, const float4 *__restrict__ tq,
+                                                                     const float *__restrict__ tgt, const float *__restrict__ tn,
+                                                                     const uint32_t *__restrict__ cell_start,
+                                                                     const IcpGrid *__restrict__ g, const double *__restrict__ T,
+                                                                     const int32_t *__restrict__ active, double r2, float r2f,
+                                                                     double *__restrict__ rows) {
+  icp_pass<PointToPlane>(sp, ns, tq, tgt, tn, cell_start, g, T, active, r2, r2f, rows);
 }
 
 // ---- the solve ----
 
 // one wave per init, after pass `k` (every active init has run the same number of passes)
-__global__ void __launch_bounds__(64) icp_solve_kernel(const double *__restrict__ rows, int nblk, int ns, const IcpGrid *__restrict__ g,
-                                                       int k, int max_iteration, double rel_fitness, double rel_rmse, double *T,
-                                                       double *fitness, double *rmse, int32_t *iters, int32_t *active) {
+template <class Est>
+__device__ __forceinline__ void icp_solve(const double *__restrict__ rows, int nblk, int ns, const IcpGrid *__restrict__ g, int k,
+                                          int max_iteration, double rel_fitness, double rel_rmse, double *T, double *fitness,
+                                          double *rmse, int32_t *iters, int32_t *active) {
   const int j = blockIdx.x;
   if (!active[j]) return;
   const int lane = threadIdx.x;
-  double S[17];
+  double S[Est::kSums];
 #pragma unroll
-  for (int a = 0; a < 17; a++) S[a] = 0.0;
+  for (int a = 0; a < Est::kSums; a++) S[a] = 0.0;
   for (int b = lane; b < nblk; b += 64) {
-    const double *r = rows + ((size_t)j * nblk + b) * kIcpRow;
+    const double *r = rows + ((size_t)j * nblk + b) * Est::kRow;
 #pragma unroll
-    for (int a = 0; a < 17; a++) S[a] += r[a];
+    for (int a = 0; a < Est::kSums; a++) S[a] += r[a];
   }
 #pragma unroll
-  for (int a = 0; a < 17; a++) S[a] = wave_sum_f64(S[a]);
+  for (int a = 0; a < Est::kSums; a++) S[a] = wave_sum_f64(S[a]);
   if (lane != 0) return;
   const double c = S[0];
   const double fit = c > 0.0 ? c / (double)ns : 0.0;
@@ -121,34 +306,13 @@ __global__ void __launch_bounds__(64) icp_solve_kernel(const double *__restrict_
   }
   if (k >= max_iteration) { iters[j] = k; active[j] = 0; return; }
   if (c <= 0.0) return;   // the update is the identity: T stays
-  // Umeyama without scale: Sigma = (1/c) sum (q - qm)(x - xm)^T = U S V^T, R = U D V^T, t = qm - R xm (relative to c_t)
-  double xm[3], qm[3], A[3][3];
-  for (int a = 0; a < 3; a++) { xm[a] = S[2 + a] / c; qm[a] = S[5 + a] / c; }
-  for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) A[a][b] = S[8 + b * 3 + a] / c - qm[a] * xm[b];   // S[8 + 3b + a] = sum x_b q_a
-  // A Sigma at the rounding level of its raw moments (one pair; every pair at one point) is exactly zero in the
-  // reference's demeaned form: take it as zero, so that R = I as there, not a rotation of the rounding noise
-  double scale = 0.0, amax = 0.0;
-  for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) {
-      scale = fmax(scale, fabs(S[8 + b * 3 + a] / c) + fabs(qm[a] * xm[b]));
-      amax = fmax(amax, fabs(A[a][b]));
-    }
-  if (amax <= 1e-12 * scale)
-    for (int a = 0; a < 3; a++)
-      for (int b = 0; b < 3; b++) A[a][b] = 0.0;
-  double U[3][3], V[3][3];
-  svd3(A, U, V);
-  const double dsign = det3(U) * det3(V) < 0.0 ? -1.0 : 1.0;
-  double R[3][3];
-  for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) R[a][b] = U[a][0] * V[b][0] + U[a][1] * V[b][1] + dsign * U[a][2] * V[b][2];
-  double t[3];
+  double R[3][3], tau[3], t[3];
+  if (!Est::update(S, c, g, R, tau)) return;
   for (int a = 0; a < 3; a++) {
-    // absolute: q = R x + t with x = x' + c_t, q = q' + c_t  ->  t = (qm' - R xm') + (c_t - R c_t)
-    double rx = 0.0, rc = 0.0;
-    for (int b = 0; b < 3; b++) { rx += R[a][b] * xm[b]; rc += R[a][b] * g->ct[b]; }
-    t[a] = (qm[a] - rx) + (g->ct[a] - rc);
+    // absolute: x' -> R x' + tau about c_t  ->  t = tau + c_t - R c_t
+    double rc = 0.0;
+    for (int b = 0; b < 3; b++) rc += R[a][b] * g->ct[b];
+    t[a] = tau[a] + (g->ct[a] - rc);
   }
   double *M = T + (size_t)j * 16, N[12];
   for (int a = 0; a < 3; a++)
@@ -157,19 +321,111 @@ __global__ void __launch_bounds__(64) icp_solve_kernel(const double *__restrict_
   for (int e = 0; e < 12; e++) M[e] = N[e];
 }
 
+__global__ void __launch_bounds__(64) icp_solve_kernel(const double *__restrict__ rows, int nblk, int ns, const IcpGrid *__restrict__ g,
+                                                       int k, int max_iteration, double rel_fitness, double rel_rmse, double *T,
+                                                       double *fitness, double *rmse, int32_t *iters, int32_t *active) {
+  icp_solve<PointToPoint>(rows, nblk, ns, g, k, max_iteration, rel_fitness, rel_rmse, T, fitness, rmse, iters, active);
+}
+
+__global__ void __launch_bounds__(64) icp_plane_solve_kernel(const double *__restrict__ rows, int nblk, int ns,
+                                                             const IcpGrid *__restrict__ g, int k, int max_iteration,
+                                                             double rel_fitness, double rel_rmse, double *T, double *fitness,
+                                                             double *rmse, int32_t *iters, int32_t *active) {
+  icp_solve<PointToPlane>(rows, nblk, ns, g, k, max_iteration, rel_fitness, rel_rmse, T, fitness, rmse, iters, active);
+}
+
+// ---- the normal estimation ----
+
+// One thread per point, in cell order (thread i takes sorted point i, so a wave's queries are neighbours).  The k best
+// (d^2, original index) so far sit sorted in the lane's column of nd / ni; a candidate enters when the list is not full
+// or it is below the last entry, ties on d^2 by the lower index.  The walk is icp_nearest's (icp_ring_walk); it ends when
+// everything outside ring k's box is farther than the k-th best, or nothing is left outside it.
+__global__ void __launch_bounds__(kNormalsThreads) icp_normals_kernel(const float4 *__restrict__ tq, const float *__restrict__ pts, int n,
+                                                                      int k, int knn, const uint32_t *__restrict__ cell_start,
+                                                                      const IcpGrid *__restrict__ g, float *__restrict__ out_normals,
+                                                                      int32_t *__restrict__ out_neighbors) {
+  __shared__ float nd[kNormalsMaxK][kNormalsThreads];
+  __shared__ uint32_t ni[kNormalsMaxK][kNormalsThreads];
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * kNormalsThreads + lane;
+  if (i >= n) return;
+  const float4 me = tq[i];
+  const float x = me.x, y = me.y, z = me.z;
+  const uint32_t self = __float_as_uint(me.w);
+  const float lx = g->lo[0], ly = g->lo[1], lz = g->lo[2], h = g->h, ih = g->inv_h;
+  const int dx = g->dims[0], dy = g->dims[1], dz = g->dims[2];
+  const int cx = icp_cell_axis(x, lx, ih, dx), cy = icp_cell_axis(y, ly, ih, dy), cz = icp_cell_axis(z, lz, ih, dz);
+  int cnt = 0;
+  float kth = 3.4e38f;          // d^2 of the k-th best once the list is full
+  uint32_t kth_id = 0xFFFFFFFFu;
+  auto visit = [&](int ca, int cb) {
+    const uint32_t e = cell_start[cb + 1];
+    for (uint32_t t = cell_start[ca]; t < e; t++) {
+      const float4 q = tq[t];
+      const float ux = q.x - x, uy = q.y - y, uz = q.z - z;
+      const float d2 = __builtin_fmaf(ux, ux, __builtin_fmaf(uy, uy, uz * uz));
+      const uint32_t id = __float_as_uint(q.w);
+      if (cnt == k && !(d2 < kth || (d2 == kth && id < kth_id))) continue;
+      int pos = cnt < k ? cnt : k - 1;   // the free slot, or the last entry, which leaves
+      while (pos > 0) {
+        const float pd = nd[pos - 1][lane];
+        const uint32_t pi = ni[pos - 1][lane];
+        if (!(pd > d2 || (pd == d2 && pi > id))) break;
+        nd[pos][lane] = pd;
+        ni[pos][lane] = pi;
+        pos--;
+      }
+      nd[pos][lane] = d2;
+      ni[pos][lane] = id;
+      if (cnt < k) cnt++;
+      if (cnt == k) { kth = nd[k - 1][lane]; kth_id = ni[k - 1][lane]; }
+    }
+  };
+  icp_ring_walk(x, y, z, cx, cy, cz, lx, ly, lz, h, dx, dy, dz, visit, [&]() { return kth; });
+  if (out_neighbors) {
+    for (int a = 0; a < knn; a++) out_neighbors[(size_t)self * knn + a] = a < cnt ? (int32_t)ni[a][lane] : -1;
+  }
+  float *o = out_normals + (size_t)self * 3;
+  if (cnt < 3) { o[0] = 0.0f; o[1] = 0.0f; o[2] = 1.0f; return; }
+  // float64 covariance of the neighbours about their mean (coordinates relative to c_t)
+  double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+  for (int a = 0; a < cnt; a++) {
+    const float *p = pts + (size_t)ni[a][lane] * 3;
+    m0 += (double)p[0] - g->ct[0]; m1 += (double)p[1] - g->ct[1]; m2 += (double)p[2] - g->ct[2];
+  }
+  m0 /= cnt; m1 /= cnt; m2 /= cnt;
+  double c00 = 0.0, c01 = 0.0, c02 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0;
+  for (int a = 0; a < cnt; a++) {
+    const float *p = pts + (size_t)ni[a][lane] * 3;
+    const double e0 = ((double)p[0] - g->ct[0]) - m0, e1 = ((double)p[1] - g->ct[1]) - m1, e2 = ((double)p[2] - g->ct[2]) - m2;
+    c00 = fma(e0, e0, c00); c01 = fma(e0, e1, c01); c02 = fma(e0, e2, c02);
+    c11 = fma(e1, e1, c11); c12 = fma(e1, e2, c12); c22 = fma(e2, e2, c22);
+  }
+  const double C[3][3] = {{c00 / cnt, c01 / cnt, c02 / cnt}, {c01 / cnt, c11 / cnt, c12 / cnt}, {c02 / cnt, c12 / cnt, c22 / cnt}};
+  double U[3][3], W[3][3];
+  svd3(C, U, W);   // C symmetric and positive semi-definite: the columns of W are its eigenvectors, the last the smallest's
+  double v0 = W[0][2], v1 = W[1][2], v2 = W[2][2];
+  const double len = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+  v0 /= len; v1 /= len; v2 /= len;
+  // the sign: the component of largest magnitude (the first of equal ones) is positive
+  double big = v0;
+  if (fabs(v1) > fabs(big)) big = v1;
+  if (fabs(v2) > fabs(big)) big = v2;
+  if (big < 0.0) { v0 = -v0; v1 = -v1; v2 = -v2; }
+  o[0] = (float)v0; o[1] = (float)v1; o[2] = (float)v2;
+}
+
 // ---- host ----
 
-int icp_impl(const float *source, int32_t ns, const float *target, int32_t nt, const double *inits, int32_t ni, double r,
-             int32_t max_iteration, double rel_fitness, double rel_rmse, double *out_T, double *out_fitness, double *out_rmse,
-             int32_t *out_iters, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (int e = icp_check_args("icp", r, ns, nt, max_iteration, ni,
-                             source && target && inits && out_T && out_fitness && out_rmse && out_iters && workspace))
+template <class Est>
+int icp_run(const float *source, int32_t ns, const float *target, const float *normals, int32_t nt, const double *inits, int32_t ni,
+            double r, int32_t max_iteration, double rel_fitness, double rel_rmse, double *out_T, double *out_fitness,
+            double *out_rmse, int32_t *out_iters, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (int e = icp_check_args(Est::kWho, r, ns, nt, max_iteration, ni,
+                             source && target && (normals || !Est::kNormals) && inits && out_T && out_fitness && out_rmse && out_iters))
     return e;
-  const IcpLayout L(ns, nt, ni, kIcpRow);
-  if (workspace_bytes < L.total || ((uintptr_t)workspace & 255)) {
-    set_error("icp: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, L.total);
-    return SCORP_ERR_INVALID;
-  }
+  const IcpLayout L(ns, nt, ni, Est::kRow);
+  if (int e = check_workspace(Est::kWho, workspace, workspace_bytes, L.total)) return e;
   const IcpWorkspace W(workspace, L);
   if (int e = icp_build_target(target, nt, L, W, stream)) return e;
   if (int e = icp_build_source(source, ns, L, W, stream)) return e;
@@ -180,14 +436,35 @@ int icp_impl(const float *source, int32_t ns, const float *target, int32_t nt, c
   const double r2 = r * r;
   const float r2f = (float)r2 * (1.0f + 1e-5f);   // the fp32 search keeps slightly more; the pair test is float64
   return icp_iterate(ni, max_iteration, W.active, stream, [&](int k) -> int {
-    icp_pass_kernel<<<dim3(nblk, ni), kIcpThreads, 0, stream>>>(W.sp, ns, W.tq, target, W.cell_start, W.g, out_T, W.active, r2, r2f,
-                                                                W.rows);
+    const dim3 grid(nblk, ni);
+    if constexpr (Est::kNormals)
+      icp_plane_pass_kernel<<<grid, kIcpThreads, 0, stream>>>(W.sp, ns, W.tq, target, normals, W.cell_start, W.g, out_T, W.active, r2,
+                                                              r2f, W.rows);
+    else
+      icp_pass_kernel<<<grid, kIcpThreads, 0, stream>>>(W.sp, ns, W.tq, target, W.cell_start, W.g, out_T, W.active, r2, r2f, W.rows);
     SCORP_KERNEL_CHECK("icp_pass", 0, stream);
-    icp_solve_kernel<<<ni, 64, 0, stream>>>(W.rows, nblk, ns, W.g, k, max_iteration, rel_fitness, rel_rmse, out_T, out_fitness,
-                                            out_rmse, out_iters, W.active);
+    (Est::kNormals ? icp_plane_solve_kernel : icp_solve_kernel)<<<ni, 64, 0, stream>>>(
+        W.rows, nblk, ns, W.g, k, max_iteration, rel_fitness, rel_rmse, out_T, out_fitness, out_rmse, out_iters, W.active);
     SCORP_KERNEL_CHECK("icp_solve", 0, stream);
     return SCORP_OK;
   });
+}
+
+int normals_impl(const float *points, int32_t n, int32_t knn, float *out_normals, int32_t *out_neighbors, void *workspace,
+                 size_t workspace_bytes, hipStream_t stream) {
+  if (knn < 3 || knn > kNormalsMaxK) { set_error("estimate_normals: knn must be in [3, %d]", kNormalsMaxK); return SCORP_ERR_INVALID; }
+  if (n <= 0) { set_error("estimate_normals: empty cloud"); return SCORP_ERR_INVALID; }
+  if (n > (1 << 30)) { set_error("estimate_normals: more than 2^30 points"); return SCORP_ERR_INVALID; }
+  if (!points || !out_normals) { set_error("estimate_normals: NULL argument"); return SCORP_ERR_INVALID; }
+  const IcpLayout L(0, n, 0, PointToPlane::kRow);
+  if (int e = check_workspace("estimate_normals", workspace, workspace_bytes, L.total)) return e;
+  const IcpWorkspace W(workspace, L);
+  if (int e = icp_build_target(points, n, L, W, stream)) return e;
+  const int k = knn < n ? knn : n;
+  icp_normals_kernel<<<(n + kNormalsThreads - 1) / kNormalsThreads, kNormalsThreads, 0, stream>>>(
+      W.tq, points, n, k, knn, W.cell_start, W.g, out_normals, out_neighbors);
+  SCORP_KERNEL_CHECK("icp_normals", 0, stream);
+  return SCORP_OK;
 }
 
 }  // namespace
@@ -196,7 +473,7 @@ int icp_impl(const float *source, int32_t ns, const float *target, int32_t nt, c
 using namespace scorp;
 
 extern "C" size_t scorp_icp_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init) {
-  return IcpLayout(n_source, n_target, n_init, kIcpRow).total;
+  return IcpLayout(n_source, n_target, n_init, PointToPoint::kRow).total;
 }
 
 extern "C" int scorp_icp_point_to_point(const float *source, int32_t n_source, const float *target, int32_t n_target,
@@ -205,7 +482,29 @@ extern "C" int scorp_icp_point_to_point(const float *source, int32_t n_source, c
                                         double *out_transformation, double *out_fitness, double *out_inlier_rmse,
                                         int32_t *out_iterations, void *workspace, size_t workspace_bytes,
                                         scorp_stream_t stream) {
-  return icp_impl(source, n_source, target, n_target, inits, n_init, max_correspondence_distance, max_iteration,
-                  relative_fitness, relative_rmse, out_transformation, out_fitness, out_inlier_rmse, out_iterations, workspace,
-                  workspace_bytes, (hipStream_t)stream);
+  return icp_run<PointToPoint>(source, n_source, target, nullptr, n_target, inits, n_init, max_correspondence_distance, max_iteration,
+                               relative_fitness, relative_rmse, out_transformation, out_fitness, out_inlier_rmse, out_iterations,
+                               workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t scorp_icp_point_to_plane_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init) {
+  return IcpLayout(n_source, n_target, n_init, PointToPlane::kRow).total;
+}
+
+extern "C" int scorp_icp_point_to_plane(const float *source, int32_t n_source, const float *target, const float *target_normals,
+                                        int32_t n_target, const double *inits, int32_t n_init,
+                                        double max_correspondence_distance, int32_t max_iteration, double relative_fitness,
+                                        double relative_rmse, double *out_transformation, double *out_fitness,
+                                        double *out_inlier_rmse, int32_t *out_iterations, void *workspace,
+                                        size_t workspace_bytes, scorp_stream_t stream) {
+  return icp_run<PointToPlane>(source, n_source, target, target_normals, n_target, inits, n_init, max_correspondence_distance,
+                               max_iteration, relative_fitness, relative_rmse, out_transformation, out_fitness, out_inlier_rmse,
+                               out_iterations, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t scorp_estimate_normals_workspace_bytes(int32_t n) { return IcpLayout(0, n, 0, PointToPlane::kRow).total; }
+
+extern "C" int scorp_estimate_normals(const float *points, int32_t n, int32_t knn, float *out_normals, int32_t *out_neighbors,
+                                      void *workspace, size_t workspace_bytes, scorp_stream_t stream) {
+  return normals_impl(points, n, knn, out_normals, out_neighbors, workspace, workspace_bytes, (hipStream_t)stream);
 }

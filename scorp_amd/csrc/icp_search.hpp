@@ -1,6 +1,7 @@
-// icp_search.hpp - what the ICP kernels (icp.hip: point-to-point, icp_plane.hip: point-to-plane and the normal
-// estimation) share: the uniform grid over the target, the stable radix sort that orders the target by cell and the source
-// by Morton code, the exact outward ring search over the grid, and the host calls that build all of it once per call.
+// icp_search.hpp - what icp.hip (both ICP estimators and the normal estimation) and mesh_distance.hip (point-to-mesh
+// distance, nearest point of a cloud) share: the uniform grid over the target, the stable radix sort that orders the
+// target by cell and the source or the queries by Morton code, the exact outward ring walk over the grid (fp32 for the
+// point searches, float64 for the mesh's), the workspace check and the host calls that build all of it once per call.
 // Everything is in an unnamed namespace: each of the two files gets its own copy of the kernels.
 #pragma once
 #include <cmath>
@@ -256,19 +257,15 @@ __global__ void icp_init_kernel(const double *__restrict__ inits, int ni, double
 
 // ---- the search ----
 
-__device__ __forceinline__ double wave_sum_f64(double v) {   // fixed butterfly: the same order on every call
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// The outward walk both searches share: rings of cells at Chebyshev distance k around cell (cx, cy, cz), clipped to the
-// grid; visit(ca, cb) takes the cells ca..cb of one grid row (cell ids are raster order, x fastest, so their points are
+// The outward walk every search shares: rings of cells at Chebyshev distance k around cell (cx, cy, cz), clipped to the
+// grid; visit(ca, cb) takes the cells ca..cb of one grid row (cell ids are raster order, x fastest, so their entries are
 // one contiguous run).  After ring k, everything outside its box is at least lb away: the walk ends when lb^2 exceeds
-// reach() - the d^2 that still matters to the caller - or nothing is left outside the box.
-template <class Visit, class Reach>
-__device__ __forceinline__ void icp_ring_walk(float x, float y, float z, int cx, int cy, int cz, float lx, float ly, float lz,
-                                              float h, int dx, int dy, int dz, Visit visit, Reach reach) {
+// reach() - the d^2 that still matters to the caller - or nothing is left outside the box.  F: float for the point
+// searches (icp_nearest, the normals' k nearest), double for the mesh distance; `none` is F's "no side left".
+template <class F, class Visit, class Reach>
+__device__ __forceinline__ void icp_ring_walk(F x, F y, F z, int cx, int cy, int cz, F lx, F ly, F lz, F h, int dx, int dy, int dz,
+                                              Visit visit, Reach reach) {
+  const F none = sizeof(F) == sizeof(float) ? (F)3.4e38f : (F)__builtin_inf();
   for (int k = 0;; k++) {
     const int z0 = max(cz - k, 0), z1 = min(cz + k, dz - 1), y0 = max(cy - k, 0), y1 = min(cy + k, dy - 1);
     const int x0 = max(cx - k, 0), x1 = min(cx + k, dx - 1);
@@ -284,15 +281,15 @@ __device__ __forceinline__ void icp_ring_walk(float x, float y, float z, int cx,
       }
     }
     // what lies outside ring k's box is at least this far away (sides past the grid hold no points)
-    float lb = 3.4e38f;
-    if (cx - k > 0) lb = fminf(lb, x - (lx + (cx - k) * h));
-    if (cx + k < dx - 1) lb = fminf(lb, (lx + (cx + k + 1) * h) - x);
-    if (cy - k > 0) lb = fminf(lb, y - (ly + (cy - k) * h));
-    if (cy + k < dy - 1) lb = fminf(lb, (ly + (cy + k + 1) * h) - y);
-    if (cz - k > 0) lb = fminf(lb, z - (lz + (cz - k) * h));
-    if (cz + k < dz - 1) lb = fminf(lb, (lz + (cz + k + 1) * h) - z);
-    if (lb >= 3.4e38f) break;
-    lb = fmaxf(lb, 0.0f);
+    F lb = none;
+    if (cx - k > 0) lb = fmin(lb, x - (lx + (cx - k) * h));
+    if (cx + k < dx - 1) lb = fmin(lb, (lx + (cx + k + 1) * h) - x);
+    if (cy - k > 0) lb = fmin(lb, y - (ly + (cy - k) * h));
+    if (cy + k < dy - 1) lb = fmin(lb, (ly + (cy + k + 1) * h) - y);
+    if (cz - k > 0) lb = fmin(lb, z - (lz + (cz - k) * h));
+    if (cz + k < dz - 1) lb = fmin(lb, (lz + (cz + k + 1) * h) - z);
+    if (lb >= none) break;
+    lb = fmax(lb, (F)0);
     if (!(lb * lb <= reach())) break;   // (a NaN query ends here too)
   }
 }
@@ -386,16 +383,27 @@ int icp_build_target(const float *target, int nt, const IcpLayout &L, const IcpW
   return SCORP_OK;
 }
 
-// The source's side: its bounding box and the points in Morton order (W.sp).
-int icp_build_source(const float *source, int ns, const IcpLayout &L, const IcpWorkspace &W, hipStream_t stream) {
-  icp_bbox_kernel<<<1, 1024, 0, stream>>>(source, ns, W.g->slo, W.g->shi);
+// The Morton order of n points (an ICP source, the queries of a distance call): their bounding box into g->slo / shi, the
+// keys, the sort over the two buffer pairs.  *order: whichever of v0 / v1 holds the sorted original indices.
+int icp_sort_source(const float *points, int n, IcpGrid *g, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, uint32_t *hist,
+                    int64_t tiles, hipStream_t stream, const uint32_t **order) {
+  icp_bbox_kernel<<<1, 1024, 0, stream>>>(points, n, g->slo, g->shi);
   SCORP_KERNEL_CHECK("icp_bbox", 0, stream);
-  icp_source_keys_kernel<<<(ns + 255) / 256, 256, 0, stream>>>(source, ns, W.g, W.k0, W.v0);
+  icp_source_keys_kernel<<<(n + 255) / 256, 256, 0, stream>>>(points, n, g, k0, v0);
   SCORP_KERNEL_CHECK("icp_source_keys", 0, stream);
-  uint32_t *a = W.k0, *b = W.v0, *c = W.k1, *d = W.v1;
-  if (int e = radix_sort(a, b, c, d, ns, 32, L.tiles, W.hist, stream)) return e;
-  icp_gather_source_kernel<<<(ns + 255) / 256, 256, 0, stream>>>(source, b, ns, W.sp);
+  if (int e = radix_sort(k0, v0, k1, v1, n, 32, tiles, hist, stream)) return e;
+  *order = v0;   // (radix_sort swaps its pointer arguments: v0 is the sorted side here)
+  return SCORP_OK;
+}
+
+// The source's side: the points in Morton order (W.sp) and, where the caller wants it, that order.
+int icp_build_source(const float *source, int ns, const IcpLayout &L, const IcpWorkspace &W, hipStream_t stream,
+                     const uint32_t **order = nullptr) {
+  const uint32_t *sorted;
+  if (int e = icp_sort_source(source, ns, W.g, W.k0, W.v0, W.k1, W.v1, W.hist, L.tiles, stream, &sorted)) return e;
+  icp_gather_source_kernel<<<(ns + 255) / 256, 256, 0, stream>>>(source, sorted, ns, W.sp);
   SCORP_KERNEL_CHECK("icp_gather_source", 0, stream);
+  if (order) *order = sorted;
   return SCORP_OK;
 }
 
@@ -417,7 +425,16 @@ int icp_iterate(int ni, int max_iteration, const int32_t *active, hipStream_t st
   return SCORP_OK;
 }
 
-// The argument checks the two ICP entry points share (`pointers`: every pointer argument is non-NULL).
+// The workspace of every entry point built on this file: there, large enough, 256-byte aligned.
+int check_workspace(const char *who, const void *workspace, size_t bytes, size_t need) {
+  if (!workspace || bytes < need || ((uintptr_t)workspace & 255)) {
+    set_error("%s: workspace NULL, too small or not 256-byte aligned (%zu < %zu)", who, bytes, need);
+    return SCORP_ERR_INVALID;
+  }
+  return SCORP_OK;
+}
+
+// The argument checks the two ICP entry points share (`pointers`: every pointer argument but the workspace is non-NULL).
 int icp_check_args(const char *who, double r, int32_t ns, int32_t nt, int32_t max_iteration, int32_t ni, bool pointers) {
   if (!(r > 0.0) || !std::isfinite(r)) { set_error("%s: max_correspondence_distance must be a positive finite number", who); return SCORP_ERR_INVALID; }
   if (ns <= 0) { set_error("%s: empty source", who); return SCORP_ERR_INVALID; }

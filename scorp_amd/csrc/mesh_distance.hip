@@ -7,8 +7,8 @@
 //           (cell, triangle) pairs are a CSR built by count, scan and fill.  Before that the pairs are only COUNTED: while
 //           there are more than mesh_pair_cap(F) the cell edge grows by 1.25 and the count runs again (a host loop with
 //           one small read-back per trip), so two scene-sized triangles never cost more than the cap.
-//   query   the queries are sorted by Morton code (the ICP source's sort), one thread per query walks rings of cells
-//           outward in the shape of icp_ring_walk, all in float64, and tests every candidate by the closest point on the
+//   query   the queries are sorted by Morton code (icp_sort_source, the ICP source's sort), one thread per query walks rings
+//           of cells outward (icp_ring_walk in float64) and tests every candidate by the closest point on the
 //           triangle (vertex, edge and face regions; a triangle with a zero normal is its three segments).  The result is
 //           the minimum of (d^2, face) in lexicographic order and is written at the query's original position, so it does
 //           not depend on the fill order of the pairs (atomics), on the sort or on how often a triangle is met.
@@ -275,32 +275,7 @@ __global__ void __launch_bounds__(kMeshDistThreads) mesh_query_kernel(MeshView m
       if (d2 < best || (d2 == best && f < bface)) { best = d2; bface = f; }
     }
   };
-  for (int k = 0;; k++) {
-    const int z0 = max(cz - k, 0), z1 = min(cz + k, dz - 1), y0 = max(cy - k, 0), y1 = min(cy + k, dy - 1);
-    const int x0 = max(cx - k, 0), x1 = min(cx + k, dx - 1);
-    for (int iz = z0; iz <= z1; iz++) {
-      for (int iy = y0; iy <= y1; iy++) {
-        const int row = (iz * dy + iy) * dx;
-        if (iz == cz - k || iz == cz + k || iy == cy - k || iy == cy + k) {   // a face of the ring: the whole row
-          if (x0 <= x1) visit(row + x0, row + x1);
-        } else {                                                                 // inside: the row's two ends
-          if (cx - k >= 0) visit(row + cx - k, row + cx - k);
-          if (cx + k < dx) visit(row + cx + k, row + cx + k);
-        }
-      }
-    }
-    // rule 6: what lies outside ring k's box is at least lb away (sides past the grid hold no triangle)
-    double lb = __builtin_inf();
-    if (cx - k > 0) lb = fmin(lb, P.x - (lx + (cx - k) * h));
-    if (cx + k < dx - 1) lb = fmin(lb, (lx + (cx + k + 1) * h) - P.x);
-    if (cy - k > 0) lb = fmin(lb, P.y - (ly + (cy - k) * h));
-    if (cy + k < dy - 1) lb = fmin(lb, (ly + (cy + k + 1) * h) - P.y);
-    if (cz - k > 0) lb = fmin(lb, P.z - (lz + (cz - k) * h));
-    if (cz + k < dz - 1) lb = fmin(lb, (lz + (cz + k + 1) * h) - P.z);
-    if (!(lb < __builtin_inf())) break;
-    lb = fmax(lb, 0.0);
-    if (!(lb * lb <= best)) break;
-  }
+  icp_ring_walk(P.x, P.y, P.z, cx, cy, cz, lx, ly, lz, h, dx, dy, dz, visit, [&]() { return best; });   // rule 6
   if (bface == 0xFFFFFFFFu) {
     store_miss(j, out_d2, out_face, out_closest);
     return;
@@ -398,14 +373,6 @@ int check_mesh_counts(int64_t Nv, int64_t F, const char *who) {
   return SCORP_OK;
 }
 
-int check_workspace(const void *workspace, size_t bytes, size_t need, const char *who) {
-  if (!workspace || bytes < need || ((uintptr_t)workspace & 255)) {
-    set_error("%s: workspace NULL, too small or not 256-byte aligned (%zu < %zu)", who, bytes, need);
-    return SCORP_ERR_INVALID;
-  }
-  return SCORP_OK;
-}
-
 }  // namespace
 }  // namespace scorp
 
@@ -421,7 +388,7 @@ extern "C" int scorp_mesh_distance_build(const float *vertices, int64_t num_vert
   if (!vertices || !faces) { set_error("mesh_distance_build: NULL argument"); return SCORP_ERR_INVALID; }
   if (int e = check_mesh_counts(num_vertices, num_faces, "mesh_distance_build")) return e;
   const MeshDistLayout L(num_faces, 1);
-  if (int e = check_workspace(workspace, workspace_bytes, L.bytes, "mesh_distance_build")) return e;
+  if (int e = check_workspace("mesh_distance_build", workspace, workspace_bytes, L.bytes)) return e;
   hipStream_t s = (hipStream_t)stream;
   char *w = (char *)workspace;
   IcpGrid *g = (IcpGrid *)(w + L.grid);
@@ -484,19 +451,16 @@ extern "C" int scorp_mesh_distance_query(const float *vertices, int64_t num_vert
   if (!vertices || !faces) { set_error("mesh_distance_query: NULL argument"); return SCORP_ERR_INVALID; }
   if (int e = check_mesh_counts(num_vertices, num_faces, "mesh_distance_query")) return e;
   const MeshDistLayout L(num_faces, num_queries);
-  if (int e = check_workspace(workspace, workspace_bytes, L.bytes, "mesh_distance_query")) return e;
+  if (int e = check_workspace("mesh_distance_query", workspace, workspace_bytes, L.bytes)) return e;
   char *w = (char *)workspace;
   IcpGrid *g = (IcpGrid *)(w + L.grid);
-  uint32_t *k0 = (uint32_t *)(w + L.keys0), *v0 = (uint32_t *)(w + L.vals0), *k1 = (uint32_t *)(w + L.keys1), *v1 = (uint32_t *)(w + L.vals1);
-  const int nq = (int)num_queries;
-  icp_bbox_kernel<<<1, 1024, 0, s>>>(queries, nq, g->slo, g->shi);
-  SCORP_KERNEL_CHECK("icp_bbox", 0, s);
-  icp_source_keys_kernel<<<mesh_blocks(num_queries), 256, 0, s>>>(queries, nq, g, k0, v0);
-  SCORP_KERNEL_CHECK("icp_source_keys", 0, s);
-  if (int e = radix_sort(k0, v0, k1, v1, nq, 32, L.tiles, (uint32_t *)(w + L.hist), s)) return e;
+  const uint32_t *order;
+  if (int e = icp_sort_source(queries, (int)num_queries, g, (uint32_t *)(w + L.keys0), (uint32_t *)(w + L.vals0), (uint32_t *)(w + L.keys1),
+                              (uint32_t *)(w + L.vals1), (uint32_t *)(w + L.hist), L.tiles, s, &order))
+    return e;
   const MeshView m{vertices, faces, (int32_t)num_vertices, (int32_t)num_faces};
   const double max_d2 = max_distance * max_distance;
-  mesh_query_kernel<<<mesh_blocks(num_queries), kMeshDistThreads, 0, s>>>(m, queries, v0, num_queries, g, (const uint32_t *)(w + L.cell_start),
+  mesh_query_kernel<<<mesh_blocks(num_queries), kMeshDistThreads, 0, s>>>(m, queries, order, num_queries, g, (const uint32_t *)(w + L.cell_start),
                                                                          (const uint32_t *)(w + L.pairs), max_d2, out_squared_distance,
                                                                          out_face, out_closest);
   SCORP_KERNEL_CHECK("mesh_query", 0, s);
@@ -536,15 +500,15 @@ extern "C" int scorp_nearest_point_distance(const float *points, int32_t num_poi
   if (num_points == 0) return SCORP_OK;
   if (!points || !cloud || !out_squared_distance || !out_index) { set_error("nearest_point_distance: NULL argument"); return SCORP_ERR_INVALID; }
   const IcpLayout L(num_points, num_cloud, 0, 1);
-  if (int e = check_workspace(workspace, workspace_bytes, L.total, "nearest_point_distance")) return e;
+  if (int e = check_workspace("nearest_point_distance", workspace, workspace_bytes, L.total)) return e;
   hipStream_t s = (hipStream_t)stream;
   const IcpWorkspace W(workspace, L);
+  const uint32_t *order;
   if (int e = icp_build_target(cloud, num_cloud, L, W, s)) return e;
-  if (int e = icp_build_source(points, num_points, L, W, s)) return e;
-  // (the source's sort is four passes over two buffers, so the sorted order ends where it started: W.v0)
+  if (int e = icp_build_source(points, num_points, L, W, s, &order)) return e;
   const double r2 = max_distance * max_distance;
   const float r2f = (float)r2 * (1.0f + 1e-5f);   // the fp32 search keeps slightly more; the pair test is float64
-  nearest_point_kernel<<<mesh_blocks(num_points), kMeshDistThreads, 0, s>>>(W.sp, W.v0, num_points, cloud, W.g, W.cell_start, W.tq, r2, r2f,
+  nearest_point_kernel<<<mesh_blocks(num_points), kMeshDistThreads, 0, s>>>(W.sp, order, num_points, cloud, W.g, W.cell_start, W.tq, r2, r2f,
                                                                            out_squared_distance, out_index);
   SCORP_KERNEL_CHECK("nearest_point", 0, s);
   return SCORP_OK;

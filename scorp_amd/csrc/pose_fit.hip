@@ -56,12 +56,6 @@ struct PoseLayout {
   }
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {   // fixed butterfly: the same order on every call
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // The similarity q ~ s R p + t from centred moments: A = sum qc pc^T = U S V^T, D = diag(1, 1, det U det V < 0 ? -1 : 1),
 // R = U D V^T, s = sum(S diag D) / spp = trace(R^T A) / spp (Umeyama) or 1 (Kabsch), t = qm - s R pm.
 __device__ void pose_solve(const double A[3][3], double spp, const double pm[3], const double qm[3], bool with_scale, double R[3][3],

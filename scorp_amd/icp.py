@@ -4,12 +4,11 @@
 The reference runs Open3D's registration_icp (TransformationEstimationPointToPoint, no scaling, max_iteration=400) once
 per initial pose, 67 poses by default.  Here every init runs in one batch through scorp_icp_point_to_point
 (csrc/icp.hip): one launch per iteration covers all inits still running.  estimation="point_to_plane" runs the same
-batch through scorp_icp_point_to_plane (csrc/icp_plane.hip) on the target's normals: model_normals(gaussians) for a
-trained model, estimate_normals(points) for a bare cloud.  Swap it in with one import:
+batch through scorp_icp_point_to_plane (the same file, the other estimator) on the target's normals:
+model_normals(gaussians) for a trained model, estimate_normals(points) for a bare cloud.  Swap it in with one import:
 
     from scorp_amd.icp import get_ICP_fitting_transformation_best
 """
-import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -70,13 +69,6 @@ def _check_estimation(estimation):
         raise ValueError(f"unknown estimation {estimation!r}: expected one of {list(ESTIMATIONS)}")
 
 
-def _workspace(nbytes, dev):
-    """(the tensor that owns it, a 256-byte aligned pointer into it, the bytes from there)."""
-    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
-    ptr = (ws.data_ptr() + 255) // 256 * 256
-    return ws, ptr, ws.numel() - (ptr - ws.data_ptr())
-
-
 def estimate_normals(points, knn=30, return_neighbors=False):
     """Unit normals [n, 3] fp32 (a device tensor) of a cloud that brings none, such as 3DGS centres: per point the
     eigenvector of the smallest eigenvalue of the float64 covariance of its min(knn, n) exact nearest neighbours (itself
@@ -89,13 +81,12 @@ def estimate_normals(points, knn=30, return_neighbors=False):
     dev = _device(points)
     P = _points("points", points, dev)
     n, knn = P.shape[0], int(knn)
-    L = _C.lib()
-    ws, ws_ptr, ws_bytes = _workspace(L.scorp_estimate_normals_workspace_bytes(n), dev)
+    size = _C.lib().scorp_estimate_normals_workspace_bytes(n)
     normals = torch.empty(n, 3, dtype=torch.float32, device=dev)
     nb = torch.empty(n, knn, dtype=torch.int32, device=dev) if return_neighbors else None
     with torch.cuda.device(dev):
-        _C.check(L.scorp_estimate_normals(P.data_ptr(), n, knn, normals.data_ptr(), nb.data_ptr() if return_neighbors else None,
-                                          ws_ptr, ws_bytes, _C.current_stream_ptr()), "scorp_estimate_normals")
+        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
+        _C.call("scorp_estimate_normals", P, n, knn, normals, nb, workspace, size)
     return (normals, nb) if return_neighbors else normals
 
 
@@ -149,23 +140,17 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     L = _C.lib()
     if plane:
         Nq = estimate_normals(Q, knn=30) if target_normals is None else _points("target_normals", target_normals, dev)
-    size = L.scorp_icp_point_to_plane_workspace_bytes if plane else L.scorp_icp_workspace_bytes
-    ws, ws_ptr, ws_bytes = _workspace(size(P.shape[0], Q.shape[0], ni), dev)
+    size = (L.scorp_icp_point_to_plane_workspace_bytes if plane else L.scorp_icp_workspace_bytes)(P.shape[0], Q.shape[0], ni)
     T_in = torch.as_tensor(np.ascontiguousarray(T0), device=dev)
     T_out = torch.empty_like(T_in)
     fit = torch.empty(ni, dtype=torch.float64, device=dev)
     rmse = torch.empty(ni, dtype=torch.float64, device=dev)
     iters = torch.empty(ni, dtype=torch.int32, device=dev)
-    tail = (T_in.data_ptr(), ni, ctypes.c_double(r), int(max_iteration), ctypes.c_double(float(relative_fitness)),
-            ctypes.c_double(float(relative_rmse)), T_out.data_ptr(), fit.data_ptr(), rmse.data_ptr(), iters.data_ptr(), ws_ptr,
-            ws_bytes, _C.current_stream_ptr())
     with torch.cuda.device(dev):
-        if plane:
-            _C.check(L.scorp_icp_point_to_plane(P.data_ptr(), P.shape[0], Q.data_ptr(), Nq.data_ptr(), Q.shape[0], *tail),
-                     "scorp_icp_point_to_plane")
-        else:
-            _C.check(L.scorp_icp_point_to_point(P.data_ptr(), P.shape[0], Q.data_ptr(), Q.shape[0], *tail),
-                     "scorp_icp_point_to_point")
+        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
+        _C.call("scorp_icp_point_to_plane" if plane else "scorp_icp_point_to_point", P, P.shape[0], Q, *((Nq,) if plane else ()),
+                Q.shape[0], T_in, ni, r, int(max_iteration), float(relative_fitness), float(relative_rmse), T_out, fit, rmse, iters,
+                workspace, size)
     return ICPResult(T_out.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy())
 
 
@@ -209,10 +194,7 @@ def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refi
     center_refined = ref.mean(axis=0)
     src = ref[downsample_indices(len(orig), len(ref))]
     inits = icp_inits(rotations, center_original, center_refined)
-    if estimation == "point_to_point":
-        res = registration_icp(src, orig, threshold, inits, max_iteration=max_iteration)
-    else:
-        res = registration_icp(src, orig, threshold, inits, max_iteration=max_iteration, estimation=estimation,
-                               target_normals=target_normals)
+    res = registration_icp(src, orig, threshold, inits, max_iteration=max_iteration, estimation=estimation,
+                           target_normals=target_normals)
     best = int(np.argmax(res.fitness))   # the first maximum: the reference keeps a pose only on a strictly higher fitness
     return res.transformation[best].copy()

@@ -1,15 +1,17 @@
-"""Compare the gfx950 instruction streams of the per-primitive and surfel kernels of two source trees.
+"""Compare the gfx950 instruction streams of the kernels of two source trees.
 
-    python scripts/isa_compare.py <tree A> <tree B> [--title TEXT]      (markdown on stdout)
+    python scripts/isa_compare.py <tree A> <tree B> [--title TEXT] [--files-a F,F,...] [--files-b F,F,...]   (markdown on stdout)
 
-Compiles csrc/gs2d*.hip (gs2d_maps.hip apart) and csrc/gs3d_pergaussian.hip of both trees to assembly with the command
-line of tests/test_kernel_resources.py (the library's flags plus --cuda-device-only -S), splits the text per kernel
+Compiles the named files of csrc/ (by default csrc/gs2d*.hip, gs2d_maps.hip apart, and csrc/gs3d_pergaussian.hip; --files-b
+defaults to --files-a) of both trees to assembly with the command line of tests/test_kernel_resources.py (the library's flags plus --cuda-device-only -S), splits the text per kernel
 symbol, drops directives and comments, and reports per kernel whether the instruction sequence is identical, a
 permutation, or different, next to the compiler's resource summary of both sides.  A kernel that is different but
 becomes a permutation once register numbers are masked is reported as "permuted, registers renamed": that is NOT a
 permutation, only the mildest kind of difference.  It compares text only.  Basic-block labels carry the ordinal of the
 function within its file, which a move between files changes: they are renumbered per kernel in order of appearance
-before the comparison."""
+before the comparison.  Kernels are matched by symbol.  A kernel of a shared header exists once per file that includes
+it: such copies are matched by file name, and a copy whose file the other tree does not have against the other tree's
+first copy."""
 import collections
 import concurrent.futures
 import glob
@@ -25,8 +27,10 @@ from tests.test_kernel_resources import asm_command  # noqa: E402
 FIGURES = ("NumVgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize", "Occupancy")   # (as the compiler's summary names them)
 
 
-def sources(tree):
+def sources(tree, names=None):
     csrc = os.path.join(tree, "scorp_amd", "csrc")
+    if names:
+        return [os.path.join(csrc, n) for n in names]
     files = [f for f in sorted(glob.glob(os.path.join(csrc, "gs2d*.hip"))) if os.path.basename(f) != "gs2d_maps.hip"]
     return files + [os.path.join(csrc, "gs3d_pergaussian.hip")]
 
@@ -90,42 +94,66 @@ def verdict_of(ia, ib):
     return "DIFFERENT"
 
 
-def tree_kernels(tree):
+def tree_kernels(tree, names=None):
+    """{symbol: [(file, instructions, figures) of every file that has it]}"""
     with concurrent.futures.ThreadPoolExecutor(max_workers=4) as pool:
-        srcs = sources(tree)
+        srcs = sources(tree, names)
         texts = list(pool.map(lambda s: assembly(tree, s), srcs))
     out = {}
     for s, t in zip(srcs, texts):
         for k, v in kernels(t, os.path.basename(s)).items():
-            assert k not in out, f"{k} in {out[k][0]} and {v[0]}"
-            out[k] = v
+            out.setdefault(k, []).append(v)
     return out
+
+
+def matched(a, b):
+    """[(symbol, copy of A or None, copy of B or None)]"""
+    rows = []
+    for k in sorted(set(a) | set(b)):
+        ca, cb = a.get(k, []), b.get(k, [])
+        if not ca or not cb:
+            rows += [(k, v, None) for v in ca] + [(k, None, v) for v in cb]
+            continue
+        by_file = {v[0]: v for v in cb}
+        used = set()
+        for v in ca:
+            w = by_file.get(v[0], cb[0])
+            used.add(w[0])
+            rows.append((k, v, w))
+        rows += [(k, ca[0], w) for w in cb if w[0] not in used]
+    return rows
+
+
+def option(name):
+    return sys.argv[sys.argv.index(name) + 1].split(",") if name in sys.argv else None
 
 
 def main():
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     title = sys.argv[sys.argv.index("--title") + 1] if "--title" in sys.argv else "Instruction streams"
-    a, b = tree_kernels(sys.argv[1]), tree_kernels(sys.argv[2])
+    files_a = option("--files-a")
+    a, b = tree_kernels(sys.argv[1], files_a), tree_kernels(sys.argv[2], option("--files-b") or files_a)
+    rows = matched(a, b)
     verdicts = collections.Counter()
     print(f"## {title}\n")
     print("| kernel | A | B | instructions A / B | sequence | " + " | ".join(FIGURES) + " |")
     print("|---|---|---|---|---|" + "---|" * len(FIGURES))
-    for k in sorted(set(a) | set(b)):
-        if k not in a or k not in b:
-            verdict = "only in A" if k in a else "only in B"
-            fa = a.get(k, b.get(k))
-            print(f"| `{k}` | {a[k][0] if k in a else '-'} | {b[k][0] if k in b else '-'} | - | {verdict} | " + " | ".join(str(fa[2].get(f)) for f in FIGURES) + " |")
+    for k, va, vb in rows:
+        if va is None or vb is None:
+            verdict = "only in A" if va else "only in B"
+            fa = va or vb
+            print(f"| `{k}` | {va[0] if va else '-'} | {vb[0] if vb else '-'} | - | {verdict} | " + " | ".join(str(fa[2].get(f)) for f in FIGURES) + " |")
             verdicts[verdict] += 1
             continue
-        (fa, ia, ra), (fb, ib, rb) = a[k], b[k]
+        (fa, ia, ra), (fb, ib, rb) = va, vb
         verdict = verdict_of(ia, ib)
         if ra != rb:
             verdict += ", RESOURCES DIFFER"
         verdicts[verdict] += 1
         figs = " | ".join(str(ra.get(f)) if ra.get(f) == rb.get(f) else f"{ra.get(f)} -> {rb.get(f)}" for f in FIGURES)
         print(f"| `{k}` | {fa} | {fb} | {len(ia)} / {len(ib)} | {verdict} | {figs} |")
-    print("\n" + ", ".join(f"{n} {v}" for v, n in sorted(verdicts.items())) + f" ({len(set(a) | set(b))} kernels).\n")
+    print("\n" + ", ".join(f"{n} {v}" for v, n in sorted(verdicts.items())) + f" ({len(rows)} kernels).\n")
 
 
 if __name__ == "__main__":

@@ -4,8 +4,8 @@ threshold).  Prints one JSON line: total ms per call (median of --reps after a w
 the 16-thread scipy cKDTree correspondence pass of the yardstick on the same machine.  --estimation point_to_plane runs
 the same fixture through scorp_icp_point_to_plane on normals estimated from the target (knn 30), and times that
 estimation too.  The per-pass kernel time comes from a run under `rocprofv3 --kernel-trace` (icp_pass_kernel /
-icp_solve_kernel, icp_plane_pass_kernel / icp_plane_solve_kernel: the first launch has every init active, the last ones
-a single init)."""
+icp_solve_kernel, icp_plane_pass_kernel / icp_plane_solve_kernel, the four thin kernels of csrc/icp.hip around its one
+pass body and one solve body: the first launch has every init active, the last ones a single init)."""
 import argparse
 import json
 import os

@@ -1,5 +1,5 @@
-"""Register budget of the point-to-plane ICP and normal-estimation kernels (icp_plane.hip), checked at compile time (no
-GPU), as tests/test_icp_resources.py checks icp.hip's: the pass carries 29 float64 sums and the ring search in registers -
+"""Register budget of the point-to-plane ICP and normal-estimation kernels (icp.hip), checked at compile time (no
+GPU), as tests/test_icp_resources.py checks the point-to-point pair of the same file: the pass carries 29 float64 sums and the ring search in registers -
 no scratch, at most 128 VGPRs (four waves per SIMD) - the normals kernel keeps its candidate list in LDS, not in scratch,
 and no kernel of the file spills."""
 import os
@@ -12,7 +12,7 @@ from tests.test_kernel_resources import _resources
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_icp_plane_kernels_keep_their_occupancy():
-    res = _resources("icp_plane.hip")
+    res = _resources("icp.hip")
     search = {k: v for k, v in res.items() if "icp_plane_pass_kernel" in k}
     assert len(search) == 1, sorted(res)
     for name, r in search.items():
