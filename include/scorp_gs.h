@@ -730,6 +730,72 @@ int scorp_nearest_point_distance(const float *points, int32_t num_points, const 
                                  double *out_squared_distance, int32_t *out_index, void *workspace, size_t workspace_bytes,
                                  scorp_stream_t stream);
 
+/* ---- looking at a mesh: depth, face, barycentric and colour maps of a triangle mesh from any number of cameras, and the
+ * number of views in which each face owns a pixel (a z-buffer rasterizer; scorp_amd/mesh/render.py) ----
+ * The rules below ARE the specification, and three of them are this project's own: positions are snapped to 1/256 pixel,
+ * nothing is clipped against the near plane (a triangle with a vertex behind it is dropped whole), and of two faces with
+ * the same fp32 depth at a pixel the lower index wins.  Nothing was compared with Open3D's or any other renderer's output.
+ * tests/mesh_render_reference.py restates coverage and depth with exact integers and fractions.
+ *
+ * Inputs (device): vertices[Nv, 3] float32; faces[F, 3] int32; colors[Nv, 3] float32 or NULL; full_proj[V, 16] float32, each
+ * camera's full_proj_transform as stored (row-major m[r][c], a point is a ROW vector: the layout scorp_tsdf_fuse takes);
+ * height H, width W; near > 0; flags; optionally support_depth[V, H, W] float32 with support_tolerance.
+ *
+ *  1. Projection, float64 on the float32 values, every product, quotient and sum rounded on its own (no fp contraction).
+ *     For vertex (x, y, z): p_j = ((z m[2][j] + (y m[1][j] + x m[0][j])) + m[3][j]) for j = 0, 1, 3; w = p_3 (for this
+ *     projection the view-space z), inv_w = 1.0 / w, sx = ((p_0 inv_w + 1) W - 1) 0.5, sy = ((p_1 inv_w + 1) H - 1) 0.5:
+ *     the splat rasterizers' pixel convention, pixel (i, j) has its centre AT (i, j), so the maps line up with render_depth
+ *     pixel for pixel.
+ *  2. Snapping.  X = (int64) floor(sx 256 + 0.5), Y likewise: positions in units of 1/256 pixel.  A vertex is unusable for
+ *     a view unless w > near, w < +inf, |floor(sx 256 + 0.5)| <= 2^29 and the same for y (a NaN fails every test).  A
+ *     triangle with an unusable vertex is DROPPED for that view: there is no clipping against the near plane, so a triangle
+ *     that crosses it disappears whole.  A face with an index outside [0, Nv) is dropped too; such an index is never followed.
+ *  3. Set-up, all int64.  The edge function of the edge a -> b at P is E(P) = (b_Y - a_Y)(P_X - a_X) - (b_X - a_X)(P_Y - a_Y).
+ *     With the corners (v_0, v_1, v_2), E_0 belongs to v_1 -> v_2, E_1 to v_2 -> v_0, E_2 to v_0 -> v_1 (the edge opposite
+ *     corner k), and A = E_2(v_2) is twice the signed area: A > 0 for corners that run counter-clockwise as the image is
+ *     looked at (x to the right, y down), the side of a face whose right-hand normal points at the camera.  A = 0: dropped.
+ *     A < 0: dropped when SCORP_MESH_RENDER_CULL_BACKFACES is set, else corners 1 and 2 change places (local order
+ *     v_0, v_2, v_1), which makes A > 0; rule 6 undoes the exchange.  E_0 + E_1 + E_2 = A at every P.  Coordinates are at
+ *     most 2^29 in size and pixel centres at most 2^22, so a difference stays below 2^30 + 2^22, a product below 2^61 and an
+ *     edge function below 2^62: nothing overflows.
+ *  4. Coverage, exact.  The pixel centre P = (256 i, 256 j) belongs to the triangle iff for every k: E_k(P) > 0, or
+ *     E_k(P) = 0 and the edge a -> b of E_k is a LEFT edge, b_Y - a_Y > 0 (it runs down the image), or a TOP edge,
+ *     b_Y - a_Y = 0 and b_X - a_X < 0.  That is the sign of E_k at P + (eps, eps^2) for a vanishing eps > 0, so any set
+ *     of triangles that tile a region without overlap own each pixel centre of it exactly once, on shared edges and at
+ *     shared corners too.  Only centres with 0 <= i < W and 0 <= j < H inside the triangle's bounding box are looked at.
+ *  5. Depth.  q = ((double) E_0 inv_w_0 + (double) E_1 inv_w_1) + (double) E_2 inv_w_2 in the local order, float64, no
+ *     contraction; depth = (float) ((double) A / q), the perspective-correct view-space depth (> 0).  The z-buffer holds
+ *     one uint64 per (view, pixel), cleared to all ones and updated by an unsigned 64-bit atomic minimum with the key
+ *     (uint64) bits(depth) << 32 | face: the nearest depth wins, equal fp32 depths go to the lower face index.  The
+ *     minimum is order-free, so the maps do not depend on the launch shape, on which path a triangle took, on the order
+ *     the faces arrive in or on how many views share a call.
+ *  6. Resolve, per (view, pixel).  An all-ones key: depth 0, face -1, barycentrics and colour 0.  Else depth and face from
+ *     the key, and from the winner's set-up b_k = ((double) E_k inv_w_k) / q in the local order, put back into the face's
+ *     own order (b_1 and b_2 change places when rule 3 exchanged the corners): out_barycentric[V, 3, H, W] = (float) b_k;
+ *     out_color[V, 3, H, W] = (float) ((b_0 c_0 + b_1 c_1) + b_2 c_2) per channel, c_k the colour of the face's k-th
+ *     vertex, float64 and rounded once.
+ *  7. Visibility.  out_visible_views[F] int32 is INCREASED by the number of views of this call in which the face owns at
+ *     least one pixel (the caller zeroes it; calls over chunks of the views accumulate).  With support_depth, a pixel
+ *     counts only if support_depth > 0 there and fabsf(depth - support_depth) <= support_tolerance in fp32.  (A flag per
+ *     (view, face) that any number of threads set to 1, then summed per face: order-free.)
+ *
+ * A triangle whose clipped box holds at most 64 pixel centres is walked by one thread, any other by a workgroup; the list
+ * of the latter has room for every face of every view, so it cannot overflow and the call never reads anything back: it
+ * does not synchronise.  Workspace: scorp_mesh_render_workspace_bytes (16 V Nv + 8 V H W + 5 V F bytes and padding; 0 for
+ * sizes outside the limits), 256-byte aligned; after the call its first V uint32 hold the length of each view's list of
+ * workgroup-walked triangles (a figure for measurements; no result depends on it).  out_barycentric, out_color and out_visible_views may be NULL and are then
+ * skipped; num_faces = 0 renders empty maps.
+ * SCORP_ERR_INVALID: a NULL required pointer (out_color without colors included), num_vertices outside [1, 2^30],
+ * num_faces outside [0, 2^28], num_views outside [1, 65535], height or width outside [1, 16384], near not positive and
+ * finite, unknown flags, support_tolerance negative or NaN beside a support_depth, a workspace too small or misaligned. */
+#define SCORP_MESH_RENDER_CULL_BACKFACES 1u   /* rule 3: drop the faces with A < 0 */
+size_t scorp_mesh_render_workspace_bytes(int64_t num_vertices, int64_t num_faces, int32_t num_views, int32_t height, int32_t width);
+int scorp_mesh_render(const float *vertices, int64_t num_vertices, const int32_t *faces, int64_t num_faces, const float *colors,
+                      const float *full_proj, int32_t num_views, int32_t height, int32_t width, double near, uint32_t flags,
+                      const float *support_depth, float support_tolerance, float *out_depth, int32_t *out_face,
+                      float *out_barycentric, float *out_color, int32_t *out_visible_views, void *workspace,
+                      size_t workspace_bytes, scorp_stream_t stream);
+
 /* ---- bounded TSDF volume: sparse 16^3-voxel blocks, fused and meshed (the route of gs2dgs/utils/mesh_utils.py:138-180
  * extract_mesh_bounded, which hands the work to Open3D's ScalableTSDFVolume) ----
  * Open3D's volume could be neither read nor run where this was written.  The rules below ARE the specification; nothing

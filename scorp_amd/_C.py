@@ -136,6 +136,7 @@ EXPORTS = [
     "scorp_mesh_decimate_select", "scorp_mesh_decimate_apply", "scorp_mesh_decimate_faces",
     "scorp_mesh_distance_workspace_bytes", "scorp_mesh_distance_build", "scorp_mesh_distance_query", "scorp_mesh_sample_points",
     "scorp_nearest_point_workspace_bytes", "scorp_nearest_point_distance",
+    "scorp_mesh_render_workspace_bytes", "scorp_mesh_render",
     "scorp_tsdf_blocks_touch", "scorp_tsdf_blocks_neighbors", "scorp_tsdf_blocks_integrate",
     "scorp_isosurface_blocks_count_cells", "scorp_isosurface_blocks_emit_vertices", "scorp_isosurface_blocks_count_faces",
     "scorp_isosurface_blocks_emit_faces",
@@ -150,6 +151,7 @@ BACKWARD_SCRATCH_ZEROED = 2   # scorp_gs3d_backward_ex flag: the caller cleared 
 BACKWARD_DETERMINISTIC = 4    # scorp_gs3d_backward_ex flag: no float atomics (plain partial rows + an ordered per-Gaussian sum)
 VOTE_SUMS, VOTE_GRADIENT, VOTE_BINARY = 0, 1, 2   # methods of scorp_gs3d_mask_vote / scorp_gs2d_mask_vote
 POSE_UMEYAMA, POSE_KABSCH = 0, 1   # methods of scorp_pose_ransac
+MESH_RENDER_CULL_BACKFACES = 1   # flag of scorp_mesh_render (include/scorp_gs.h)
 ERR_INVALID, ERR_NO_INLIERS = -1, -4   # return codes the Python layer tells apart (include/scorp_gs.h)
 
 _lib = None
@@ -289,6 +291,10 @@ def lib():
     L.scorp_nearest_point_workspace_bytes.restype = sz
     L.scorp_nearest_point_workspace_bytes.argtypes = [i32, i32]
     L.scorp_nearest_point_distance.argtypes = [vp, i32, vp, i32, f64, vp, vp, vp, sz, vp]
+    L.scorp_mesh_render_workspace_bytes.restype = sz
+    L.scorp_mesh_render_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
+    L.scorp_mesh_render.argtypes = [vp, i64, vp, i64, vp, vp, i32, i32, i32, f64, ctypes.c_uint32, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp,
+                                    sz, vp]
     bv, f32 = ctypes.POINTER(ScorpTsdfBlockViews), ctypes.c_float
     L.scorp_tsdf_blocks_touch.argtypes = [bv, f32, f32, i32, vp, vp, u64, vp, vp]
     L.scorp_tsdf_blocks_neighbors.argtypes = [vp, i64, vp, vp]

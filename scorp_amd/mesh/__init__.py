@@ -27,7 +27,9 @@ target triangle count by edge collapses, an independent set of edges per round (
 project's own rules, in include/scorp_gs.h).  `point_mesh_distance`, `sample_points_uniformly`, `nearest_point_distance`
 and the figures of `mesh_distance` / `mesh_cloud_distance` MEASURE a mesh: the exact distance to the nearest triangle through a
 uniform grid of (cell, triangle) pairs, in float64 (csrc/mesh_distance.hip; held to a float64 brute force of another
-formulation, tests/mesh_distance_reference.py).
+formulation, tests/mesh_distance_reference.py).  `render_mesh`, `face_visibility`, `cull_unseen_faces` and `depth_difference`
+LOOK at a mesh from cameras: a z-buffer rasterizer with exact integer coverage and one 64-bit atomic minimum per candidate
+(csrc/mesh_render.hip; this project's own rules, held to exact integers and fractions by tests/mesh_render_reference.py).
 
 CUDA tensors run the HIP kernels; CPU tensors run a torch / numpy form of the same statements.
 
@@ -40,6 +42,7 @@ One module per subsystem, every public name re-exported here:
     simplify.py   cluster_vertices, simplify_vertex_clustering
     decimate.py   simplify_quadric_decimation and its host loop _decimate over _DecimateHip / _DecimateNumpy
     distance.py   point_mesh_distance, sample_points_uniformly, nearest_point_distance, mesh_distance, mesh_cloud_distance
+    render.py     render_mesh, face_visibility, cull_unseen_faces, depth_difference
     extractor.py  focus_point, GaussianExtractor (imports the others; nothing imports it)
 Every stream-taking C-ABI call of the package goes through _C.call.  A test that patches a module global (tsdf.LAUNCH_SAMPLES) patches the
 home module: the names below are copies.
@@ -53,6 +56,8 @@ from .distance import (MAX_CLOUD_POINTS, MAX_QUERIES, PAIR_CAP_FACTOR, PAIR_CAP_
                        SurfaceSamples, mesh_cloud_distance, mesh_distance, nearest_point_distance, point_mesh_distance,
                        sample_points_uniformly, triangle_area_prefix)
 from .extractor import GaussianExtractor, focus_point
+from .render import (MAX_RENDER_SIDE, MAX_RENDER_VIEWS, WORKSPACE_CAP, DepthDifference, MeshRender, _render_mesh_numpy, cull_unseen_faces,
+                     depth_difference, face_visibility, render_mesh)
 from .simplify import CELL_SIDE, CONTRACTIONS, QUADRIC_TRUNCATE, cluster_vertices, simplify_vertex_clustering
 from .surface import _scan_counts, _surface_nets_numpy, extract_surface
 from .tsdf import LAUNCH_SAMPLES, MAX_RANGE, tsdf_fuse, uncontract

@@ -7,6 +7,7 @@ import torch
 
 from ._common import Mesh, _check_method, empty_mesh
 from .blocks import extract_surface_blocks, tsdf_blocks_fuse
+from .render import cull_unseen_faces, render_mesh
 from .surface import extract_surface
 from .tsdf import MAX_RANGE, tsdf_fuse, uncontract
 
@@ -157,6 +158,23 @@ class GaussianExtractor:
         depth, rgb, world_to_cam, intrinsics = self.bounded_views(depth_trunc, mask_backgrond)
         return extract_surface_blocks(tsdf_blocks_fuse(depth, rgb, world_to_cam, intrinsics, voxel_size, sdf_trunc, stride=stride),
                                       method=method)
+
+    @torch.no_grad()
+    def render_mesh(self, mesh, **kw):
+        """render_mesh (render.py) from the views kept by reconstruction(), on their pixel grid: the depth of the result
+        compares with self.depthmaps pixel for pixel (depth_difference)."""
+        self._need_maps()
+        _, H, W = self.depthmaps.shape
+        return render_mesh(mesh, self.full_proj, H, W, **kw)
+
+    @torch.no_grad()
+    def cull_unseen_faces(self, mesh, min_views=1, depth_tolerance=None):
+        """The faces of `mesh` that own a pixel in at least `min_views` of the kept views (cull_unseen_faces, render.py);
+        with depth_tolerance only the pixels where the surfel depth map has a value within that distance of the mesh's."""
+        self._need_maps()
+        _, H, W = self.depthmaps.shape
+        return cull_unseen_faces(mesh, self.full_proj, H, W, support_depth=None if depth_tolerance is None else self.depthmaps,
+                                 support_tolerance=depth_tolerance, min_views=min_views)
 
     @torch.no_grad()
     def export_image(self, path):
