@@ -796,6 +796,74 @@ int scorp_mesh_render(const float *vertices, int64_t num_vertices, const int32_t
                       float *out_barycentric, float *out_color, int32_t *out_visible_views, void *workspace,
                       size_t workspace_bytes, scorp_stream_t stream);
 
+/* ---- smoothing a mesh, and its normals: face and vertex normals, Laplacian and Taubin half-steps, the normal map of a
+ * rendered mesh (what Open3D's compute_triangle_normals / compute_vertex_normals / filter_smooth_laplacian /
+ * filter_smooth_taubin are used for; scorp_amd/mesh/smooth.py) ----
+ * The rules below ARE the specification and they are this project's own.  Nothing here was or can be compared with Open3D's
+ * output: Open3D was not available, and its summation order is not part of its interface.  The inverse-distance weights of
+ * rule 7 are what Open3D's Laplacian filter is BELIEVED to use; that was not checked.  tests/mesh_smooth_reference.py
+ * restates the rules as per-vertex loops over Python sets, lists and floats.
+ *
+ * Inputs (device): vertices[Nv, 3] float32; faces[F, 3] int32.  All arithmetic is float64 on the float32 values, every
+ * product, quotient, square root and sum rounded on its own (no fp contraction), and each output is rounded to float32 once.
+ *
+ *  1. Sides.  A face (a, b, c) has the sides (a, b), (b, c), (c, a).  A side with equal ends is ignored.  Indices out of
+ *     range are refused by the Python layer (check_mesh); the kernels skip them and never follow one.
+ *  2. Neighbours of vertex v: the distinct other ends of the sides that name v, in ascending order, each once - however many
+ *     faces share the side, so duplicate faces and non-manifold edges change nothing.  As a CSR: neighbor_offsets[Nv + 1]
+ *     int32, neighbors[neighbor_offsets[Nv]] int32.
+ *  3. Incident corners of v: one entry per face corner that names v, exactly 3 F entries in all, in ascending face index; a
+ *     face that names v twice is listed twice.  As a CSR: corner_offsets[Nv + 1] int32, corner_faces[3 F] int32.
+ *  4. Boundary.  A vertex is a boundary vertex when it is an end of an undirected side {a, b} that occurs exactly once over
+ *     all faces.
+ *  5. Face normal.  e1 = b - a, e2 = c - a; n = e1 x e2 component by component, n_x = e1_y e2_z - e1_z e2_y,
+ *     n_y = e1_z e2_x - e1_x e2_z, n_z = e1_x e2_y - e1_y e2_x.  Its unit form is n / sqrt((n_x^2 + n_y^2) + n_z^2); a zero
+ *     length gives (+0, +0, +0).
+ *  6. Vertex normal: the float64 sum over the incident corners in rule 3's order, s = s + n per component, of n
+ *     (SCORP_MESH_NORMALS_AREA: weighted by twice the face's area) or of n's unit form (SCORP_MESH_NORMALS_UNIFORM); the sum
+ *     is normalised as in rule 5 and rounded to float32 once.  A zero sum and a vertex with no face give +0.  There is no
+ *     angle weighting: it needs acos, which no reference here reproduces bit for bit.
+ *  7. Half-step with factor f.  A vertex with no neighbour, and a fixed vertex, is copied.  Otherwise with p the vertex and
+ *     q_j its neighbours in rule 2's order: s = s + w_j q_j per component and W = W + w_j, from s = 0 and W = 0; the new
+ *     position is (float) (p + f (s / W - p)) per component.  SCORP_MESH_SMOOTH_UNIFORM: w_j = 1.
+ *     SCORP_MESH_SMOOTH_INVERSE_DISTANCE: w_j = 1 / (sqrt((d_x^2 + d_y^2) + d_z^2) + 1e-12) with d = p - q_j.  Every
+ *     half-step reads the float32 output of the half-step before it and writes another buffer (Jacobi, never in place).
+ *  8. Filters (Python).  filter_smooth_laplacian(n, lambda) is n half-steps with factor lambda; filter_smooth_taubin(n,
+ *     lambda, mu) is n times [lambda, mu]; the defaults are n = 1, lambda = 0.5, mu = -0.53.  n = 0 returns the input's
+ *     positions bit for bit.  Faces and colours are never touched.  fix_boundary fixes rule 4's vertices.
+ *
+ * scorp_mesh_face_normals: out_normals[F, 3] = (float) n, or n's unit form when `normalized` is not 0; a face with an
+ * index outside [0, Nv) gives +0.
+ * scorp_mesh_vertex_normals: out_normals[Nv, 3] by rule 6.  A slice of the CSR is clamped to [0, 3 F] and an entry outside
+ * [0, F) is skipped.
+ * scorp_mesh_smooth: enqueues all num_steps half-steps, step k with factors[k] (HOST doubles, read before the call
+ * returns), without synchronising.  It ping-pongs between `scratch` and `out` (each [Nv, 3] float32, neither may be
+ * `vertices`; scratch may be NULL for num_steps <= 1) and the last half-step lands in `out` for odd and even counts alike;
+ * num_steps = 0 copies vertices to out.  `fixed`: uint8[Nv], not 0 = the vertex is copied, or NULL.  A slice of the CSR is
+ * clamped to [0, offsets[Nv]] and a neighbour outside [0, Nv) is skipped; a vertex whose neighbours are all skipped is copied.
+ * scorp_mesh_normal_map: per (view, pixel) of a mesh render's face map[V, H, W] int32 and barycentric map[V, 3, H, W]
+ * (rule 6 of the mesh-render block): out_normals[V, 3, H, W] float32 in world space.  With vertex_normals[Nv, 3] float32 the
+ * value is ((b_0 N_a + b_1 N_b) + b_2 N_c) per component, normalised as in rule 5; with NULL it is the face's unit normal
+ * of rule 5 and barycentric may be NULL.  A pixel whose face is -1, or outside [0, F), gives +0.
+ * SCORP_ERR_INVALID: a NULL required pointer, num_vertices outside [1, 2^30], num_faces outside [0, 2^28], an unknown
+ * weighting or weights, num_steps outside [0, 2^20], a factor that is not finite, aliased buffers, num_views outside
+ * [1, 65535], height or width outside [1, 16384], vertex_normals without barycentric. */
+#define SCORP_MESH_NORMALS_AREA 0
+#define SCORP_MESH_NORMALS_UNIFORM 1
+#define SCORP_MESH_SMOOTH_UNIFORM 0
+#define SCORP_MESH_SMOOTH_INVERSE_DISTANCE 1
+int scorp_mesh_face_normals(const float *vertices, int64_t num_vertices, const int32_t *faces, int64_t num_faces, int32_t normalized,
+                            float *out_normals, scorp_stream_t stream);
+int scorp_mesh_vertex_normals(const float *vertices, int64_t num_vertices, const int32_t *faces, int64_t num_faces,
+                              const int32_t *corner_offsets, const int32_t *corner_faces, int32_t weighting, float *out_normals,
+                              scorp_stream_t stream);
+int scorp_mesh_smooth(const float *vertices, int64_t num_vertices, const int32_t *offsets, const int32_t *neighbors,
+                      const uint8_t *fixed, const double *factors, int32_t num_steps, int32_t weights, float *scratch, float *out,
+                      scorp_stream_t stream);
+int scorp_mesh_normal_map(const float *vertices, int64_t num_vertices, const int32_t *faces, int64_t num_faces,
+                          const float *vertex_normals, const int32_t *face_map, const float *barycentric, int32_t num_views,
+                          int32_t height, int32_t width, float *out_normals, scorp_stream_t stream);
+
 /* ---- bounded TSDF volume: sparse 16^3-voxel blocks, fused and meshed (the route of gs2dgs/utils/mesh_utils.py:138-180
  * extract_mesh_bounded, which hands the work to Open3D's ScalableTSDFVolume) ----
  * Open3D's volume could be neither read nor run where this was written.  The rules below ARE the specification; nothing

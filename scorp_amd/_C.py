@@ -137,6 +137,7 @@ EXPORTS = [
     "scorp_mesh_distance_workspace_bytes", "scorp_mesh_distance_build", "scorp_mesh_distance_query", "scorp_mesh_sample_points",
     "scorp_nearest_point_workspace_bytes", "scorp_nearest_point_distance",
     "scorp_mesh_render_workspace_bytes", "scorp_mesh_render",
+    "scorp_mesh_face_normals", "scorp_mesh_vertex_normals", "scorp_mesh_smooth", "scorp_mesh_normal_map",
     "scorp_tsdf_blocks_touch", "scorp_tsdf_blocks_neighbors", "scorp_tsdf_blocks_integrate",
     "scorp_isosurface_blocks_count_cells", "scorp_isosurface_blocks_emit_vertices", "scorp_isosurface_blocks_count_faces",
     "scorp_isosurface_blocks_emit_faces",
@@ -152,6 +153,8 @@ BACKWARD_DETERMINISTIC = 4    # scorp_gs3d_backward_ex flag: no float atomics (p
 VOTE_SUMS, VOTE_GRADIENT, VOTE_BINARY = 0, 1, 2   # methods of scorp_gs3d_mask_vote / scorp_gs2d_mask_vote
 POSE_UMEYAMA, POSE_KABSCH = 0, 1   # methods of scorp_pose_ransac
 MESH_RENDER_CULL_BACKFACES = 1   # flag of scorp_mesh_render (include/scorp_gs.h)
+MESH_NORMALS_AREA, MESH_NORMALS_UNIFORM = 0, 1   # weightings of scorp_mesh_vertex_normals
+MESH_SMOOTH_UNIFORM, MESH_SMOOTH_INVERSE_DISTANCE = 0, 1   # weights of scorp_mesh_smooth
 ERR_INVALID, ERR_NO_INLIERS = -1, -4   # return codes the Python layer tells apart (include/scorp_gs.h)
 
 _lib = None
@@ -295,7 +298,11 @@ def lib():
     L.scorp_mesh_render_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
     L.scorp_mesh_render.argtypes = [vp, i64, vp, i64, vp, vp, i32, i32, i32, f64, ctypes.c_uint32, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp,
                                     sz, vp]
-    bv, f32 = ctypes.POINTER(ScorpTsdfBlockViews), ctypes.c_float
+    L.scorp_mesh_face_normals.argtypes = [vp, i64, vp, i64, i32, vp, vp]
+    L.scorp_mesh_vertex_normals.argtypes = [vp, i64, vp, i64, vp, vp, i32, vp, vp]
+    L.scorp_mesh_smooth.argtypes = [vp, i64, vp, vp, vp, ctypes.POINTER(f64), i32, i32, vp, vp, vp]
+    L.scorp_mesh_normal_map.argtypes = [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, vp, vp]
+    bv, f32 =ctypes.POINTER(ScorpTsdfBlockViews), ctypes.c_float
     L.scorp_tsdf_blocks_touch.argtypes = [bv, f32, f32, i32, vp, vp, u64, vp, vp]
     L.scorp_tsdf_blocks_neighbors.argtypes = [vp, i64, vp, vp]
     L.scorp_tsdf_blocks_integrate.argtypes = [bv, f32, f32, vp, vp, i64, vp, vp, vp, vp]

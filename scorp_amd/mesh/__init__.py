@@ -30,6 +30,11 @@ uniform grid of (cell, triangle) pairs, in float64 (csrc/mesh_distance.hip; held
 formulation, tests/mesh_distance_reference.py).  `render_mesh`, `face_visibility`, `cull_unseen_faces` and `depth_difference`
 LOOK at a mesh from cameras: a z-buffer rasterizer with exact integer coverage and one 64-bit atomic minimum per candidate
 (csrc/mesh_render.hip; this project's own rules, held to exact integers and fractions by tests/mesh_render_reference.py).
+`filter_smooth_laplacian`, `filter_smooth_taubin`, `face_normals`, `vertex_normals`, `normal_map` and `normal_difference`
+SMOOTH a mesh and give it normals: `mesh_adjacency` puts each vertex's neighbours and incident faces into CSR form in
+ascending order, and one thread per vertex sums over its slice in float64, so the results are the same bits on every run
+(csrc/mesh_smooth.hip; this project's own rules, in include/scorp_gs.h, held bit for bit to the per-vertex Python loops of
+tests/mesh_smooth_reference.py; uncompared with Open3D's filters of the same names).
 
 CUDA tensors run the HIP kernels; CPU tensors run a torch / numpy form of the same statements.
 
@@ -43,6 +48,8 @@ One module per subsystem, every public name re-exported here:
     decimate.py   simplify_quadric_decimation and its host loop _decimate over _DecimateHip / _DecimateNumpy
     distance.py   point_mesh_distance, sample_points_uniformly, nearest_point_distance, mesh_distance, mesh_cloud_distance
     render.py     render_mesh, face_visibility, cull_unseen_faces, depth_difference
+    smooth.py     mesh_adjacency, face_normals, vertex_normals, filter_smooth_laplacian, filter_smooth_taubin, normal_map,
+                  normal_difference
     extractor.py  focus_point, GaussianExtractor (imports the others; nothing imports it)
 Every stream-taking C-ABI call of the package goes through _C.call.  A test that patches a module global (tsdf.LAUNCH_SAMPLES) patches the
 home module: the names below are copies.
@@ -59,5 +66,7 @@ from .extractor import GaussianExtractor, focus_point
 from .render import (MAX_RENDER_SIDE, MAX_RENDER_VIEWS, WORKSPACE_CAP, DepthDifference, MeshRender, _render_mesh_numpy, cull_unseen_faces,
                      depth_difference, face_visibility, render_mesh)
 from .simplify import CELL_SIDE, CONTRACTIONS, QUADRIC_TRUNCATE, cluster_vertices, simplify_vertex_clustering
+from .smooth import (DISTANCE_EPS, MAX_SMOOTH_STEPS, SMOOTH_WEIGHTS, WEIGHTINGS, MeshAdjacency, NormalDifference, face_normals,
+                     filter_smooth_laplacian, filter_smooth_taubin, mesh_adjacency, normal_difference, normal_map, vertex_normals)
 from .surface import _scan_counts, _surface_nets_numpy, extract_surface
 from .tsdf import LAUNCH_SAMPLES, MAX_RANGE, tsdf_fuse, uncontract

@@ -8,6 +8,7 @@ import torch
 from ._common import Mesh, _check_method, empty_mesh
 from .blocks import extract_surface_blocks, tsdf_blocks_fuse
 from .render import cull_unseen_faces, render_mesh
+from .smooth import normal_difference, normal_map
 from .surface import extract_surface
 from .tsdf import MAX_RANGE, tsdf_fuse, uncontract
 
@@ -42,16 +43,19 @@ class GaussianExtractor:
         self.depthmaps = None    # [V, H, W] on the device
         self.rgbmaps = None      # [V, 3, H, W]
         self.full_proj = None    # [V, 4, 4]
+        self.normalmaps = None   # [V, 3, H, W], world space, alpha-weighted: only after reconstruction(keep_normals=True)
         self.viewpoint_stack = []
 
     @torch.no_grad()
-    def reconstruction(self, viewpoint_stack):
-        """Render every camera and keep its colour and surface-depth maps (the 'render' and 'render_depth' keys)."""
+    def reconstruction(self, viewpoint_stack, keep_normals=False):
+        """Render every camera and keep its colour and surface-depth maps (the 'render' and 'render_depth' keys); with
+        keep_normals also its normal map ('render_normal': world space, alpha-weighted) as self.normalmaps, for
+        normal_difference."""
         self.clean()
         self.viewpoint_stack = list(viewpoint_stack)
         if not self.viewpoint_stack:
             raise ValueError("reconstruction needs at least one camera")
-        depths, rgbs = [], []
+        depths, rgbs, normals = [], [], []
         for cam in self.viewpoint_stack:
             pkg = self.render(cam, self.gaussians)
             rgb, depth = pkg["render"], pkg["render_depth"]
@@ -59,8 +63,12 @@ class GaussianExtractor:
                 raise ValueError(f"all views must share one resolution: {tuple(depth.shape)} after {tuple(depths[0].shape)}")
             rgbs.append(rgb)
             depths.append(depth)
+            if keep_normals:
+                normals.append(pkg["render_normal"])
         self.depthmaps = torch.stack(depths, 0).reshape(len(depths), *depths[0].shape[-2:]).contiguous()
         self.rgbmaps = torch.stack(rgbs, 0).contiguous()
+        if keep_normals:
+            self.normalmaps = torch.stack(normals, 0).contiguous()
         self.full_proj = torch.stack([cam.full_proj_transform.to(self.device) for cam in self.viewpoint_stack], 0).contiguous()
         self.estimate_bounding_sphere()
 
@@ -175,6 +183,17 @@ class GaussianExtractor:
         _, H, W = self.depthmaps.shape
         return cull_unseen_faces(mesh, self.full_proj, H, W, support_depth=None if depth_tolerance is None else self.depthmaps,
                                  support_tolerance=depth_tolerance, min_views=min_views)
+
+    @torch.no_grad()
+    def normal_difference(self, mesh, normals=None):
+        """How the orientation of `mesh` differs from the surfel model's own normals in the kept views
+        (reconstruction(..., keep_normals=True)): normal_difference (smooth.py) of the mesh's normal map - flat, or
+        interpolated from `normals` [Nv, 3] - against self.normalmaps."""
+        self._need_maps()
+        if self.normalmaps is None:
+            raise RuntimeError("call reconstruction(viewpoint_stack, keep_normals=True) first")
+        out = self.render_mesh(mesh, colors=False, barycentric=normals is not None)
+        return normal_difference(normal_map(out, mesh, normals), self.normalmaps)
 
     @torch.no_grad()
     def export_image(self, path):

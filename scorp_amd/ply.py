@@ -106,18 +106,28 @@ def read_gaussian_ply(path, max_sh_degree=None):
                 scaling=scaling, rotation=rotation)
 
 
-def write_mesh_ply(path, mesh):
+def write_mesh_ply(path, mesh, normals=None):
     """A triangle mesh (scorp_amd.mesh.Mesh, or anything with vertices [Nv,3], faces [Nf,3] and colors [Nv,3] in [0,1])
     as binary little-endian PLY: element vertex with float x y z and uchar red green blue, element face with
-    `list uchar int vertex_indices` - the layout Open3D and MeshLab write for a coloured mesh."""
+    `list uchar int vertex_indices` - the layout Open3D and MeshLab write for a coloured mesh.  With `normals` [Nv,3]
+    (say scorp_amd.mesh.vertex_normals) float nx ny nz follow x y z, as those programs write a mesh with vertex normals;
+    with None the file is what it was before there were any."""
     host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
     verts, faces, colors = host(mesh.vertices), host(mesh.faces), host(mesh.colors)
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
-    v = np.empty(len(verts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    axes = ("x", "y", "z")
+    if normals is not None:
+        normals = host(normals)
+        if normals.shape != (len(verts), 3):
+            raise ValueError(f"normals must be [{len(verts)}, 3]; got {tuple(normals.shape)}")
+        axes += ("nx", "ny", "nz")
+    v = np.empty(len(verts), dtype=[(nm, "<f4") for nm in axes] + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     for k, nm in enumerate(("x", "y", "z")):
         v[nm] = verts[:, k]
+    for k, nm in enumerate(axes[3:]):
+        v[nm] = normals[:, k]
     rgb8 = np.rint(np.clip(np.nan_to_num(colors.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
     for k, nm in enumerate(("red", "green", "blue")):
         v[nm] = rgb8[:, k]
@@ -125,7 +135,7 @@ def write_mesh_ply(path, mesh):
     f["n"] = 3
     f["i"] = faces
     header = ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {len(verts)}\n" +
-              "property float x\nproperty float y\nproperty float z\n" +
+              "".join(f"property float {nm}\n" for nm in axes) +
               "property uchar red\nproperty uchar green\nproperty uchar blue\n" +
               f"element face {len(faces)}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as out:
@@ -135,7 +145,8 @@ def write_mesh_ply(path, mesh):
 
 
 def read_mesh_ply(path):
-    """(vertices [Nv,3] float32, faces [Nf,3] int32, colors [Nv,3] uint8) of a file written by write_mesh_ply."""
+    """(vertices [Nv,3] float32, faces [Nf,3] int32, colors [Nv,3] uint8) of a file written by write_mesh_ply; the
+    normals of a file that carries them are passed over (read_ply_vertices returns them as nx, ny, nz)."""
     v = read_ply_vertices(path)
     with open(path, "rb") as fh:
         data = fh.read()
