@@ -107,7 +107,8 @@ __device__ __forceinline__ float splat_exponent(float dx, float dy, float A, flo
 }
 
 // The 64-bit finaliser of MurmurHash3: every bit of the key reaches the low bits, which the open-addressing tables take their
-// slot from (tsdf_blocks.hip, mesh_cluster.hip, mesh_simplify.hip).
+// slot from (tsdf_blocks.hip, which reads a slot before it swaps; table_claim of mesh_common.hpp; the face triples of
+// mesh_simplify.hip).
 __device__ __forceinline__ uint64_t mix64(uint64_t k) {
   k ^= k >> 33;
   k *= 0xFF51AFD7ED558CCDull;
@@ -153,6 +154,22 @@ __device__ __forceinline__ double wave_sum_f64(double v) {   // fixed butterfly:
 #pragma unroll
   for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
   return v;
+}
+
+// ... and of a u64 (mesh_distance.hip)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+// The splitmix64 finaliser, on either side: the edge priorities of mesh_decimate.hip (rule 7), the variates of
+// mesh_sample_kernel
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
 }
 
 // fp16 pairs of the blend backwards' split form (gs3d_backward.hip, gs2d_backward.hip)

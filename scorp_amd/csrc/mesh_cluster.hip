@@ -16,16 +16,14 @@
 //          waves' atomic adds arrive, in their last bits.
 // A root is only ever hooked under a SMALLER index, so the root of a finished component is its smallest triangle: labels
 // and numbering do not depend on the execution order, two calls give the same integers.  Nothing waits on another lane's
-// progress: no locks, no spinning on a value someone else must write.
-#include "common.hpp"
+// progress: no locks, no spinning on a value someone else must write.  The table's claim, the face load and area, the wave
+// loop of stats and the host checks are mesh_common.hpp's.
+#include "mesh_common.hpp"
 
 namespace scorp {
 namespace {
 
 constexpr int kClusterThreads = 256;
-constexpr int64_t kClusterMaxFaces = (int64_t)1 << 28;
-constexpr uint64_t kEmptyKey = ~(uint64_t)0;     // no edge has it: vertex indices are non-negative int32
-constexpr int32_t kEmptyOwner = 0x7FFFFFFF;      // above every triangle index (num_faces <= 2^28)
 
 // parent[] while other lanes hook roots: an agent-scope relaxed atomic load.  A plain load may be served from a line of the
 // CU's vector cache that another CU's compare-and-swap has rewritten since, for as long as the loop runs.  (A stale value
@@ -89,17 +87,11 @@ __global__ void __launch_bounds__(kClusterThreads) cluster_link_kernel(const int
     const uint32_t a = v[e], b = v[e == 2 ? 0 : e + 1];
     const uint64_t key = (uint64_t)(a < b ? a : b) << 32 | (uint64_t)(a < b ? b : a);
     if (key == kEmptyKey) continue;   // (two indices of -1: not a mesh; the empty marker is never claimed as an edge)
-    uint64_t slot = mix64(key) & slot_mask;
-    // linear probing, bounded by the table's size: with num_slots >= 6 num_faces at most half the slots are ever taken
-    for (uint64_t probe = 0; probe <= slot_mask; probe++) {
-      const uint64_t prev = atomicCAS((unsigned long long *)(keys + slot), (unsigned long long)kEmptyKey, (unsigned long long)key);
-      if (prev == kEmptyKey || prev == key) {
-        const int32_t old = atomicMin(owner + slot, t);
-        if (old != kEmptyOwner) unite(parent, t, old);
-        break;
-      }
-      slot = (slot + 1) & slot_mask;
-    }
+    // (with num_slots >= 6 num_faces at most half the slots are ever taken)
+    const int64_t slot = table_claim(keys, slot_mask, key);
+    if (slot == kTableFull) continue;
+    const int32_t old = atomicMin(owner + slot, t);
+    if (old != kEmptyOwner) unite(parent, t, old);
   }
 }
 
@@ -119,20 +111,12 @@ __global__ void __launch_bounds__(kClusterThreads) cluster_roots_kernel(const in
   out_is_root[t] = x == (int32_t)t;
 }
 
-// the sum of v over all 64 lanes, in every lane (a fixed butterfly: the same lanes give the same bits)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-
 __global__ void __launch_bounds__(kClusterThreads) cluster_stats_kernel(const int32_t *__restrict__ tri_idx,
                                                                         const float *__restrict__ verts, int64_t num_vertices,
                                                                         const int32_t *__restrict__ root,
                                                                         const int32_t *__restrict__ root_scan, int32_t faces,
                                                                         int32_t clusters, int32_t *__restrict__ out_cluster,
                                                                         int32_t *out_count, double *out_area) {
-#pragma clang fp contract(off)   // every product and sum of the area rounded on its own, as the float64 restatements round
   const bool with_area = out_area != nullptr;   // (uniform: a kernel argument)
   const int64_t t = (int64_t)blockIdx.x * kClusterThreads + threadIdx.x;
   int32_t c = -1;
@@ -143,43 +127,20 @@ __global__ void __launch_bounds__(kClusterThreads) cluster_stats_kernel(const in
     out_cluster[t] = c;
     if (c < 0 || c >= clusters) c = -1;   // (a scan that does not belong to these roots adds nothing out of bounds)
     if (with_area && c >= 0) {
-      const int64_t i0 = tri_idx[3 * t], i1 = tri_idx[3 * t + 1], i2 = tri_idx[3 * t + 2];
-      if (i0 >= 0 && i0 < num_vertices && i1 >= 0 && i1 < num_vertices && i2 >= 0 && i2 < num_vertices) {
-        const double ax = verts[3 * i0], ay = verts[3 * i0 + 1], az = verts[3 * i0 + 2];
-        const double ux = (double)verts[3 * i1] - ax, uy = (double)verts[3 * i1 + 1] - ay, uz = (double)verts[3 * i1 + 2] - az;
-        const double wx = (double)verts[3 * i2] - ax, wy = (double)verts[3 * i2 + 1] - ay, wz = (double)verts[3 * i2 + 2] - az;
-        const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
-        area = 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
-      }
+      // (num_vertices has no upper bound here: 2^31 lets every non-negative index through)
+      const Face f = load_face(tri_idx, t, (uint32_t)min(num_vertices, (int64_t)1 << 31));
+      if (f.ok) area = 0.5 * norm3(face_cross(verts, f));
     }
   }
-  // Lanes of the wave that hold the same cluster combine, and the first of them issues the atomics: one per distinct
-  // cluster in the wave instead of 64 on one address.  The loop is wave-uniform (every lane runs every round, the lanes past
-  // the last triangle with c = -1), so the ballots and the butterfly see all 64 lanes.
-  const int lane = threadIdx.x & 63;
-  uint64_t todo = __ballot(c >= 0);
-  while (todo) {
-    const int leader = __builtin_ctzll(todo);
-    const int32_t lc = __shfl(c, leader);
-    const bool mine = c == lc;
-    const uint64_t same = __ballot(mine);
+  // one atomic per distinct cluster in the wave (the lanes past the last triangle come with c = -1)
+  wave_combine_equal(c, [&](int32_t lc, bool mine, int count, bool leads) {
     double s = 0.0;
-    if (with_area) s = wave_sum(mine ? area : 0.0);
-    if (lane == leader) {
-      atomicAdd(out_count + lc, (int32_t)__builtin_popcountll(same));
+    if (with_area) s = wave_sum_f64(mine ? area : 0.0);
+    if (leads) {
+      atomicAdd(out_count + lc, count);
       if (with_area) atomicAdd(out_area + lc, s);
     }
-    todo &= ~same;
-  }
-}
-
-inline unsigned cluster_blocks(uint64_t n) { return (unsigned)((n + kClusterThreads - 1) / kClusterThreads); }
-
-int check_faces(int64_t num_faces, const char *what) {
-  if (num_faces < 1 || num_faces > kClusterMaxFaces) {
-    set_error("%s: num_faces must be in [1, 2^28]", what); return SCORP_ERR_INVALID;
-  }
-  return SCORP_OK;
+  });
 }
 
 }  // namespace
@@ -191,19 +152,11 @@ extern "C" int scorp_mesh_cluster_link(const int32_t *faces, int64_t num_faces, 
                                        int32_t *parent, scorp_stream_t stream) {
   if (!faces || !keys || !owner || !parent) { set_error("mesh_cluster_link: NULL argument"); return SCORP_ERR_INVALID; }
   if (int e = check_faces(num_faces, "mesh_cluster_link")) return e;
-  if (num_slots == 0 || (num_slots & (num_slots - 1)) != 0) {
-    set_error("mesh_cluster_link: num_slots must be a power of two"); return SCORP_ERR_INVALID;
-  }
-  if (num_slots < 6 * (uint64_t)num_faces) {
-    set_error("mesh_cluster_link: num_slots must be at least 6 num_faces (%llu < %llu)", (unsigned long long)num_slots,
-              (unsigned long long)(6 * (uint64_t)num_faces));
-    return SCORP_ERR_INVALID;
-  }
-  if (num_slots > ((uint64_t)1 << 32)) { set_error("mesh_cluster_link: num_slots above 2^32"); return SCORP_ERR_INVALID; }
+  if (int e = check_slots(num_slots, (uint64_t)num_faces, 6, 32, "mesh_cluster_link", "num_faces")) return e;
   hipStream_t s = (hipStream_t)stream;
-  cluster_init_kernel<<<cluster_blocks(num_slots), kClusterThreads, 0, s>>>(keys, owner, num_slots, parent, (int32_t)num_faces);
+  cluster_init_kernel<<<blocks_for(num_slots, kClusterThreads), kClusterThreads, 0, s>>>(keys, owner, num_slots, parent, (int32_t)num_faces);
   SCORP_KERNEL_CHECK("cluster_init", 0, s);
-  cluster_link_kernel<<<cluster_blocks((uint64_t)num_faces), kClusterThreads, 0, s>>>(faces, (int32_t)num_faces, keys, owner,
+  cluster_link_kernel<<<blocks_for((uint64_t)num_faces, kClusterThreads), kClusterThreads, 0, s>>>(faces, (int32_t)num_faces, keys, owner,
                                                                                      num_slots - 1, parent);
   SCORP_KERNEL_CHECK("cluster_link", 0, s);
   return SCORP_OK;
@@ -214,7 +167,7 @@ extern "C" int scorp_mesh_cluster_roots(const int32_t *parent, int64_t num_faces
   if (!parent || !out_root || !out_is_root) { set_error("mesh_cluster_roots: NULL argument"); return SCORP_ERR_INVALID; }
   if (int e = check_faces(num_faces, "mesh_cluster_roots")) return e;
   hipStream_t s = (hipStream_t)stream;
-  cluster_roots_kernel<<<cluster_blocks((uint64_t)num_faces), kClusterThreads, 0, s>>>(parent, (int32_t)num_faces, out_root, out_is_root);
+  cluster_roots_kernel<<<blocks_for((uint64_t)num_faces, kClusterThreads), kClusterThreads, 0, s>>>(parent, (int32_t)num_faces, out_root, out_is_root);
   SCORP_KERNEL_CHECK("cluster_roots", 0, s);
   return SCORP_OK;
 }
@@ -232,7 +185,7 @@ extern "C" int scorp_mesh_cluster_stats(const int32_t *faces, const float *verti
   hipStream_t s = (hipStream_t)stream;
   SCORP_HIP_CHECK(hipMemsetAsync(out_count, 0, (size_t)num_clusters * sizeof(int32_t), s));
   if (area) SCORP_HIP_CHECK(hipMemsetAsync(out_area, 0, (size_t)num_clusters * sizeof(double), s));
-  cluster_stats_kernel<<<cluster_blocks((uint64_t)num_faces), kClusterThreads, 0, s>>>(
+  cluster_stats_kernel<<<blocks_for((uint64_t)num_faces, kClusterThreads), kClusterThreads, 0, s>>>(
       faces, area ? vertices : nullptr, area ? num_vertices : 0, root, root_scan, (int32_t)num_faces, (int32_t)num_clusters, out_cluster,
       out_count, area ? out_area : nullptr);
   SCORP_KERNEL_CHECK("cluster_stats", 0, s);

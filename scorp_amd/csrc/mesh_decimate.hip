@@ -17,36 +17,17 @@
 //   apply       the selected edges within the budget: P[lo] = x, Q[lo] += Q[hi], colours, counts, vmap[hi] = lo.
 //   faces       faces mapped through vmap, keep[t] = 0 for a face with two equal indices.
 // All arithmetic is float64 with fp contraction off; no float is summed by atomics, so every bit of the result is a
-// function of the input alone.  No kernel uses LDS or scratch (tests/test_mesh_decimate_resources.py).
-#include "common.hpp"
+// function of the input alone.  No kernel uses LDS or scratch (tests/test_mesh_decimate_resources.py).  The vector type, the
+// face load, the CSR slice and the host checks are mesh_common.hpp's; splitmix64 is common.hpp's.
+#include "mesh_common.hpp"
 
 namespace scorp {
 namespace {
 
 constexpr int kDecimateThreads = 256;
-constexpr int64_t kDecimateMaxVertices = (int64_t)1 << 30;
-constexpr int64_t kDecimateMaxFaces = (int64_t)1 << 28;
 constexpr int32_t kNoRank = 0x7FFFFFFF;
 constexpr int kQ = 10;   // doubles per quadric: A as xx xy xz yy yz zz, b 3, c
 constexpr double kDetFloor = 1e-9, kReach = 4.0;
-
-struct V3 {
-  double x, y, z;
-};
-
-__device__ __forceinline__ V3 load3(const double *__restrict__ p, int64_t v) { return {p[3 * v], p[3 * v + 1], p[3 * v + 2]}; }
-__device__ __forceinline__ V3 sub3(V3 a, V3 b) {
-#pragma clang fp contract(off)
-  return {a.x - b.x, a.y - b.y, a.z - b.z};
-}
-__device__ __forceinline__ V3 cross3(V3 u, V3 w) {
-#pragma clang fp contract(off)
-  return {u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
-__device__ __forceinline__ double dot3(V3 u, V3 w) {
-#pragma clang fp contract(off)
-  return (u.x * w.x + u.y * w.y) + u.z * w.z;
-}
 
 struct Quadric {
   double xx, xy, xz, yy, yz, zz, b0, b1, b2, c;
@@ -65,7 +46,7 @@ __device__ __forceinline__ Quadric add_q(const Quadric &a, const Quadric &b) {
   return {a.xx + b.xx, a.xy + b.xy, a.xz + b.xz, a.yy + b.yy, a.yz + b.yz, a.zz + b.zz, a.b0 + b.b0, a.b1 + b.b1, a.b2 + b.b2, a.c + b.c};
 }
 // q += w (n n^T, d n, d^2)
-__device__ __forceinline__ void add_plane(Quadric &q, V3 n, double d, double w) {
+__device__ __forceinline__ void add_plane(Quadric &q, Vec3d n, double d, double w) {
 #pragma clang fp contract(off)
   const double w0 = w * n.x, w1 = w * n.y, w2 = w * n.z, wd = w * d;
   q.xx += w0 * n.x; q.xy += w0 * n.y; q.xz += w0 * n.z;
@@ -73,7 +54,7 @@ __device__ __forceinline__ void add_plane(Quadric &q, V3 n, double d, double w) 
   q.b0 += wd * n.x; q.b1 += wd * n.y; q.b2 += wd * n.z;
   q.c += wd * d;
 }
-__device__ __forceinline__ double cost_of(const Quadric &q, V3 x) {
+__device__ __forceinline__ double cost_of(const Quadric &q, Vec3d x) {
 #pragma clang fp contract(off)
   const double s2 = (q.xx * (x.x * x.x) + q.yy * (x.y * x.y)) + q.zz * (x.z * x.z);
   const double s1 = (q.xy * (x.x * x.y) + q.xz * (x.x * x.z)) + q.yz * (x.y * x.z);
@@ -83,7 +64,7 @@ __device__ __forceinline__ double cost_of(const Quadric &q, V3 x) {
 }
 
 // rule 4: the point of the collapse and its cost
-__device__ __forceinline__ V3 place(const Quadric &q, V3 plo, V3 phi, double *cost) {
+__device__ __forceinline__ Vec3d place(const Quadric &q, Vec3d plo, Vec3d phi, double *cost) {
 #pragma clang fp contract(off)
   const double c00 = q.yy * q.zz - q.yz * q.yz;
   const double c01 = q.xz * q.yz - q.xy * q.zz;
@@ -93,52 +74,23 @@ __device__ __forceinline__ V3 place(const Quadric &q, V3 plo, V3 phi, double *co
   const double c22 = q.xx * q.yy - q.xy * q.xy;
   const double det = (q.xx * c00 + q.xy * c01) + q.xz * c02;
   const double t = (q.xx + q.yy) + q.zz;
-  const V3 mid = {0.5 * (plo.x + phi.x), 0.5 * (plo.y + phi.y), 0.5 * (plo.z + phi.z)};
+  const Vec3d mid = {0.5 * (plo.x + phi.x), 0.5 * (plo.y + phi.y), 0.5 * (plo.z + phi.z)};
   if (det > kDetFloor * ((t * t) * t)) {
-    const V3 x = {-((c00 * q.b0 + c01 * q.b1) + c02 * q.b2) / det, -((c01 * q.b0 + c11 * q.b1) + c12 * q.b2) / det,
+    const Vec3d x = {-((c00 * q.b0 + c01 * q.b1) + c02 * q.b2) / det, -((c01 * q.b0 + c11 * q.b1) + c12 * q.b2) / det,
                   -((c02 * q.b0 + c12 * q.b1) + c22 * q.b2) / det};
-    const V3 dx = sub3(x, mid), de = sub3(phi, plo);
+    const Vec3d dx = sub3(x, mid), de = sub3(phi, plo);
     if (dot3(dx, dx) <= kReach * dot3(de, de)) {   // (false for NaN)
       *cost = cost_of(q, x);
       return x;
     }
   }
-  V3 best = plo;
+  Vec3d best = plo;
   double best_cost = cost_of(q, plo);
   const double ch = cost_of(q, phi), cm = cost_of(q, mid);
   if (ch < best_cost) { best = phi; best_cost = ch; }
   if (cm < best_cost) { best = mid; best_cost = cm; }
   *cost = best_cost;
   return best;
-}
-
-// the splitmix64 finaliser (rule 7)
-__device__ __forceinline__ uint64_t splitmix(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-struct Face {
-  int32_t a, b, c;
-  bool ok;   // all three in [0, num_vertices)
-};
-__device__ __forceinline__ Face load_face(const int32_t *__restrict__ faces, int64_t t, int32_t num_vertices) {
-  Face f = {faces[3 * t], faces[3 * t + 1], faces[3 * t + 2], false};
-  f.ok = f.a >= 0 && f.a < num_vertices && f.b >= 0 && f.b < num_vertices && f.c >= 0 && f.c < num_vertices;
-  return f;
-}
-
-// the face list of vertex v in the CSR, clamped to the list (a CSR that does not belong to the faces is never read out of bounds)
-struct Range {
-  int64_t beg, end;
-};
-__device__ __forceinline__ Range face_range(const int32_t *__restrict__ vf_start, int64_t v, int64_t entries) {
-  int64_t b = vf_start[v], e = vf_start[v + 1];
-  b = b < 0 ? 0 : (b > entries ? entries : b);
-  e = e < b ? b : (e > entries ? entries : e);
-  return {b, e};
 }
 
 __device__ __forceinline__ bool edge_ends(const int64_t *__restrict__ keys, int64_t e, int32_t num_vertices, int32_t *lo, int32_t *hi) {
@@ -161,17 +113,17 @@ __global__ void __launch_bounds__(kDecimateThreads) decimate_quadrics_kernel(con
   const int64_t v = (int64_t)blockIdx.x * kDecimateThreads + threadIdx.x;
   if (v >= num_vertices) return;
   Quadric q = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  const Range r = face_range(vf_start, v, 3 * (int64_t)num_faces);
+  const Range r = csr_range(vf_start, v, 3 * (int64_t)num_faces);
   for (int64_t i = r.beg; i < r.end; i++) {
     const int32_t t = vf_face[i];
     if (t < 0 || t >= num_faces) continue;
     const Face f = load_face(faces, t, num_vertices);
     if (!f.ok) continue;
-    const V3 p0 = load3(P, f.a), p1 = load3(P, f.b), p2 = load3(P, f.c);
-    const V3 N = cross3(sub3(p1, p0), sub3(p2, p0));
-    const double len = sqrt(dot3(N, N));
+    const Vec3d p0 = load3(P, f.a), p1 = load3(P, f.b), p2 = load3(P, f.c);
+    const Vec3d N = cross3(sub3(p1, p0), sub3(p2, p0));
+    const double len = norm3(N);
     if (!(len > 0.0)) continue;
-    const V3 n = {N.x / len, N.y / len, N.z / len};
+    const Vec3d n = div3(N, len);
     add_plane(q, n, -dot3(n, p0), 0.5 * len);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -179,12 +131,12 @@ __global__ void __launch_bounds__(kDecimateThreads) decimate_quadrics_kernel(con
       if (va != (int32_t)v && vb != (int32_t)v) continue;
       const int32_t e = face_edge[3 * (int64_t)t + k];
       if (e < 0 || e >= num_edges || edge_faces[e] != 1) continue;
-      const V3 pa = k == 0 ? p0 : k == 1 ? p1 : p2, pb = k == 0 ? p1 : k == 1 ? p2 : p0;
-      const V3 ev = sub3(pb, pa);
-      const V3 m = cross3(ev, n);
-      const double ml = sqrt(dot3(m, m));
+      const Vec3d pa = k == 0 ? p0 : k == 1 ? p1 : p2, pb = k == 0 ? p1 : k == 1 ? p2 : p0;
+      const Vec3d ev = sub3(pb, pa);
+      const Vec3d m = cross3(ev, n);
+      const double ml = norm3(m);
       if (!(ml > 0.0)) continue;
-      const V3 mu = {m.x / ml, m.y / ml, m.z / ml};
+      const Vec3d mu = div3(m, ml);
       add_plane(q, mu, -dot3(mu, pa), boundary_weight * dot3(ev, ev));
     }
   }
@@ -220,12 +172,12 @@ __device__ __forceinline__ bool has_neighbour(const int32_t *__restrict__ faces,
 }
 
 // Rule 5 for one face that holds `moved` and not the edge's other end: the normal before and after `moved` goes to x
-__device__ __forceinline__ bool flip_ok(const double *__restrict__ P, Face f, int32_t moved, V3 x) {
+__device__ __forceinline__ bool flip_ok(const double *__restrict__ P, Face f, int32_t moved, Vec3d x) {
 #pragma clang fp contract(off)
-  const V3 p0 = load3(P, f.a), p1 = load3(P, f.b), p2 = load3(P, f.c);
-  const V3 old_n = cross3(sub3(p1, p0), sub3(p2, p0));
-  const V3 q0 = f.a == moved ? x : p0, q1 = f.b == moved ? x : p1, q2 = f.c == moved ? x : p2;
-  const V3 new_n = cross3(sub3(q1, q0), sub3(q2, q0));
+  const Vec3d p0 = load3(P, f.a), p1 = load3(P, f.b), p2 = load3(P, f.c);
+  const Vec3d old_n = cross3(sub3(p1, p0), sub3(p2, p0));
+  const Vec3d q0 = f.a == moved ? x : p0, q1 = f.b == moved ? x : p1, q2 = f.c == moved ? x : p2;
+  const Vec3d new_n = cross3(sub3(q1, q0), sub3(q2, q0));
   return dot3(old_n, new_n) > 0.0;
 }
 
@@ -242,7 +194,7 @@ __global__ void __launch_bounds__(kDecimateThreads) decimate_candidates_kernel(c
   if (e >= num_edges) return;
   const double inf = __builtin_inf();
   double cost = inf;
-  V3 x = {0.0, 0.0, 0.0};
+  Vec3d x = {0.0, 0.0, 0.0};
   int32_t lo, hi;
   bool ok = edge_ends(keys, e, num_vertices, &lo, &hi) && lo != hi;
   const int32_t n = edge_faces[e];
@@ -252,12 +204,12 @@ __global__ void __launch_bounds__(kDecimateThreads) decimate_candidates_kernel(c
     ok = !((fl | fh) & 2) && !(n == 2 && (fl & 1) && (fh & 1));
   }
   if (ok) {
-    const V3 plo = load3(P, lo), phi = load3(P, hi);
+    const Vec3d plo = load3(P, lo), phi = load3(P, hi);
     double c;
     x = place(add_q(load_q(Q, lo), load_q(Q, hi)), plo, phi, &c);
     ok = c <= maximum_error;   // (false for NaN)
     const int64_t entries = 3 * (int64_t)num_faces;
-    const Range rlo = face_range(vf_start, lo, entries), rhi = face_range(vf_start, hi, entries);
+    const Range rlo = csr_range(vf_start, lo, entries), rhi = csr_range(vf_start, hi, entries);
     // the faces of lo: those with hi give the apexes
     int32_t apex0 = -1, apex1 = -1, shared = 0;
     if (ok) {
@@ -311,7 +263,7 @@ __global__ void __launch_bounds__(kDecimateThreads) decimate_hash_kernel(const i
   const int64_t i = (int64_t)blockIdx.x * kDecimateThreads + threadIdx.x;
   if (i >= num_window) return;
   const int32_t e = window[i];
-  out_hash[i] = e >= 0 && e < num_edges ? (int64_t)(splitmix((uint64_t)keys[e] ^ round_mix) >> 1) : 0x7FFFFFFFFFFFFFFFll;
+  out_hash[i] = e >= 0 && e < num_edges ? (int64_t)(splitmix64((uint64_t)keys[e] ^ round_mix) >> 1) : 0x7FFFFFFFFFFFFFFFll;
 }
 
 __global__ void __launch_bounds__(kDecimateThreads) decimate_vmin_init_kernel(int32_t *__restrict__ vmin, int32_t num_vertices) {
@@ -405,17 +357,9 @@ __global__ void __launch_bounds__(kDecimateThreads) decimate_faces_kernel(const 
   out_keep[t] = ok && m[0] != m[1] && m[1] != m[2] && m[2] != m[0];
 }
 
-inline unsigned decimate_blocks(int64_t n) { return (unsigned)((n + kDecimateThreads - 1) / kDecimateThreads); }
-
-int check_range(int64_t n, int64_t most, const char *what, const char *name, const char *bound) {
-  if (n < 1 || n > most) {
-    set_error("%s: %s must be in [1, %s]", what, name, bound); return SCORP_ERR_INVALID;
-  }
-  return SCORP_OK;
-}
 int check_mesh(int64_t num_vertices, int64_t num_faces, const char *what) {
-  if (int e = check_range(num_vertices, kDecimateMaxVertices, what, "num_vertices", "2^30")) return e;
-  return check_range(num_faces, kDecimateMaxFaces, what, "num_faces", "2^28");
+  if (int e = check_vertices(num_vertices, what)) return e;
+  return check_faces(num_faces, what);
 }
 // every face has three edges and every edge at least one face
 int check_edges(int64_t num_edges, int64_t num_faces, const char *what) {
@@ -449,7 +393,7 @@ extern "C" int scorp_mesh_decimate_quadrics(const double *positions, int64_t num
     set_error("mesh_decimate_quadrics: boundary_weight must be finite and not negative"); return SCORP_ERR_INVALID;
   }
   hipStream_t s = (hipStream_t)stream;
-  decimate_quadrics_kernel<<<decimate_blocks(num_vertices), kDecimateThreads, 0, s>>>(
+  decimate_quadrics_kernel<<<blocks_for(num_vertices, kDecimateThreads), kDecimateThreads, 0, s>>>(
       positions, (int32_t)num_vertices, faces, (int32_t)num_faces, face_edge, edge_faces, (int32_t)num_edges, vf_start, vf_face,
       boundary_weight, out_quadrics);
   SCORP_KERNEL_CHECK("decimate_quadrics", 0, s);
@@ -459,11 +403,11 @@ extern "C" int scorp_mesh_decimate_quadrics(const double *positions, int64_t num
 extern "C" int scorp_mesh_decimate_flags(const int64_t *edge_keys, const int32_t *edge_faces, int64_t num_edges, int64_t num_vertices,
                                          int32_t *out_flags, scorp_stream_t stream) {
   if (!edge_keys || !edge_faces || !out_flags) { set_error("mesh_decimate_flags: NULL argument"); return SCORP_ERR_INVALID; }
-  if (int e = check_range(num_vertices, kDecimateMaxVertices, "mesh_decimate_flags", "num_vertices", "2^30")) return e;
-  if (int e = check_edges(num_edges, kDecimateMaxFaces, "mesh_decimate_flags")) return e;
+  if (int e = check_vertices(num_vertices, "mesh_decimate_flags")) return e;
+  if (int e = check_edges(num_edges, kMeshMaxFaces, "mesh_decimate_flags")) return e;
   hipStream_t s = (hipStream_t)stream;
   SCORP_HIP_CHECK(hipMemsetAsync(out_flags, 0, (size_t)num_vertices * sizeof(int32_t), s));
-  decimate_flags_kernel<<<decimate_blocks(num_edges), kDecimateThreads, 0, s>>>(edge_keys, edge_faces, (int32_t)num_edges,
+  decimate_flags_kernel<<<blocks_for(num_edges, kDecimateThreads), kDecimateThreads, 0, s>>>(edge_keys, edge_faces, (int32_t)num_edges,
                                                                                 (int32_t)num_vertices, out_flags);
   SCORP_KERNEL_CHECK("decimate_flags", 0, s);
   return SCORP_OK;
@@ -481,7 +425,7 @@ extern "C" int scorp_mesh_decimate_candidates(const double *positions, const dou
   if (int e = check_edges(num_edges, num_faces, "mesh_decimate_candidates")) return e;
   if (!(maximum_error >= 0.0)) { set_error("mesh_decimate_candidates: maximum_error must not be negative or NaN"); return SCORP_ERR_INVALID; }
   hipStream_t s = (hipStream_t)stream;
-  decimate_candidates_kernel<<<decimate_blocks(num_edges), kDecimateThreads, 0, s>>>(
+  decimate_candidates_kernel<<<blocks_for(num_edges, kDecimateThreads), kDecimateThreads, 0, s>>>(
       positions, quadrics, (int32_t)num_vertices, faces, (int32_t)num_faces, edge_keys, edge_faces, (int32_t)num_edges, vf_start, vf_face,
       flags, maximum_error, out_cost, out_x);
   SCORP_KERNEL_CHECK("decimate_candidates", 0, s);
@@ -491,16 +435,12 @@ extern "C" int scorp_mesh_decimate_candidates(const double *positions, const dou
 extern "C" int scorp_mesh_decimate_hash(const int64_t *edge_keys, int64_t num_edges, const int32_t *window, int64_t num_window,
                                         int64_t round, int64_t *out_hash, scorp_stream_t stream) {
   if (!edge_keys || !window || !out_hash) { set_error("mesh_decimate_hash: NULL argument"); return SCORP_ERR_INVALID; }
-  if (int e = check_edges(num_edges, kDecimateMaxFaces, "mesh_decimate_hash")) return e;
+  if (int e = check_edges(num_edges, kMeshMaxFaces, "mesh_decimate_hash")) return e;
   if (int e = check_window(num_window, num_edges, "mesh_decimate_hash")) return e;
   if (round < 1) { set_error("mesh_decimate_hash: round counts from 1"); return SCORP_ERR_INVALID; }
   hipStream_t s = (hipStream_t)stream;
-  uint64_t m = (uint64_t)round + 0x9E3779B97F4A7C15ull;   // the finaliser on the host (the device's form is splitmix above)
-  m = (m ^ (m >> 30)) * 0xBF58476D1CE4E5B9ull;
-  m = (m ^ (m >> 27)) * 0x94D049BB133111EBull;
-  m ^= m >> 31;
-  decimate_hash_kernel<<<decimate_blocks(num_window), kDecimateThreads, 0, s>>>(edge_keys, (int32_t)num_edges, window, (int32_t)num_window, m,
-                                                                                out_hash);
+  decimate_hash_kernel<<<blocks_for(num_window, kDecimateThreads), kDecimateThreads, 0, s>>>(edge_keys, (int32_t)num_edges, window, (int32_t)num_window,
+                                                                                splitmix64((uint64_t)round), out_hash);
   SCORP_KERNEL_CHECK("decimate_hash", 0, s);
   return SCORP_OK;
 }
@@ -509,19 +449,19 @@ extern "C" int scorp_mesh_decimate_select(const int64_t *edge_keys, int64_t num_
                                           int64_t num_vertices, int32_t *vmin, int32_t *vmin2, uint8_t *out_selected,
                                           scorp_stream_t stream) {
   if (!edge_keys || !ranked || !vmin || !vmin2 || !out_selected) { set_error("mesh_decimate_select: NULL argument"); return SCORP_ERR_INVALID; }
-  if (int e = check_range(num_vertices, kDecimateMaxVertices, "mesh_decimate_select", "num_vertices", "2^30")) return e;
-  if (int e = check_edges(num_edges, kDecimateMaxFaces, "mesh_decimate_select")) return e;
+  if (int e = check_vertices(num_vertices, "mesh_decimate_select")) return e;
+  if (int e = check_edges(num_edges, kMeshMaxFaces, "mesh_decimate_select")) return e;
   if (int e = check_window(num_window, num_edges, "mesh_decimate_select")) return e;
   hipStream_t s = (hipStream_t)stream;
   const int32_t E = (int32_t)num_edges, W = (int32_t)num_window, Nv = (int32_t)num_vertices;
-  decimate_vmin_init_kernel<<<decimate_blocks(num_vertices), kDecimateThreads, 0, s>>>(vmin, Nv);
+  decimate_vmin_init_kernel<<<blocks_for(num_vertices, kDecimateThreads), kDecimateThreads, 0, s>>>(vmin, Nv);
   SCORP_KERNEL_CHECK("decimate_vmin_init", 0, s);
-  decimate_vmin_kernel<<<decimate_blocks(num_window), kDecimateThreads, 0, s>>>(edge_keys, E, ranked, W, Nv, vmin);
+  decimate_vmin_kernel<<<blocks_for(num_window, kDecimateThreads), kDecimateThreads, 0, s>>>(edge_keys, E, ranked, W, Nv, vmin);
   SCORP_KERNEL_CHECK("decimate_vmin", 0, s);
   SCORP_HIP_CHECK(hipMemcpyAsync(vmin2, vmin, (size_t)num_vertices * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  decimate_vmin2_kernel<<<decimate_blocks(num_edges), kDecimateThreads, 0, s>>>(edge_keys, E, Nv, vmin, vmin2);
+  decimate_vmin2_kernel<<<blocks_for(num_edges, kDecimateThreads), kDecimateThreads, 0, s>>>(edge_keys, E, Nv, vmin, vmin2);
   SCORP_KERNEL_CHECK("decimate_vmin2", 0, s);
-  decimate_select_kernel<<<decimate_blocks(num_window), kDecimateThreads, 0, s>>>(edge_keys, E, ranked, W, Nv, vmin2, out_selected);
+  decimate_select_kernel<<<blocks_for(num_window, kDecimateThreads), kDecimateThreads, 0, s>>>(edge_keys, E, ranked, W, Nv, vmin2, out_selected);
   SCORP_KERNEL_CHECK("decimate_select", 0, s);
   return SCORP_OK;
 }
@@ -532,13 +472,13 @@ extern "C" int scorp_mesh_decimate_apply(const int64_t *edge_keys, int64_t num_e
   if (!edge_keys || !ranked || !applied || !x || !positions || !quadrics || !colors || !count || !out_vmap) {
     set_error("mesh_decimate_apply: NULL argument"); return SCORP_ERR_INVALID;
   }
-  if (int e = check_range(num_vertices, kDecimateMaxVertices, "mesh_decimate_apply", "num_vertices", "2^30")) return e;
-  if (int e = check_edges(num_edges, kDecimateMaxFaces, "mesh_decimate_apply")) return e;
+  if (int e = check_vertices(num_vertices, "mesh_decimate_apply")) return e;
+  if (int e = check_edges(num_edges, kMeshMaxFaces, "mesh_decimate_apply")) return e;
   if (int e = check_window(num_window, num_edges, "mesh_decimate_apply")) return e;
   hipStream_t s = (hipStream_t)stream;
-  decimate_identity_kernel<<<decimate_blocks(num_vertices), kDecimateThreads, 0, s>>>(out_vmap, (int32_t)num_vertices);
+  decimate_identity_kernel<<<blocks_for(num_vertices, kDecimateThreads), kDecimateThreads, 0, s>>>(out_vmap, (int32_t)num_vertices);
   SCORP_KERNEL_CHECK("decimate_identity", 0, s);
-  decimate_apply_kernel<<<decimate_blocks(num_window), kDecimateThreads, 0, s>>>(edge_keys, (int32_t)num_edges, ranked, applied,
+  decimate_apply_kernel<<<blocks_for(num_window, kDecimateThreads), kDecimateThreads, 0, s>>>(edge_keys, (int32_t)num_edges, ranked, applied,
                                                                                  (int32_t)num_window, x, (int32_t)num_vertices, positions,
                                                                                  quadrics, colors, count, out_vmap);
   SCORP_KERNEL_CHECK("decimate_apply", 0, s);
@@ -550,7 +490,7 @@ extern "C" int scorp_mesh_decimate_faces(const int32_t *faces, int64_t num_faces
   if (!faces || !vmap || !out_faces || !out_keep) { set_error("mesh_decimate_faces: NULL argument"); return SCORP_ERR_INVALID; }
   if (int e = check_mesh(num_vertices, num_faces, "mesh_decimate_faces")) return e;
   hipStream_t s = (hipStream_t)stream;
-  decimate_faces_kernel<<<decimate_blocks(num_faces), kDecimateThreads, 0, s>>>(faces, (int32_t)num_faces, vmap, (int32_t)num_vertices, out_faces,
+  decimate_faces_kernel<<<blocks_for(num_faces, kDecimateThreads), kDecimateThreads, 0, s>>>(faces, (int32_t)num_faces, vmap, (int32_t)num_vertices, out_faces,
                                                                                 out_keep);
   SCORP_KERNEL_CHECK("decimate_faces", 0, s);
   return SCORP_OK;

@@ -14,15 +14,15 @@
 //           not depend on the fill order of the pairs (atomics), on the sort or on how often a triangle is met.
 //   sample  one thread per sample: stratified area coordinate, binary search in the caller's float64 prefix of the areas.
 //   nearest one thin kernel over icp_build_target + icp_build_source + icp_nearest.
-// No float is summed by atomics.  No kernel spills (tests/test_mesh_distance_resources.py).
+// No float is summed by atomics.  No kernel spills (tests/test_mesh_distance_resources.py).  The vector type, the face load
+// and the host checks are mesh_common.hpp's; wave_sum_u64 and splitmix64 are common.hpp's.
 #include "icp_search.hpp"
+#include "mesh_common.hpp"
 
 namespace scorp {
 namespace {
 
 constexpr int kMeshDistThreads = 256;
-constexpr int64_t kMeshDistMaxVertices = (int64_t)1 << 30;
-constexpr int64_t kMeshDistMaxFaces = (int64_t)1 << 28;
 constexpr int64_t kMeshDistMaxQueries = 0x7FFFFFFF;
 constexpr int kMeshDistMaxGrow = 64;        // 1.25^64 > 1e6 > kMaxGridDim: the grid is one cell long before
 constexpr double kMeshCellPad = 1e-9;       // a triangle's cell range is padded by this many cells on either side
@@ -52,74 +52,50 @@ struct MeshDistLayout {
   }
 };
 
-struct D3 {
-  double x, y, z;
-};
-
-__device__ __forceinline__ D3 sub(D3 a, D3 b) {
-#pragma clang fp contract(off)
-  return {a.x - b.x, a.y - b.y, a.z - b.z};
-}
-__device__ __forceinline__ double dot(D3 u, D3 w) {
-#pragma clang fp contract(off)
-  return (u.x * w.x + u.y * w.y) + u.z * w.z;
-}
-__device__ __forceinline__ D3 cross(D3 u, D3 w) {
-#pragma clang fp contract(off)
-  return {u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
-__device__ __forceinline__ D3 along(D3 a, double t, D3 e) {   // a + t e
-#pragma clang fp contract(off)
-  return {a.x + t * e.x, a.y + t * e.y, a.z + t * e.z};
-}
-__device__ __forceinline__ D3 load_f3(const float *__restrict__ p, int64_t i) {
-  return {(double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2]};
-}
-
 // rule 5: the closest point of the segment from a (e = b - a, ap = p - a); no division when the segment is a point
-__device__ __forceinline__ D3 closest_on_segment(D3 a, D3 e, D3 ap) {
+__device__ __forceinline__ Vec3d closest_on_segment(Vec3d a, Vec3d e, Vec3d ap) {
 #pragma clang fp contract(off)
-  const double t = dot(ap, e), den = dot(e, e);
+  const double t = dot3(ap, e), den = dot3(e, e);
   if (!(t > 0.0)) return a;
-  if (t >= den) return along(a, 1.0, e);
-  return along(a, t / den, e);
+  if (t >= den) return along3(a, 1.0, e);
+  return along3(a, t / den, e);
 }
 
 // rule 4 / 5: the closest point of triangle (A, B, C) to P.  A and P are relative to the grid centre; ab, ac, bc are the
 // edges taken from the float32 inputs themselves (float64 differences of float32 values).
-__device__ __forceinline__ D3 closest_on_triangle(D3 P, D3 A, D3 ab, D3 ac, D3 bc) {
+__device__ __forceinline__ Vec3d closest_on_triangle(Vec3d P, Vec3d A, Vec3d ab, Vec3d ac, Vec3d bc) {
 #pragma clang fp contract(off)
-  const D3 n = cross(ab, ac);
-  const D3 ap = sub(P, A);
+  const Vec3d n = cross3(ab, ac);
+  const Vec3d ap = sub3(P, A);
   if (n.x == 0.0 && n.y == 0.0 && n.z == 0.0) {   // collinear or repeated vertices: the union of the three segments
-    const D3 B = along(A, 1.0, ab), C = along(A, 1.0, ac);
-    const D3 c0 = closest_on_segment(A, ab, ap), c1 = closest_on_segment(B, bc, sub(P, B));
-    const D3 ca = {-ac.x, -ac.y, -ac.z};
-    const D3 c2 = closest_on_segment(C, ca, sub(P, C));
-    const D3 u0 = sub(P, c0), u1 = sub(P, c1), u2 = sub(P, c2);
-    const double e0 = dot(u0, u0), e1 = dot(u1, u1), e2 = dot(u2, u2);
-    D3 best = c0;
+    const Vec3d B = along3(A, 1.0, ab), C = along3(A, 1.0, ac);
+    const Vec3d c0 = closest_on_segment(A, ab, ap), c1 = closest_on_segment(B, bc, sub3(P, B));
+    const Vec3d ca = {-ac.x, -ac.y, -ac.z};
+    const Vec3d c2 = closest_on_segment(C, ca, sub3(P, C));
+    const Vec3d u0 = sub3(P, c0), u1 = sub3(P, c1), u2 = sub3(P, c2);
+    const double e0 = dot3(u0, u0), e1 = dot3(u1, u1), e2 = dot3(u2, u2);
+    Vec3d best = c0;
     double eb = e0;
     if (e1 < eb) { best = c1; eb = e1; }
     if (e2 < eb) { best = c2; }
     return best;
   }
-  const double d1 = dot(ab, ap), d2 = dot(ac, ap);
+  const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
   if (d1 <= 0.0 && d2 <= 0.0) return A;                                   // vertex A
-  const D3 bp = sub(ap, ab);
-  const double d3 = dot(ab, bp), d4 = dot(ac, bp);
-  if (d3 >= 0.0 && d4 <= d3) return along(A, 1.0, ab);                     // vertex B
+  const Vec3d bp = sub3(ap, ab);
+  const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
+  if (d3 >= 0.0 && d4 <= d3) return along3(A, 1.0, ab);                     // vertex B
   const double vc = d1 * d4 - d3 * d2;
-  if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) return along(A, d1 / (d1 - d3), ab);   // edge AB
-  const D3 cp = sub(ap, ac);
-  const double d5 = dot(ab, cp), d6 = dot(ac, cp);
-  if (d6 >= 0.0 && d5 <= d6) return along(A, 1.0, ac);                     // vertex C
+  if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) return along3(A, d1 / (d1 - d3), ab);   // edge AB
+  const Vec3d cp = sub3(ap, ac);
+  const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+  if (d6 >= 0.0 && d5 <= d6) return along3(A, 1.0, ac);                     // vertex C
   const double vb = d5 * d2 - d1 * d6;
-  if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) return along(A, d2 / (d2 - d6), ac);   // edge AC
+  if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) return along3(A, d2 / (d2 - d6), ac);   // edge AC
   const double va = d3 * d6 - d5 * d4;
   if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0)                  // edge BC
-    return along(along(A, 1.0, ab), (d4 - d3) / ((d4 - d3) + (d5 - d6)), bc);
-  const double s = dot(n, ap) / dot(n, n);                                 // the face: P minus its offset along the normal
+    return along3(along3(A, 1.0, ab), (d4 - d3) / ((d4 - d3) + (d5 - d6)), bc);
+  const double s = dot3(n, ap) / dot3(n, n);                                 // the face: P minus its offset along the normal
   return {P.x - s * n.x, P.y - s * n.y, P.z - s * n.z};
 }
 
@@ -130,38 +106,32 @@ struct MeshView {
 };
 
 // (closest point, d^2) of face f to P; false when an index of the face is out of range
-__device__ __forceinline__ bool face_distance(const MeshView &m, const double ct[3], int32_t f, D3 P, D3 &c, double &d2) {
+__device__ __forceinline__ bool face_distance(const MeshView &m, const double ct[3], int32_t f, Vec3d P, Vec3d &c, double &d2) {
 #pragma clang fp contract(off)
-  const int32_t i0 = m.faces[3 * (int64_t)f], i1 = m.faces[3 * (int64_t)f + 1], i2 = m.faces[3 * (int64_t)f + 2];
-  if ((uint32_t)i0 >= (uint32_t)m.Nv || (uint32_t)i1 >= (uint32_t)m.Nv || (uint32_t)i2 >= (uint32_t)m.Nv) return false;
-  const D3 a = load_f3(m.verts, i0), b = load_f3(m.verts, i1), cc = load_f3(m.verts, i2);
-  const D3 A = {a.x - ct[0], a.y - ct[1], a.z - ct[2]};
-  c = closest_on_triangle(P, A, sub(b, a), sub(cc, a), sub(cc, b));
-  const D3 u = sub(P, c);
-  d2 = dot(u, u);
+  const Face t = load_face(m.faces, f, m.Nv);
+  if (!t.ok) return false;
+  const Vec3d a = load3(m.verts, t.a), b = load3(m.verts, t.b), cc = load3(m.verts, t.c);
+  const Vec3d A = {a.x - ct[0], a.y - ct[1], a.z - ct[2]};
+  c = closest_on_triangle(P, A, sub3(b, a), sub3(cc, a), sub3(cc, b));
+  const Vec3d u = sub3(P, c);
+  d2 = dot3(u, u);
   return true;
 }
 
 // rule 2: the cells [lo, hi] per axis the triangle's padded bounding box overlaps; false for a face with a bad index
 __device__ __forceinline__ bool face_cells(const MeshView &m, const IcpGrid *__restrict__ g, int32_t f, int lo[3], int hi[3]) {
-  const int32_t i0 = m.faces[3 * (int64_t)f], i1 = m.faces[3 * (int64_t)f + 1], i2 = m.faces[3 * (int64_t)f + 2];
-  if ((uint32_t)i0 >= (uint32_t)m.Nv || (uint32_t)i1 >= (uint32_t)m.Nv || (uint32_t)i2 >= (uint32_t)m.Nv) return false;
+  const Face t = load_face(m.faces, f, m.Nv);
+  if (!t.ok) return false;
   const double h = (double)g->h;
   for (int d = 0; d < 3; d++) {
-    const double a = (double)m.verts[3 * (int64_t)i0 + d], b = (double)m.verts[3 * (int64_t)i1 + d],
-                 c = (double)m.verts[3 * (int64_t)i2 + d];
+    const double a = (double)m.verts[3 * (int64_t)t.a + d], b = (double)m.verts[3 * (int64_t)t.b + d],
+                 c = (double)m.verts[3 * (int64_t)t.c + d];
     const double mn = fmin(a, fmin(b, c)) - g->ct[d], mx = fmax(a, fmax(b, c)) - g->ct[d];
     const double top = (double)(g->dims[d] - 1);
     lo[d] = (int)fmin(fmax(floor((mn - (double)g->lo[d]) / h - kMeshCellPad), 0.0), top);
     hi[d] = (int)fmin(fmax(floor((mx - (double)g->lo[d]) / h + kMeshCellPad), 0.0), top);
   }
   return true;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
 }
 
 // the number of (cell, triangle) pairs of the current grid
@@ -246,7 +216,7 @@ __global__ void __launch_bounds__(kMeshDistThreads) mesh_query_kernel(MeshView m
     return;
   }
   const double ct[3] = {g->ct[0], g->ct[1], g->ct[2]};
-  const D3 P = {(double)qx - ct[0], (double)qy - ct[1], (double)qz - ct[2]};
+  const Vec3d P = {(double)qx - ct[0], (double)qy - ct[1], (double)qz - ct[2]};
   double best = max_d2;
   {  // the distance to the vertices' bounding box: nothing is closer than that
     const double ex = fmax(fmax(((double)g->tlo[0] - ct[0]) - P.x, P.x - ((double)g->thi[0] - ct[0])), 0.0);
@@ -269,7 +239,7 @@ __global__ void __launch_bounds__(kMeshDistThreads) mesh_query_kernel(MeshView m
     for (uint32_t t = cell_start[ca]; t < e; t++) {
       const uint32_t f = pairs[t];
       if (f >= (uint32_t)m.F) continue;
-      D3 c;
+      Vec3d c;
       double d2;
       if (!face_distance(m, ct, (int32_t)f, P, c, d2)) continue;
       if (d2 < best || (d2 == best && f < bface)) { best = d2; bface = f; }
@@ -280,7 +250,7 @@ __global__ void __launch_bounds__(kMeshDistThreads) mesh_query_kernel(MeshView m
     store_miss(j, out_d2, out_face, out_closest);
     return;
   }
-  D3 c;
+  Vec3d c;
   double d2;
   face_distance(m, ct, (int32_t)bface, P, c, d2);
   out_d2[j] = d2;
@@ -292,16 +262,9 @@ __global__ void __launch_bounds__(kMeshDistThreads) mesh_query_kernel(MeshView m
 
 // ---- the sampler ----
 
-__device__ __forceinline__ uint64_t splitmix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // the variate k of sample i: mix(mix(mix(seed) ^ i) ^ k), its upper 53 bits as a float64 in [0, 1)
 __device__ __forceinline__ double sample_variate(uint64_t mixed_seed, uint64_t i, uint64_t k) {
-  return (double)(splitmix(splitmix(mixed_seed ^ i) ^ k) >> 11) * 0x1p-53;
+  return (double)(splitmix64(splitmix64(mixed_seed ^ i) ^ k) >> 11) * 0x1p-53;
 }
 
 __global__ void __launch_bounds__(kMeshDistThreads) mesh_sample_kernel(MeshView m, const double *__restrict__ prefix, int64_t n,
@@ -324,12 +287,12 @@ __global__ void __launch_bounds__(kMeshDistThreads) mesh_sample_kernel(MeshView 
   out_bary[3 * i] = (float)w0;
   out_bary[3 * i + 1] = (float)w1;
   out_bary[3 * i + 2] = (float)w2;
-  const int32_t i0 = m.faces[3 * (int64_t)lo], i1 = m.faces[3 * (int64_t)lo + 1], i2 = m.faces[3 * (int64_t)lo + 2];
-  if ((uint32_t)i0 >= (uint32_t)m.Nv || (uint32_t)i1 >= (uint32_t)m.Nv || (uint32_t)i2 >= (uint32_t)m.Nv) {
+  const Face f = load_face(m.faces, lo, m.Nv);
+  if (!f.ok) {
     out_points[3 * i] = out_points[3 * i + 1] = out_points[3 * i + 2] = __builtin_nanf("");
     return;
   }
-  const D3 A = load_f3(m.verts, i0), B = load_f3(m.verts, i1), C = load_f3(m.verts, i2);
+  const Vec3d A = load3(m.verts, f.a), B = load3(m.verts, f.b), C = load3(m.verts, f.c);
   out_points[3 * i] = (float)((w0 * A.x + w1 * B.x) + w2 * C.x);
   out_points[3 * i + 1] = (float)((w0 * A.y + w1 * B.y) + w2 * C.y);
   out_points[3 * i + 2] = (float)((w0 * A.z + w1 * B.z) + w2 * C.z);
@@ -365,12 +328,9 @@ __global__ void __launch_bounds__(kMeshDistThreads) nearest_point_kernel(const f
   out_index[j] = id;
 }
 
-int mesh_blocks(int64_t n) { return (int)((n + kMeshDistThreads - 1) / kMeshDistThreads); }
-
 int check_mesh_counts(int64_t Nv, int64_t F, const char *who) {
-  if (Nv < 1 || Nv > kMeshDistMaxVertices) { set_error("%s: num_vertices must be in [1, 2^30]; got %lld", who, (long long)Nv); return SCORP_ERR_INVALID; }
-  if (F < 1 || F > kMeshDistMaxFaces) { set_error("%s: num_faces must be in [1, 2^28]; got %lld", who, (long long)F); return SCORP_ERR_INVALID; }
-  return SCORP_OK;
+  if (int e = check_vertices(Nv, who, true)) return e;
+  return check_faces(F, who, 1, true);
 }
 
 }  // namespace
@@ -379,7 +339,7 @@ int check_mesh_counts(int64_t Nv, int64_t F, const char *who) {
 using namespace scorp;
 
 extern "C" size_t scorp_mesh_distance_workspace_bytes(int64_t num_faces, int64_t num_queries) {
-  if (num_faces > kMeshDistMaxFaces || num_queries > kMeshDistMaxQueries) return 0;
+  if (num_faces > kMeshMaxFaces || num_queries > kMeshDistMaxQueries) return 0;
   return MeshDistLayout(num_faces, num_queries).bytes;
 }
 
@@ -405,7 +365,7 @@ extern "C" int scorp_mesh_distance_build(const float *vertices, int64_t num_vert
   int grow = 0;
   for (;; grow++) {
     SCORP_HIP_CHECK(hipMemsetAsync(total, 0, 8, s));
-    mesh_pair_total_kernel<<<mesh_blocks(num_faces), kMeshDistThreads, 0, s>>>(m, g, total);
+    mesh_pair_total_kernel<<<blocks_for(num_faces, kMeshDistThreads), kMeshDistThreads, 0, s>>>(m, g, total);
     SCORP_KERNEL_CHECK("mesh_pair_total", 0, s);
     SCORP_HIP_CHECK(hipMemcpyAsync(&n_pairs, total, 8, hipMemcpyDeviceToHost, s));
     SCORP_HIP_CHECK(hipStreamSynchronize(s));
@@ -419,12 +379,12 @@ extern "C" int scorp_mesh_distance_build(const float *vertices, int64_t num_vert
   SCORP_HIP_CHECK(hipStreamSynchronize(s));
   if (host.ncells < 1 || host.ncells > cell_cap) { set_error("mesh_distance_build: %d cells above the cap", host.ncells); return SCORP_ERR_INVALID; }
   SCORP_HIP_CHECK(hipMemsetAsync(cell_start, 0, ((size_t)host.ncells + 1) * 4, s));
-  mesh_pair_count_kernel<<<mesh_blocks(num_faces), kMeshDistThreads, 0, s>>>(m, g, cell_start);
+  mesh_pair_count_kernel<<<blocks_for(num_faces, kMeshDistThreads), kMeshDistThreads, 0, s>>>(m, g, cell_start);
   SCORP_KERNEL_CHECK("mesh_pair_count", 0, s);
   icp_scan_kernel<<<1, 1024, 0, s>>>(cell_start, (int64_t)host.ncells + 1);
   SCORP_KERNEL_CHECK("icp_scan", 0, s);
   SCORP_HIP_CHECK(hipMemcpyAsync(cursor, cell_start, (size_t)host.ncells * 4, hipMemcpyDeviceToDevice, s));
-  mesh_pair_fill_kernel<<<mesh_blocks(num_faces), kMeshDistThreads, 0, s>>>(m, g, cursor, pairs, (uint32_t)pair_cap);
+  mesh_pair_fill_kernel<<<blocks_for(num_faces, kMeshDistThreads), kMeshDistThreads, 0, s>>>(m, g, cursor, pairs, (uint32_t)pair_cap);
   SCORP_KERNEL_CHECK("mesh_pair_fill", 0, s);
   if (out_header) {
     out_header[0] = (int64_t)n_pairs; out_header[1] = pair_cap; out_header[2] = host.ncells; out_header[3] = cell_cap;
@@ -438,13 +398,13 @@ extern "C" int scorp_mesh_distance_query(const float *vertices, int64_t num_vert
                                          int32_t *out_face, float *out_closest, void *workspace, size_t workspace_bytes,
                                          scorp_stream_t stream) {
   if (num_queries < 0 || num_queries > kMeshDistMaxQueries) { set_error("mesh_distance_query: num_queries must be in [0, 2^31 - 1]"); return SCORP_ERR_INVALID; }
-  if (num_faces < 0 || num_faces > kMeshDistMaxFaces) { set_error("mesh_distance_query: num_faces must be in [0, 2^28]"); return SCORP_ERR_INVALID; }
+  if (int e = check_faces(num_faces, "mesh_distance_query", 0)) return e;
   if (!(max_distance >= 0.0)) { set_error("mesh_distance_query: max_distance must not be negative or NaN"); return SCORP_ERR_INVALID; }
   if (num_queries == 0) return SCORP_OK;
   if (!queries || !out_squared_distance || !out_face || !out_closest) { set_error("mesh_distance_query: NULL argument"); return SCORP_ERR_INVALID; }
   hipStream_t s = (hipStream_t)stream;
   if (num_faces == 0) {   // an empty mesh: every query misses
-    mesh_miss_kernel<<<mesh_blocks(num_queries), kMeshDistThreads, 0, s>>>(num_queries, out_squared_distance, out_face, out_closest);
+    mesh_miss_kernel<<<blocks_for(num_queries, kMeshDistThreads), kMeshDistThreads, 0, s>>>(num_queries, out_squared_distance, out_face, out_closest);
     SCORP_KERNEL_CHECK("mesh_miss", 0, s);
     return SCORP_OK;
   }
@@ -460,7 +420,7 @@ extern "C" int scorp_mesh_distance_query(const float *vertices, int64_t num_vert
     return e;
   const MeshView m{vertices, faces, (int32_t)num_vertices, (int32_t)num_faces};
   const double max_d2 = max_distance * max_distance;
-  mesh_query_kernel<<<mesh_blocks(num_queries), kMeshDistThreads, 0, s>>>(m, queries, order, num_queries, g, (const uint32_t *)(w + L.cell_start),
+  mesh_query_kernel<<<blocks_for(num_queries, kMeshDistThreads), kMeshDistThreads, 0, s>>>(m, queries, order, num_queries, g, (const uint32_t *)(w + L.cell_start),
                                                                          (const uint32_t *)(w + L.pairs), max_d2, out_squared_distance,
                                                                          out_face, out_closest);
   SCORP_KERNEL_CHECK("mesh_query", 0, s);
@@ -476,12 +436,8 @@ extern "C" int scorp_mesh_sample_points(const float *vertices, int64_t num_verti
   if (num_samples == 0) return SCORP_OK;
   if (!out_points || !out_faces || !out_barycentric) { set_error("mesh_sample_points: NULL argument"); return SCORP_ERR_INVALID; }
   hipStream_t s = (hipStream_t)stream;
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull;   // mix(seed) on the host (the device's form is splitmix above)
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
   const MeshView m{vertices, faces, (int32_t)num_vertices, (int32_t)num_faces};
-  mesh_sample_kernel<<<mesh_blocks(num_samples), kMeshDistThreads, 0, s>>>(m, area_prefix, num_samples, z, out_points, out_faces,
+  mesh_sample_kernel<<<blocks_for(num_samples, kMeshDistThreads), kMeshDistThreads, 0, s>>>(m, area_prefix, num_samples, splitmix64(seed), out_points, out_faces,
                                                                           out_barycentric);
   SCORP_KERNEL_CHECK("mesh_sample", 0, s);
   return SCORP_OK;
@@ -508,7 +464,7 @@ extern "C" int scorp_nearest_point_distance(const float *points, int32_t num_poi
   if (int e = icp_build_source(points, num_points, L, W, s, &order)) return e;
   const double r2 = max_distance * max_distance;
   const float r2f = (float)r2 * (1.0f + 1e-5f);   // the fp32 search keeps slightly more; the pair test is float64
-  nearest_point_kernel<<<mesh_blocks(num_points), kMeshDistThreads, 0, s>>>(W.sp, order, num_points, cloud, W.g, W.cell_start, W.tq, r2, r2f,
+  nearest_point_kernel<<<blocks_for(num_points, kMeshDistThreads), kMeshDistThreads, 0, s>>>(W.sp, order, num_points, cloud, W.g, W.cell_start, W.tq, r2, r2f,
                                                                            out_squared_distance, out_index);
   SCORP_KERNEL_CHECK("nearest_point", 0, s);
   return SCORP_OK;

@@ -16,8 +16,9 @@
 //   count    one thread per face: the view flags summed onto out_visible_views.
 // Coverage is exact integer arithmetic, the depth float64 with contraction off, the z-buffer one 64-bit unsigned atomicMin
 // per candidate (an ordinary vector global atomic): the maps are a function of the inputs alone.  Every loop runs over a box
-// clipped to the image.  No kernel spills or uses LDS (tests/test_mesh_render_resources.py).
-#include "common.hpp"
+// clipped to the image.  No kernel spills or uses LDS (tests/test_mesh_render_resources.py).  The face load, the bounds of a
+// mesh and their checks are mesh_common.hpp's.
+#include "mesh_common.hpp"
 
 namespace scorp {
 namespace {
@@ -25,8 +26,6 @@ namespace {
 constexpr int kMeshRenderThreads = 256;
 constexpr int kMeshRenderSmallBox = 64;        // pixel centres a single thread walks; a larger box goes to the large list
 constexpr int kMeshRenderLargeGroups = 1024;   // workgroups per view that stride over the large list
-constexpr int64_t kMeshRenderMaxVertices = (int64_t)1 << 30;
-constexpr int64_t kMeshRenderMaxFaces = (int64_t)1 << 28;
 constexpr int kMeshRenderMaxViews = 65535;     // the views are the grid's y dimension
 constexpr int kMeshRenderMaxSide = 16384;
 constexpr double kMeshRenderSnapLimit = 536870912.0;   // 2^29, in units of 1/256 pixel (rule 2)
@@ -52,7 +51,7 @@ struct MeshRenderLayout {
 };
 
 bool mesh_render_sizes_ok(int64_t Nv, int64_t F, int64_t V, int64_t H, int64_t W) {
-  return Nv >= 1 && Nv <= kMeshRenderMaxVertices && F >= 0 && F <= kMeshRenderMaxFaces && V >= 1 && V <= kMeshRenderMaxViews && H >= 1 &&
+  return Nv >= 1 && Nv <= kMeshMaxVertices && F >= 0 && F <= kMeshMaxFaces && V >= 1 && V <= kMeshRenderMaxViews && H >= 1 &&
          H <= kMeshRenderMaxSide && W >= 1 && W <= kMeshRenderMaxSide;
 }
 
@@ -79,10 +78,11 @@ __device__ __forceinline__ bool owns(int64_t e, bool tl) { return e > 0 || (e ==
 // rules 2 (the drops) and 3; false: the face is dropped for this view
 __device__ __forceinline__ bool tri_setup(const int32_t *__restrict__ faces, int32_t Nv, const ProjVert *__restrict__ pv, int64_t f,
                                           uint32_t flags, Tri &t) {
-  t.i0 = faces[3 * f];
-  t.i1 = faces[3 * f + 1];
-  t.i2 = faces[3 * f + 2];
-  if ((uint32_t)t.i0 >= (uint32_t)Nv || (uint32_t)t.i1 >= (uint32_t)Nv || (uint32_t)t.i2 >= (uint32_t)Nv) return false;
+  const Face face = load_face(faces, f, Nv);
+  t.i0 = face.a;
+  t.i1 = face.b;
+  t.i2 = face.c;
+  if (!face.ok) return false;
   const ProjVert a = pv[t.i0], b = pv[t.i1], c = pv[t.i2];
   if (!(a.inv_w > 0.0) || !(b.inv_w > 0.0) || !(c.inv_w > 0.0)) return false;
   t.x0 = a.X; t.y0 = a.Y; t.iw0 = a.inv_w;
@@ -273,8 +273,6 @@ __global__ void __launch_bounds__(kMeshRenderThreads) mesh_render_count_kernel(c
   out_visible_views[f] += n;
 }
 
-unsigned mesh_render_blocks(size_t n) { return (unsigned)((n + kMeshRenderThreads - 1) / kMeshRenderThreads); }
-
 }  // namespace
 }  // namespace scorp
 
@@ -291,8 +289,8 @@ extern "C" int scorp_mesh_render(const float *vertices, int64_t num_vertices, co
                                  const float *support_depth, float support_tolerance, float *out_depth, int32_t *out_face,
                                  float *out_barycentric, float *out_color, int32_t *out_visible_views, void *workspace,
                                  size_t workspace_bytes, scorp_stream_t stream) {
-  if (num_vertices < 1 || num_vertices > kMeshRenderMaxVertices) { set_error("mesh_render: num_vertices must be in [1, 2^30]; got %lld", (long long)num_vertices); return SCORP_ERR_INVALID; }
-  if (num_faces < 0 || num_faces > kMeshRenderMaxFaces) { set_error("mesh_render: num_faces must be in [0, 2^28]; got %lld", (long long)num_faces); return SCORP_ERR_INVALID; }
+  if (int e = check_vertices(num_vertices, "mesh_render", true)) return e;
+  if (int e = check_faces(num_faces, "mesh_render", 0, true)) return e;
   if (num_views < 1 || num_views > kMeshRenderMaxViews) { set_error("mesh_render: num_views must be in [1, 65535]; got %d", num_views); return SCORP_ERR_INVALID; }
   if (height < 1 || height > kMeshRenderMaxSide || width < 1 || width > kMeshRenderMaxSide) { set_error("mesh_render: height and width must be in [1, 16384]; got %d x %d", height, width); return SCORP_ERR_INVALID; }
   if (!(near > 0.0) || !(near < __builtin_inf())) { set_error("mesh_render: near must be positive and finite"); return SCORP_ERR_INVALID; }
@@ -317,10 +315,10 @@ extern "C" int scorp_mesh_render(const float *vertices, int64_t num_vertices, co
   SCORP_HIP_CHECK(hipMemsetAsync(count, 0, (size_t)num_views * 4, s));
   if (num_faces > 0) {
     if (view_flags) SCORP_HIP_CHECK(hipMemsetAsync(view_flags, 0, (size_t)num_views * (size_t)num_faces, s));
-    mesh_render_project_kernel<<<dim3(mesh_render_blocks((size_t)num_vertices), (unsigned)num_views), kMeshRenderThreads, 0, s>>>(
+    mesh_render_project_kernel<<<dim3(blocks_for((size_t)num_vertices, kMeshRenderThreads), (unsigned)num_views), kMeshRenderThreads, 0, s>>>(
         vertices, num_vertices, full_proj, height, width, near, proj);
     SCORP_KERNEL_CHECK("mesh_render_project", 0, s);
-    mesh_render_small_kernel<<<dim3(mesh_render_blocks((size_t)num_faces), (unsigned)num_views), kMeshRenderThreads, 0, s>>>(
+    mesh_render_small_kernel<<<dim3(blocks_for((size_t)num_faces, kMeshRenderThreads), (unsigned)num_views), kMeshRenderThreads, 0, s>>>(
         faces, num_faces, Nv, proj, height, width, flags, keys, list, count);
     SCORP_KERNEL_CHECK("mesh_render_small", 0, s);
     const unsigned groups = (unsigned)(num_faces < kMeshRenderLargeGroups ? num_faces : kMeshRenderLargeGroups);
@@ -328,12 +326,12 @@ extern "C" int scorp_mesh_render(const float *vertices, int64_t num_vertices, co
                                                                                              flags, keys, list, count);
     SCORP_KERNEL_CHECK("mesh_render_large", 0, s);
   }
-  mesh_render_resolve_kernel<<<dim3(mesh_render_blocks(hw), (unsigned)num_views), kMeshRenderThreads, 0, s>>>(
+  mesh_render_resolve_kernel<<<dim3(blocks_for(hw, kMeshRenderThreads), (unsigned)num_views), kMeshRenderThreads, 0, s>>>(
       faces, num_faces, Nv, proj, colors, height, width, flags, keys, support_depth, support_tolerance, out_depth, out_face, out_barycentric,
       out_color, view_flags);
   SCORP_KERNEL_CHECK("mesh_render_resolve", 0, s);
   if (view_flags) {
-    mesh_render_count_kernel<<<mesh_render_blocks((size_t)num_faces), kMeshRenderThreads, 0, s>>>(view_flags, num_faces, num_views,
+    mesh_render_count_kernel<<<blocks_for((size_t)num_faces, kMeshRenderThreads), kMeshRenderThreads, 0, s>>>(view_flags, num_faces, num_views,
                                                                                                  out_visible_views);
     SCORP_KERNEL_CHECK("mesh_render_count", 0, s);
   }

@@ -16,19 +16,15 @@
 //   faces       remap, rotate the smallest cell first, and a second open-addressing table of FACE INDICES whose key is the
 //               ordered triple of the face stored in the slot: equal triples meet in one slot and atomicMin leaves the
 //               smallest face index there, so keep[t] does not depend on the execution order either.
-// Nothing waits on another lane's progress: no locks, no spinning on a value someone else must write.
-#include "common.hpp"
+// Nothing waits on another lane's progress: no locks, no spinning on a value someone else must write.  The cell table's
+// claim, the face load and cross product, the wave loop of the quadrics and the host checks are mesh_common.hpp's.
+#include "mesh_common.hpp"
 #include "svd3.hpp"
 
 namespace scorp {
 namespace {
 
 constexpr int kSimplifyThreads = 256;
-constexpr int64_t kSimplifyMaxVertices = (int64_t)1 << 30;
-constexpr int64_t kSimplifyMaxFaces = (int64_t)1 << 28;
-constexpr uint64_t kMaxSlots = (uint64_t)1 << 31;
-constexpr uint64_t kEmptyCell = ~(uint64_t)0;   // no cell has it: a key has 63 bits
-constexpr int32_t kEmptyOwner = 0x7FFFFFFF;     // above every vertex and face index
 constexpr int32_t kCellSide = 1 << 21;          // cell indices per axis
 constexpr int kAcc = 16;                        // doubles per cell: position 3, colour 3, count, A 6 (xx xy xz yy yz zz), b 3
 
@@ -69,7 +65,7 @@ __global__ void __launch_bounds__(kSimplifyThreads) simplify_init_kernel(uint64_
                                                                          uint64_t slots, int32_t *__restrict__ overflow) {
   const uint64_t i = (uint64_t)blockIdx.x * kSimplifyThreads + threadIdx.x;
   if (i < slots) {
-    keys[i] = kEmptyCell;
+    keys[i] = kEmptyKey;
     owner[i] = kEmptyOwner;
   }
   if (i == 0) *overflow = 0;
@@ -90,16 +86,11 @@ __global__ void __launch_bounds__(kSimplifyThreads) simplify_cells_kernel(const 
     atomicOr(overflow, 1);
   } else {
     const uint64_t key = (uint64_t)c[0] << 42 | (uint64_t)c[1] << 21 | (uint64_t)c[2];
-    uint64_t slot = mix64(key) & slot_mask;
-    // linear probing, bounded by the table's size: with num_slots >= 2 num_vertices at most half the slots are ever taken
-    for (uint64_t probe = 0; probe <= slot_mask; probe++) {
-      const uint64_t prev = atomicCAS((unsigned long long *)(keys + slot), (unsigned long long)kEmptyCell, (unsigned long long)key);
-      if (prev == kEmptyCell || prev == key) {
-        atomicMin(owner + slot, v);
-        found = (int32_t)slot;
-        break;
-      }
-      slot = (slot + 1) & slot_mask;
+    // (with num_slots >= 2 num_vertices at most half the slots are ever taken)
+    const int64_t slot = table_claim(keys, slot_mask, key);
+    if (slot != kTableFull) {
+      atomicMin(owner + slot, v);
+      found = (int32_t)slot;
     }
   }
   out_slot[v64] = found;
@@ -156,13 +147,6 @@ __global__ void __launch_bounds__(kSimplifyThreads) simplify_vertex_sums_kernel(
   unsafeAtomicAdd(a + 6, 1.0);
 }
 
-// the sum of v over all 64 lanes, in every lane (a fixed butterfly: the same lanes give the same bits)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-
 // Every triangle of non-zero area adds a n n^T and a d n to the cell of each corner.  Surface extraction emits triangles in
 // lattice order, so the lanes of a wave share few cells: the lanes that hold the same cell combine first and the wave issues
 // one atomic per distinct cell, corner and term instead of one per lane (measured against the per-lane form on the meshes of
@@ -174,30 +158,25 @@ __global__ void __launch_bounds__(kSimplifyThreads) simplify_quadrics_kernel(con
                                                                              int32_t cells, double *acc) {
 #pragma clang fp contract(off)   // every product and sum rounded on its own, as the float64 restatements round
   const int64_t t = (int64_t)blockIdx.x * kSimplifyThreads + threadIdx.x;
-  bool live = t < faces;
-  int32_t idx[3] = {0, 0, 0};
-  if (live) {
-    for (int k = 0; k < 3; k++) idx[k] = tri_idx[3 * t + k];
-    for (int k = 0; k < 3; k++) live = live && idx[k] >= 0 && idx[k] < num_vertices;
-  }
+  Face f = {0, 0, 0, false};
+  if (t < faces) f = load_face(tri_idx, t, num_vertices);
+  bool live = f.ok;
+  const int32_t idx[3] = {f.a, f.b, f.c};
   float p[3][3] = {};
   double n[3] = {0.0, 0.0, 0.0}, area = 0.0;
   if (live) {
     for (int k = 0; k < 3; k++)
       for (int d = 0; d < 3; d++) p[k][d] = verts[3 * (int64_t)idx[k] + d];
-    const double ux = (double)p[1][0] - (double)p[0][0], uy = (double)p[1][1] - (double)p[0][1], uz = (double)p[1][2] - (double)p[0][2];
-    const double wx = (double)p[2][0] - (double)p[0][0], wy = (double)p[2][1] - (double)p[0][1], wz = (double)p[2][2] - (double)p[0][2];
-    const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
-    const double len = sqrt((cx * cx + cy * cy) + cz * cz);
+    const Vec3d N = face_cross(verts, f);
+    const double len = norm3(N);
     live = len > 0.0;
     if (live) {
       area = 0.5 * len;
-      n[0] = cx / len; n[1] = cy / len; n[2] = cz / len;
+      n[0] = N.x / len; n[1] = N.y / len; n[2] = N.z / len;
     }
   }
   const double an[3] = {area * n[0], area * n[1], area * n[2]};
   const Grid g = load_grid(min_bound, h);
-  const int lane = threadIdx.x & 63;
   for (int k = 0; k < 3; k++) {
     int32_t c = -1;
     double term[9] = {};
@@ -212,22 +191,15 @@ __global__ void __launch_bounds__(kSimplifyThreads) simplify_quadrics_kernel(con
       term[3] = an[1] * n[1]; term[4] = an[1] * n[2]; term[5] = an[2] * n[2];
       term[6] = ad * n[0]; term[7] = ad * n[1]; term[8] = ad * n[2];
     }
-    // wave-uniform: every lane runs every round, the lanes without a contribution with c = -1
-    uint64_t todo = __ballot(c >= 0);
-    while (todo) {
-      const int leader = __builtin_ctzll(todo);
-      const int32_t lc = __shfl(c, leader);
-      const bool mine = c == lc;
-      const uint64_t same = __ballot(mine);
-      const bool alone = __builtin_popcountll(same) == 1;   // (uniform)
+    wave_combine_equal(c, [&](int32_t lc, bool mine, int count, bool leads) {
+      const bool alone = count == 1;   // (uniform: the butterfly is skipped for a cell only one lane holds)
       double *a = acc + (int64_t)lc * kAcc + 7;
 #pragma unroll
       for (int j = 0; j < 9; j++) {
-        const double s = alone ? term[j] : wave_sum(mine ? term[j] : 0.0);
-        if (lane == leader) unsafeAtomicAdd(a + j, s);
+        const double s = alone ? term[j] : wave_sum_f64(mine ? term[j] : 0.0);
+        if (leads) unsafeAtomicAdd(a + j, s);
       }
-      todo &= ~same;
-    }
+    });
   }
 }
 
@@ -360,30 +332,6 @@ __global__ void __launch_bounds__(kSimplifyThreads) simplify_faces_keep_kernel(c
   }
 }
 
-inline unsigned simplify_blocks(uint64_t n) { return (unsigned)((n + kSimplifyThreads - 1) / kSimplifyThreads); }
-
-int check_count(int64_t n, int64_t most, const char *what, const char *name, const char *bound) {
-  if (n < 1 || n > most) {
-    set_error("%s: %s must be in [1, %s]", what, name, bound); return SCORP_ERR_INVALID;
-  }
-  return SCORP_OK;
-}
-
-int check_vertices(int64_t n, const char *what) { return check_count(n, kSimplifyMaxVertices, what, "num_vertices", "2^30"); }
-
-int check_slots(uint64_t num_slots, uint64_t entries, const char *what, const char *of) {
-  if (num_slots == 0 || (num_slots & (num_slots - 1)) != 0) {
-    set_error("%s: num_slots must be a power of two", what); return SCORP_ERR_INVALID;
-  }
-  if (num_slots < 2 * entries) {
-    set_error("%s: num_slots must be at least 2 %s (%llu < %llu)", what, of, (unsigned long long)num_slots,
-              (unsigned long long)(2 * entries));
-    return SCORP_ERR_INVALID;
-  }
-  if (num_slots > kMaxSlots) { set_error("%s: num_slots above 2^31", what); return SCORP_ERR_INVALID; }
-  return SCORP_OK;
-}
-
 int check_voxel(double h, const char *what) {
   if (!(h > 0.0) || !std::isfinite(h)) { set_error("%s: voxel_size must be positive and finite", what); return SCORP_ERR_INVALID; }
   return SCORP_OK;
@@ -402,11 +350,11 @@ extern "C" int scorp_mesh_simplify_cells(const float *vertices, int64_t num_vert
   }
   if (int e = check_vertices(num_vertices, "mesh_simplify_cells")) return e;
   if (int e = check_voxel(voxel_size, "mesh_simplify_cells")) return e;
-  if (int e = check_slots(num_slots, (uint64_t)num_vertices, "mesh_simplify_cells", "num_vertices")) return e;
+  if (int e = check_slots(num_slots, (uint64_t)num_vertices, 2, 31, "mesh_simplify_cells", "num_vertices")) return e;
   hipStream_t s = (hipStream_t)stream;
-  simplify_init_kernel<<<simplify_blocks(num_slots), kSimplifyThreads, 0, s>>>(keys, owner, num_slots, out_overflow);
+  simplify_init_kernel<<<blocks_for(num_slots, kSimplifyThreads), kSimplifyThreads, 0, s>>>(keys, owner, num_slots, out_overflow);
   SCORP_KERNEL_CHECK("simplify_init", 0, s);
-  simplify_cells_kernel<<<simplify_blocks((uint64_t)num_vertices), kSimplifyThreads, 0, s>>>(vertices, (int32_t)num_vertices, min_bound, voxel_size,
+  simplify_cells_kernel<<<blocks_for((uint64_t)num_vertices, kSimplifyThreads), kSimplifyThreads, 0, s>>>(vertices, (int32_t)num_vertices, min_bound, voxel_size,
                                                                                            keys, owner, num_slots - 1, out_slot, out_overflow);
   SCORP_KERNEL_CHECK("simplify_cells", 0, s);
   return SCORP_OK;
@@ -416,9 +364,9 @@ extern "C" int scorp_mesh_simplify_roots(const int32_t *owner, uint64_t num_slot
                                          int32_t *out_rep, uint8_t *out_is_root, scorp_stream_t stream) {
   if (!owner || !slot || !out_rep || !out_is_root) { set_error("mesh_simplify_roots: NULL argument"); return SCORP_ERR_INVALID; }
   if (int e = check_vertices(num_vertices, "mesh_simplify_roots")) return e;
-  if (int e = check_slots(num_slots, (uint64_t)num_vertices, "mesh_simplify_roots", "num_vertices")) return e;
+  if (int e = check_slots(num_slots, (uint64_t)num_vertices, 2, 31, "mesh_simplify_roots", "num_vertices")) return e;
   hipStream_t s = (hipStream_t)stream;
-  simplify_roots_kernel<<<simplify_blocks((uint64_t)num_vertices), kSimplifyThreads, 0, s>>>(owner, num_slots, slot, (int32_t)num_vertices, out_rep,
+  simplify_roots_kernel<<<blocks_for((uint64_t)num_vertices, kSimplifyThreads), kSimplifyThreads, 0, s>>>(owner, num_slots, slot, (int32_t)num_vertices, out_rep,
                                                                                            out_is_root);
   SCORP_KERNEL_CHECK("simplify_roots", 0, s);
   return SCORP_OK;
@@ -437,14 +385,14 @@ extern "C" int scorp_mesh_simplify_accumulate(const float *vertices, const float
     set_error("mesh_simplify_accumulate: num_cells must be in [1, num_vertices]"); return SCORP_ERR_INVALID;
   }
   if (quadric)
-    if (int e = check_count(num_faces, kSimplifyMaxFaces, "mesh_simplify_accumulate", "num_faces", "2^28")) return e;
+    if (int e = check_faces(num_faces, "mesh_simplify_accumulate")) return e;
   hipStream_t s = (hipStream_t)stream;
   SCORP_HIP_CHECK(hipMemsetAsync(out_acc, 0, (size_t)num_cells * kAcc * sizeof(double), s));
-  simplify_vertex_sums_kernel<<<simplify_blocks((uint64_t)num_vertices), kSimplifyThreads, 0, s>>>(
+  simplify_vertex_sums_kernel<<<blocks_for((uint64_t)num_vertices, kSimplifyThreads), kSimplifyThreads, 0, s>>>(
       vertices, colors, (int32_t)num_vertices, min_bound, voxel_size, rep, rep_scan, (int32_t)num_cells, out_vertex_cell, out_cell_ijk, out_acc);
   SCORP_KERNEL_CHECK("simplify_vertex_sums", 0, s);
   if (quadric) {
-    simplify_quadrics_kernel<<<simplify_blocks((uint64_t)num_faces), kSimplifyThreads, 0, s>>>(
+    simplify_quadrics_kernel<<<blocks_for((uint64_t)num_faces, kSimplifyThreads), kSimplifyThreads, 0, s>>>(
         faces, (int32_t)num_faces, vertices, (int32_t)num_vertices, min_bound, voxel_size, rep, rep_scan, (int32_t)num_cells, out_acc);
     SCORP_KERNEL_CHECK("simplify_quadrics", 0, s);
   }
@@ -454,10 +402,10 @@ extern "C" int scorp_mesh_simplify_accumulate(const float *vertices, const float
 extern "C" int scorp_mesh_simplify_place(const double *acc, const int32_t *cell_ijk, int64_t num_cells, const float *min_bound,
                                          double voxel_size, int32_t quadric, float *out_vertices, float *out_colors, scorp_stream_t stream) {
   if (!acc || !cell_ijk || !min_bound || !out_vertices || !out_colors) { set_error("mesh_simplify_place: NULL argument"); return SCORP_ERR_INVALID; }
-  if (int e = check_count(num_cells, kSimplifyMaxVertices, "mesh_simplify_place", "num_cells", "2^30")) return e;
+  if (int e = check_count(num_cells, 1, kMeshMaxVertices, "mesh_simplify_place", "num_cells", "2^30")) return e;
   if (int e = check_voxel(voxel_size, "mesh_simplify_place")) return e;
   hipStream_t s = (hipStream_t)stream;
-  simplify_place_kernel<<<simplify_blocks((uint64_t)num_cells), kSimplifyThreads, 0, s>>>(acc, cell_ijk, (int32_t)num_cells, min_bound, voxel_size,
+  simplify_place_kernel<<<blocks_for((uint64_t)num_cells, kSimplifyThreads), kSimplifyThreads, 0, s>>>(acc, cell_ijk, (int32_t)num_cells, min_bound, voxel_size,
                                                                                         quadric ? 1 : 0, out_vertices, out_colors);
   SCORP_KERNEL_CHECK("simplify_place", 0, s);
   return SCORP_OK;
@@ -466,17 +414,17 @@ extern "C" int scorp_mesh_simplify_place(const double *acc, const int32_t *cell_
 extern "C" int scorp_mesh_simplify_faces(const int32_t *faces, int64_t num_faces, const int32_t *vertex_cell, int64_t num_vertices,
                                          int32_t *table, uint64_t num_slots, int32_t *out_faces, uint8_t *out_keep, scorp_stream_t stream) {
   if (!faces || !vertex_cell || !table || !out_faces || !out_keep) { set_error("mesh_simplify_faces: NULL argument"); return SCORP_ERR_INVALID; }
-  if (int e = check_count(num_faces, kSimplifyMaxFaces, "mesh_simplify_faces", "num_faces", "2^28")) return e;
+  if (int e = check_faces(num_faces, "mesh_simplify_faces")) return e;
   if (int e = check_vertices(num_vertices, "mesh_simplify_faces")) return e;
-  if (int e = check_slots(num_slots, (uint64_t)num_faces, "mesh_simplify_faces", "num_faces")) return e;
+  if (int e = check_slots(num_slots, (uint64_t)num_faces, 2, 31, "mesh_simplify_faces", "num_faces")) return e;
   hipStream_t s = (hipStream_t)stream;
   const uint64_t n = num_slots > (uint64_t)num_faces ? num_slots : (uint64_t)num_faces;
-  simplify_faces_remap_kernel<<<simplify_blocks(n), kSimplifyThreads, 0, s>>>(faces, (int32_t)num_faces, vertex_cell, (int32_t)num_vertices, table,
+  simplify_faces_remap_kernel<<<blocks_for(n, kSimplifyThreads), kSimplifyThreads, 0, s>>>(faces, (int32_t)num_faces, vertex_cell, (int32_t)num_vertices, table,
                                                                              num_slots, out_faces, out_keep);
   SCORP_KERNEL_CHECK("simplify_faces_remap", 0, s);
-  simplify_faces_insert_kernel<<<simplify_blocks((uint64_t)num_faces), kSimplifyThreads, 0, s>>>(out_faces, (int32_t)num_faces, table, num_slots - 1);
+  simplify_faces_insert_kernel<<<blocks_for((uint64_t)num_faces, kSimplifyThreads), kSimplifyThreads, 0, s>>>(out_faces, (int32_t)num_faces, table, num_slots - 1);
   SCORP_KERNEL_CHECK("simplify_faces_insert", 0, s);
-  simplify_faces_keep_kernel<<<simplify_blocks((uint64_t)num_faces), kSimplifyThreads, 0, s>>>(out_faces, (int32_t)num_faces, table, num_slots - 1,
+  simplify_faces_keep_kernel<<<blocks_for((uint64_t)num_faces, kSimplifyThreads), kSimplifyThreads, 0, s>>>(out_faces, (int32_t)num_faces, table, num_slots - 1,
                                                                                              out_keep);
   SCORP_KERNEL_CHECK("simplify_faces_keep", 0, s);
   return SCORP_OK;

@@ -40,6 +40,7 @@ CUDA tensors run the HIP kernels; CPU tensors run a torch / numpy form of the sa
 
 One module per subsystem, every public name re-exported here:
     _common.py    Mesh, empty_mesh, drop_unreferenced, check_mesh (the simplifiers' argument checks), METHODS
+    _topology.py  edge_keys, vertex_face_csr, table_slots, proper_faces and the float64 numpy cross / dot / unit of the CPU forms
     tsdf.py       tsdf_fuse over samples or a lattice, uncontract
     surface.py    extract_surface: dense surface nets and marching cubes
     blocks.py     BlockVolume, tsdf_blocks_fuse, block_neighbors, extract_surface_blocks

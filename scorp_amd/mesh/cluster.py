@@ -5,28 +5,17 @@ import torch
 
 from .. import _C
 from ._common import MAX_CLUSTER_FACES, Mesh, drop_unreferenced, empty_mesh
+from ._topology import _dot3, _face_cross, edge_keys, proper_faces, table_slots
 
 MIN_CLUSTER_TRIANGLES = 50    # mesh_utils.py:36: no cluster below it is ever kept
 
 
-def _triangle_areas_numpy(f, v):
-    """0.5 |(v1 - v0) x (v2 - v0)| in float64 from the float32 vertices, every product and sum rounded on its own."""
-    v = np.asarray(v, np.float32).astype(np.float64)
-    u, w = v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
-    nx = u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1]
-    ny = u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2]
-    nz = u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
-    return 0.5 * np.sqrt((nx * nx + ny * ny) + nz * nz)
-
-
 def _cluster_numpy(f, verts):
-    """The rules of include/scorp_gs.h (connected triangles) in numpy: the 3F edge keys grouped by np.unique, then every
+    """The rules of include/scorp_gs.h (connected triangles) in numpy: the 3F edge_keys grouped by np.unique, then every
     triangle takes the smallest label on its edges and the labels are pointer-jumped, until nothing changes.  A label is
     always a triangle of the same component, so the fixed point is the component's smallest triangle index."""
     F = f.shape[0]
-    f = f.astype(np.int64)
-    a, b = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)                     # edge e of triangle t at 3 t + e
-    _, edge = np.unique(np.minimum(a, b) << 32 | np.maximum(a, b), return_inverse=True)
+    _, edge = np.unique(edge_keys(f).reshape(-1), return_inverse=True)   # edge e of triangle t at 3 t + e
     edge = edge.reshape(-1)
     order = np.argsort(edge, kind="stable")
     tri = order // 3                                                        # the triangles edge by edge
@@ -47,7 +36,10 @@ def _cluster_numpy(f, verts):
     cluster = (np.cumsum(is_root) - 1)[label].astype(np.int32)
     C = int(is_root.sum())
     counts = np.bincount(cluster, minlength=C).astype(np.int32)
-    area = np.bincount(cluster, weights=_triangle_areas_numpy(f, verts), minlength=C) if verts is not None else None
+    area = None
+    if verts is not None:   # 0.5 |(v1 - v0) x (v2 - v0)| per triangle
+        n = _face_cross(verts, f)
+        area = np.bincount(cluster, weights=0.5 * np.sqrt(_dot3(n, n)), minlength=C)
     return cluster, counts, area
 
 
@@ -81,7 +73,7 @@ def cluster_connected_triangles(faces, vertices=None):
     if dev.type != "cuda":
         cluster, counts, area = _cluster_numpy(faces.numpy(), vertices.numpy() if vertices is not None else None)
         return torch.from_numpy(cluster), torch.from_numpy(counts), torch.from_numpy(area) if area is not None else None
-    slots = 1 << (6 * F - 1).bit_length()   # the power of two >= 6 F
+    slots = table_slots(F, 6)
     with torch.cuda.device(dev):
         keys = torch.empty(slots, dtype=torch.int64, device=dev)
         owner = torch.empty(slots, dtype=torch.int32, device=dev)
@@ -125,5 +117,5 @@ def post_process_mesh(mesh, cluster_to_keep=1000):
     C = cluster_n_triangles.numel()
     n = torch.sort(cluster_n_triangles)[0][C - min(cluster_to_keep, C)].clamp(min=MIN_CLUSTER_TRIANGLES)
     verts, faces, colors = drop_unreferenced(verts, faces[cluster_n_triangles[triangle_clusters.long()] >= n], colors)
-    faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 2] != faces[:, 0])]
+    faces = faces[proper_faces(faces)]
     return Mesh(verts.to(torch.float32), faces.contiguous(), colors.to(torch.float32))

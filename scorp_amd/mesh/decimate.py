@@ -7,6 +7,7 @@ import torch
 
 from .. import _C
 from ._common import Mesh, check_mesh, drop_unreferenced, empty_mesh
+from ._topology import _cross3, _dot3, edge_keys, proper_faces, vertex_face_csr
 
 DECIMATE_DET_FLOOR = 1e-9    # rule 4: the 3x3 solve is taken iff det > this ((t t) t), t the trace
 DECIMATE_REACH = 4.0         # ... and |x - mid|^2 <= this |P[hi] - P[lo]|^2
@@ -18,15 +19,6 @@ def _splitmix(x):
     x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
     x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
     return x ^ (x >> 31)
-
-
-def _dot3(u, w):
-    return (u[..., 0] * w[..., 0] + u[..., 1] * w[..., 1]) + u[..., 2] * w[..., 2]
-
-
-def _cross3(u, w):
-    return np.stack([u[..., 1] * w[..., 2] - u[..., 2] * w[..., 1], u[..., 2] * w[..., 0] - u[..., 0] * w[..., 2],
-                     u[..., 0] * w[..., 1] - u[..., 1] * w[..., 0]], -1)
 
 
 def _plane_quadric(n, d, w):
@@ -158,7 +150,7 @@ class _DecimateNumpy:
     def faces(self, faces, vmap, out_faces, keep):
         m = vmap.numpy()[faces.numpy()]
         out_faces.numpy()[:] = m
-        keep.numpy()[:] = (m[:, 0] != m[:, 1]) & (m[:, 1] != m[:, 2]) & (m[:, 2] != m[:, 0])
+        keep.numpy()[:] = proper_faces(m)
 
 
 class _DecimateHip:
@@ -191,13 +183,8 @@ class _DecimateHip:
 def _decimate_tables(faces, Nv):
     """One `unique` and one stable sort over the current faces: (edge_keys [E] int64 ascending, face_edge [F, 3] int32,
     edge_faces [E] int32, vf_start [Nv + 1] int32, vf_face [3 F] int32)."""
-    f = faces.long()
-    a, b = f, f.roll(-1, 1)
-    keys, inverse, counts = torch.unique((torch.minimum(a, b) << 32 | torch.maximum(a, b)).reshape(-1), return_inverse=True, return_counts=True)
-    order = torch.sort(f.reshape(-1), stable=True)[1]          # (stable: a vertex's faces in ascending index)
-    start = torch.zeros(Nv + 1, dtype=torch.int32, device=faces.device)
-    start[1:] = torch.cumsum(torch.bincount(f.reshape(-1), minlength=Nv), 0)
-    return keys, inverse.reshape(-1, 3).to(torch.int32).contiguous(), counts.to(torch.int32), start, (order // 3).to(torch.int32)
+    keys, inverse, counts = torch.unique(edge_keys(faces).reshape(-1), return_inverse=True, return_counts=True)
+    return (keys, inverse.reshape(-1, 3).to(torch.int32).contiguous(), counts.to(torch.int32)) + vertex_face_csr(faces, Nv)
 
 
 def _decimate(verts, colors, faces, target, max_err, bw, ops, rounds=None):
@@ -209,7 +196,7 @@ def _decimate(verts, colors, faces, target, max_err, bw, ops, rounds=None):
     P = (verts.double() - origin).contiguous()
     C = colors.double().contiguous()
     count = torch.ones(Nv, dtype=torch.int32, device=dev)
-    faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 2] != faces[:, 0])].contiguous()
+    faces = faces[proper_faces(faces)].contiguous()
     Q = new(Nv, 10, dtype=torch.float64)
     flags, vmin, vmin2, vmap = (new(Nv, dtype=torch.int32) for _ in range(4))
     rnd = 0

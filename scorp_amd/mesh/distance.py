@@ -10,7 +10,7 @@ import torch
 
 from .. import _C
 from ._common import check_mesh
-from .decimate import _cross3, _dot3
+from ._topology import _cross3, _dot3
 
 MAX_QUERIES = (1 << 31) - 1      # the C ABI's bound on queries and samples
 MAX_CLOUD_POINTS = 1 << 30       # ... and on the points of a cloud to search

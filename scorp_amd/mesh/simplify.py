@@ -8,6 +8,7 @@ import torch
 from .. import _C
 from ._common import Mesh, check_mesh, empty_mesh
 from ._common import drop_unreferenced as _drop_unreferenced   # (simplify_vertex_clustering has an argument of that name)
+from ._topology import _dot3, _face_cross, proper_faces, table_slots
 
 CONTRACTIONS = ("average", "quadric")
 CELL_SIDE = 1 << 21             # cell indices per axis: three pack into one 63-bit key
@@ -34,10 +35,8 @@ def _simplify_numpy(v32, col, f, h, quadric):
     if quadric:
         centre = origin + (ijk[first[order]] + 0.5) * h
         f64 = f.astype(np.int64)
-        p0 = v[f64[:, 0]]
-        u, w = v[f64[:, 1]] - p0, v[f64[:, 2]] - p0
-        N = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], 1)
-        length = np.sqrt((N[:, 0] * N[:, 0] + N[:, 1] * N[:, 1]) + N[:, 2] * N[:, 2])
+        p0, N = v[f64[:, 0]], _face_cross(v32, f)
+        length = np.sqrt(_dot3(N, N))
         live = length > 0.0
         f64, p0, N, length = f64[live], p0[live], N[live], length[live]
         a = 0.5 * length
@@ -66,7 +65,7 @@ def _simplify_numpy(v32, col, f, h, quadric):
         moved = (count > 1) & (sigma[:, 0] > 0.0) & (np.abs(x) <= h).all(1)
         positions = np.where(moved[:, None], (centre + x).astype(np.float32), positions)
     t = cell[f.astype(np.int64)]
-    t = t[(t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 2] != t[:, 0])]
+    t = t[proper_faces(t)]
     t = np.take_along_axis(t, (np.argmin(t, 1)[:, None] + np.arange(3)[None]) % 3, 1)
     if t.shape[0]:
         _, keep = np.unique(t, axis=0, return_index=True)   # the first (smallest-index) face of every ordered triple
@@ -79,7 +78,7 @@ def _simplify_gpu(verts, colors, faces, lo, h, quadric):
     Nv, F = verts.shape[0], faces.shape[0]
     i32 = partial(torch.empty, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        slots = 1 << (2 * Nv - 1).bit_length()   # the power of two >= 2 Nv
+        slots = table_slots(Nv, 2)
         keys = torch.empty(slots, dtype=torch.int64, device=dev)
         owner, slot, overflow = i32(slots), i32(Nv), i32(1)
         _C.call("scorp_mesh_simplify_cells", verts, Nv, lo, h, keys, owner, slots, slot, overflow)
@@ -97,7 +96,7 @@ def _simplify_gpu(verts, colors, faces, lo, h, quadric):
         positions = torch.empty(C, 3, dtype=torch.float32, device=dev)
         colours = torch.empty(C, 3, dtype=torch.float32, device=dev)
         _C.call("scorp_mesh_simplify_place", acc, cell_ijk, C, lo, h, quadric, positions, colours)
-        slots = 1 << (2 * F - 1).bit_length()
+        slots = table_slots(F, 2)
         table, rotated = i32(slots), i32(F, 3)
         keep = torch.empty(F, dtype=torch.uint8, device=dev)
         _C.call("scorp_mesh_simplify_faces", faces, F, vertex_cell, Nv, table, slots, rotated, keep)

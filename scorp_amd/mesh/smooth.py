@@ -14,6 +14,7 @@ import torch
 
 from .. import _C
 from ._common import Mesh, check_mesh
+from ._topology import _face_cross, _unit, edge_keys, vertex_face_csr
 from .render import MAX_RENDER_VIEWS
 
 WEIGHTINGS = {"area": _C.MESH_NORMALS_AREA, "uniform": _C.MESH_NORMALS_UNIFORM}                         # rule 6
@@ -63,8 +64,8 @@ def _shapes(mesh):
 
 
 def mesh_adjacency(mesh):
-    """The MeshAdjacency of `mesh` (rules 2 - 4 of the mesh-smooth block of include/scorp_gs.h), built as decimate.py builds
-    its edge keys: 64-bit keys, a sort, unique_consecutive, counts into offsets.  Duplicate faces and non-manifold edges add
+    """The MeshAdjacency of `mesh` (rules 2 - 4 of the mesh-smooth block of include/scorp_gs.h), built on the edge keys and
+    the vertex -> face CSR of _topology.py: 64-bit keys, a sort, unique_consecutive, counts into offsets.  Duplicate faces and non-manifold edges add
     no neighbour; a side with equal ends is ignored; an unreferenced vertex has empty slices.  Pass it as `adjacency=` to
     vertex_normals and the filters to build it once for many calls on meshes of the same faces."""
     checked, Nv, F, dev = _shapes(mesh)
@@ -78,10 +79,8 @@ def mesh_adjacency(mesh):
     directed = torch.unique_consecutive(torch.sort(torch.cat([a << 32 | b, b << 32 | a]))[0])   # rule 2: (v, neighbour) ascending, each once
     neighbors = (directed & 0xFFFFFFFF).to(torch.int32)
     neighbor_offsets = _offsets(torch.bincount(directed >> 32, minlength=Nv))
-    corners = f.reshape(-1)                                          # rule 3: stable, so a vertex's corners in ascending face index
-    corner_faces = (torch.sort(corners, stable=True)[1] // 3).to(torch.int32)
-    corner_offsets = _offsets(torch.bincount(corners, minlength=Nv))
-    sides, counts = torch.unique_consecutive(torch.sort(torch.minimum(a, b) << 32 | torch.maximum(a, b))[0], return_counts=True)
+    corner_offsets, corner_faces = vertex_face_csr(f, Nv)            # rule 3 (every corner, proper side or not)
+    sides, counts = torch.unique_consecutive(torch.sort(edge_keys(f).reshape(-1)[proper])[0], return_counts=True)
     once = sides[counts == 1]                                        # rule 4
     boundary = torch.zeros(Nv, dtype=torch.bool, device=dev)
     boundary[once >> 32] = True
@@ -103,23 +102,7 @@ def _adjacency_for(mesh, adjacency, Nv, F, dev, needed=True):
 
 # ---- the numpy form ----
 
-def _unit_numpy(n):
-    """rule 5: n [..., 3] float64 over its length; +0 where the length is zero"""
-    with np.errstate(all="ignore"):
-        length = np.sqrt((n[..., 0] * n[..., 0] + n[..., 1] * n[..., 1]) + n[..., 2] * n[..., 2])
-        ok = length > 0.0
-        return np.where(ok[..., None], n / np.where(ok, length, 1.0)[..., None], 0.0)
-
-
-def _face_cross_numpy(verts, faces):
-    """rule 5: e1 x e2 of every face, float64 [F, 3]"""
-    v = verts.astype(np.float64)
-    idx = faces.astype(np.int64)
-    a, b, c = v[idx[:, 0]], v[idx[:, 1]], v[idx[:, 2]]
-    e1, e2 = b - a, c - a
-    return np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
-                     e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
-
+# (rule 5 is _topology.py's _face_cross and _unit)
 
 def _ranked(offsets):
     """The slices of a CSR walked in step: yields (rows, positions) for entry 0 of every row that has one, then entry 1,
@@ -133,13 +116,13 @@ def _ranked(offsets):
 
 def _vertex_normals_numpy(verts, faces, corner_offsets, corner_faces, weighting):
     """rule 6"""
-    n = _face_cross_numpy(verts, faces)
+    n = _face_cross(verts, faces)
     if weighting == _C.MESH_NORMALS_UNIFORM:
-        n = _unit_numpy(n)
+        n = _unit(n)
     s = np.zeros((verts.shape[0], 3), np.float64)
     for rows, at in _ranked(corner_offsets):
         s[rows] = s[rows] + n[corner_faces[at]]
-    return _unit_numpy(s).astype(np.float32)
+    return _unit(s).astype(np.float32)
 
 
 def _smooth_step_numpy(src, offsets, neighbors, fixed, factor, weights):
@@ -171,11 +154,11 @@ def _normal_map_numpy(verts, faces, normals, face_map, bary):
     vi, jj, ii = np.nonzero(face_map >= 0)
     f = face_map[vi, jj, ii].astype(np.int64)
     if normals is None:
-        n = _unit_numpy(_face_cross_numpy(verts, faces))[f]
+        n = _unit(_face_cross(verts, faces))[f]
     else:
         N = normals.astype(np.float64)[faces.astype(np.int64)[f]]                 # [n, 3 corners, 3]
         b = [bary[vi, k, jj, ii].astype(np.float64)[:, None] for k in range(3)]
-        n = _unit_numpy((b[0] * N[:, 0] + b[1] * N[:, 1]) + b[2] * N[:, 2])
+        n = _unit((b[0] * N[:, 0] + b[1] * N[:, 1]) + b[2] * N[:, 2])
     for ch in range(3):
         out[vi, ch, jj, ii] = n[:, ch].astype(np.float32)
     return out
@@ -191,8 +174,8 @@ def face_normals(mesh, normalized=True):
         return torch.zeros(F, 3, dtype=torch.float32, device=dev)
     verts, faces = checked[0], checked[1]
     if dev.type != "cuda":
-        n = _face_cross_numpy(verts.numpy(), faces.numpy())
-        return torch.from_numpy((_unit_numpy(n) if normalized else n).astype(np.float32))
+        n = _face_cross(verts.numpy(), faces.numpy())
+        return torch.from_numpy((_unit(n) if normalized else n).astype(np.float32))
     out = torch.empty(F, 3, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _C.call("scorp_mesh_face_normals", verts, Nv, faces, F, 1 if normalized else 0, out)
