@@ -17,6 +17,7 @@ Dataset I/O, tensorboard and checkpoint plumbing of the scripts are out of scope
 cameras and ground-truth tensors that are already resident on the GPU.
 """
 import random
+from typing import Callable, NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -26,6 +27,7 @@ from .rasterizer3d import PairPolicy
 from .loss import depth_losses, depth_normal_losses, isotropic_loss, psnr
 from .parallel import average_gradients, average_gradients_sparse, collective, world
 from .renderer import render
+from .train_view import train_view, train_view2d
 
 
 class PipelineParams:
@@ -34,6 +36,18 @@ class PipelineParams:
     compute_cov3D_python = False
     debug = False
     fused_activations = True
+
+
+class _ViewKind(NamedTuple):
+    """What the one-call views of the two kinds do differently for training_iteration; the rest of the fused branch is shared."""
+    view: Callable           # the default view function
+    surfel_weights: bool     # takes lambda_normal, lambda_dist after lambda_dssim
+    stats_components: int    # the _stats_norm_components its statistics restate (see _stats_components)
+    takes_grad_out: bool     # can write its gradients into the data-parallel arena (train_view2d has no grad_out)
+
+
+_VIEW3D = _ViewKind(train_view, surfel_weights=False, stats_components=2, takes_grad_out=True)
+_VIEW2D = _ViewKind(train_view2d, surfel_weights=True, stats_components=3, takes_grad_out=False)
 
 
 def _sync_densification_stats(gaussians):
@@ -69,61 +83,46 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
     `fused_step` (with `fused_view`): let the view apply the optimizer step itself where that is the same computation (see
     below).  `view_fn`: the one-call view (default train_view.train_view, train_view.train_view2d for surfels; the CPU tests of
     the loop's bookkeeping pass a stand-in)."""
-    stepped_in_view = False
+    stepped_in_view, arena = False, None     # arena: the gradient arena THIS iteration's view wrote into, if it did
     gaussians.update_learning_rate(iteration)
     if iteration % 1000 == 0:
         gaussians.oneupSHdegree()
     bg = torch.rand(3, device=background.device) if opt.random_background else background
     extra_terms = iteration > getattr(opt, "depth_from_iter", 1 << 30) and (
         gt_depth is not None or gt_depth_est is not None or getattr(opt, "lambda_isotropic", 0.0) > 0)
-    if (fused_view and surfels and loss_fn is fused_l1_ssim_loss and getattr(pipe, "fused_activations", False)
-            and hasattr(gaussians, "raw_leaves")):
-        # the 2DGS iteration (train_2dgs.py:95-150) by ONE library call: render + loss + regularisers + backward.  After
-        # depth_from_iter the view carries the depth, depth-normal and isotropic terms too (the conditions of the `else:`
-        # branch below), so the three quarters of a default run that have them stay on this path.
-        view_fn = view_fn or _default_view2d_fn()
-        lambda_normal = opt.lambda_normal if iteration > 7000 else 0.0
-        lambda_dist = opt.lambda_dist if iteration > 3000 else 0.0
-        kw_view = {}
-        if _step_in_view_ok(gaussians, opt, iteration, densify, data_parallel, white_background, fused_step):
-            kw_view["optimizer"] = gaussians.optimizer
-            if densify and iteration < opt.densify_until_iter and _stats_components(gaussians) == 3:
-                kw_view["stats"] = (gaussians.max_radii2D, gaussians.xyz_gradient_accum, gaussians.denom)
-        if extra_terms:
-            kw_view.update(_view_terms_kw(opt, iteration, gt_depth, gt_depth_est, surfels=True))
-        pkg = view_fn(cam, gaussians, pipe, bg, gt_image, opt.lambda_dssim, lambda_normal, lambda_dist, **kw_view)
-        loss = pkg["loss"]
-        stepped_in_view = bool(pkg.get("optimizer_stepped"))
-        ovf = _shared_overflow(pkg, data_parallel)
-        if hasattr(gaussians.optimizer, "skip_flag") and not stepped_in_view:
-            gaussians.optimizer.skip_flag = ovf
-        pkg["visibility_filter"] = pkg["visibility_filter"] & (ovf == 0)
-    elif (fused_view and not surfels and render_fn is render and loss_fn is fused_l1_ssim_loss
-            and getattr(pipe, "fused_activations", False)):
-        # render + loss + backward enqueued by ONE library call (train_view.py); same kernels and results, no autograd
-        # graph.  The pair buffer is reserved, the caller drains (see train()).  After depth_from_iter the view carries the
-        # depth terms and the isotropic regulariser too (the conditions of the `else:` branch below), so the three quarters
-        # of a default run that have them stay on this path.
-        view_fn = view_fn or _default_view_fn()
+    # What this iteration does to the model after its backward (train_3dgs.py:178-188), decided once: the fused branch reads it
+    # to know whether the step may run inside the view, the block under no_grad below carries it out.
+    in_window = densify and iteration < opt.densify_until_iter
+    densifies = in_window and iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0
+    resets = in_window and (iteration % opt.opacity_reset_interval == 0 or (white_background and iteration == opt.densify_from_iter))
+    kind = _VIEW2D if surfels else _VIEW3D
+    if (fused_view and loss_fn is fused_l1_ssim_loss and getattr(pipe, "fused_activations", False)
+            and (hasattr(gaussians, "raw_leaves") if surfels else render_fn is render)):
+        # render + loss (+ the surfel regularisers: train_2dgs.py:95-150) + backward enqueued by ONE library call
+        # (train_view.py); same kernels and results, no autograd graph.  The pair buffer is reserved, the caller drains (see
+        # train()).  After depth_from_iter the view carries the depth, depth-normal and isotropic terms too (the conditions of
+        # the `else:` branch below), so the three quarters of a default run that have them stay on this path.
+        view_fn = view_fn or kind.view
         # The optimizer step itself inside the view (ScorpFusedAdam: the per-Gaussian backward kernel applies Adam and the
         # view's statistics while it holds the gradient row) on the iterations where the reference's optimizer.step() sees
         # this view's gradients as they are: one replica (no averaging first) and neither a densification nor an opacity
         # reset in between - after those the reference's leaves are fresh tensors without .grad and its step() passes them by
         # (train_3dgs.py:183-193), which the separate path below reproduces.
-        step_in_view = _step_in_view_ok(gaussians, opt, iteration, densify, data_parallel, white_background, fused_step)
+        step_in_view = _step_in_view_ok(gaussians, data_parallel, fused_step, densifies, resets)
         kw_view = {}
-        if data_parallel and not sparse_gradients and not step_in_view:
+        if kind.takes_grad_out and data_parallel and not sparse_gradients and not step_in_view:
             # the view writes its gradients straight into the flat arena the collective reduces in place (parallel.GradArena)
             arena = _grad_arena(gaussians)
             if arena is not None:
                 kw_view["grad_out"] = arena.views
         if step_in_view:
             kw_view["optimizer"] = gaussians.optimizer
-            if densify and iteration < opt.densify_until_iter and _stats_components(gaussians) == 2:
+            if in_window and _stats_components(gaussians) == kind.stats_components:
                 kw_view["stats"] = (gaussians.max_radii2D, gaussians.xyz_gradient_accum, gaussians.denom)
         if extra_terms:
-            kw_view.update(_view_terms_kw(opt, iteration, gt_depth, gt_depth_est))
-        pkg = view_fn(cam, gaussians, pipe, bg, gt_image, opt.lambda_dssim, **kw_view)
+            kw_view.update(_view_terms_kw(opt, iteration, gt_depth, gt_depth_est, surfels))
+        weights = _surfel_weights(opt, iteration) if kind.surfel_weights else ()
+        pkg = view_fn(cam, gaussians, pipe, bg, gt_image, opt.lambda_dssim, *weights, **kw_view)
         loss = pkg["loss"]
         stepped_in_view = bool(pkg.get("optimizer_stepped"))
         # The pair buffer was reserved, not sized from this view's count.  If the view overflowed it (device word
@@ -146,10 +145,9 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
             # one condition for both kinds: DESIGN.md 4.6)
             if getattr(opt, "lambda_isotropic", 0.0) > 0:
                 loss = loss + opt.lambda_isotropic * isotropic_loss(gaussians.get_scaling)
-        if surfels:   # train_2dgs.py:142-150: normal consistency after 7000 iterations, depth distortion after 3000
+        if surfels:   # train_2dgs.py:142-150
             from .renderer2d import fused_surfel_regularizers, surfel_regularizers
-            lambda_normal = opt.lambda_normal if iteration > 7000 else 0.0
-            lambda_dist = opt.lambda_dist if iteration > 3000 else 0.0
+            lambda_normal, lambda_dist = _surfel_weights(opt, iteration)
             if lambda_normal > 0 or lambda_dist > 0:
                 reg = fused_surfel_regularizers if getattr(pkg, "allmap", None) is not None else surfel_regularizers
                 normal_loss, dist_loss = reg(pkg, lambda_normal, lambda_dist)
@@ -162,20 +160,18 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
             # flows through the rasterizer: the isotropic regulariser gives EVERY Gaussian a scaling gradient, a
             # caller-supplied render / loss function may do anything, and then the dense average is the right one.
             rasterizer_only = not extra_terms and loss_fn is fused_l1_ssim_loss and (render_fn is render or surfels)
-            arena = getattr(gaussians, "_grad_arena_obj", None)
             if sparse_gradients and rasterizer_only:
                 average_gradients_sparse(ps, pkg["radii"] > 0)    # (the view's own visibility: not masked by an overflow)
-            elif arena is not None and fused_view and all(p.grad is None or (v is not None and p.grad.data_ptr() == v.data_ptr())
-                                                          for p, v in zip(arena.params, arena.views)):
+            elif arena is not None:   # (this iteration's view was handed arena.views as grad_out: the gradients are there)
                 arena.attach()        # (a leaf nothing was written for: zeros)
                 arena.average()       # in place, two collectives back to back, one wait
             else:
                 average_gradients(ps)
-        if densify and iteration < opt.densify_until_iter:
+        if in_window:
             vis, radii = pkg["visibility_filter"], pkg["radii"]
             if not pkg.get("stats_accumulated"):     # (the fused step's kernel has done it)
                 gaussians.accumulate_view_stats(pkg["viewspace_points"], vis, radii)   # train_3dgs.py:180-181, no mask indexing
-            if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
+            if densifies:
                 size_threshold = opt.max_screen_size if iteration > opt.opacity_reset_interval else None   # train_3dgs.py:184
                 if data_parallel:
                     _sync_densification_stats(gaussians)
@@ -185,7 +181,7 @@ def training_iteration(gaussians, cam, gt_image, opt, pipe, background, iteratio
                     # the reservation context keeps pairs PER GAUSSIAN, so the resized model starts from a scaled
                     # reservation; drain now so that it is also the freshest figure (one event wait per 100 iterations)
                     _drain_reservation(optimizer=gaussians.optimizer)
-            if iteration % opt.opacity_reset_interval == 0 or (white_background and iteration == opt.densify_from_iter):
+            if resets:
                 gaussians.reset_opacity()   # train_3dgs.py:187-188
         if not stepped_in_view:
             gaussians.optimizer.step()
@@ -198,7 +194,13 @@ def _dn_l1_weight(opt, iteration):
     return get_expon_lr_func(opt.dn_l1_weight_init, opt.dn_l1_weight_final, max_steps=opt.iterations)(iteration)
 
 
-def _view_terms_kw(opt, iteration, gt_depth, gt_depth_est, surfels=False):
+def _surfel_weights(opt, iteration):
+    """(lambda_normal, lambda_dist) of train_2dgs.py:142-150: normal consistency after 7000 iterations, depth distortion after
+    3000."""
+    return (opt.lambda_normal if iteration > 7000 else 0.0, opt.lambda_dist if iteration > 3000 else 0.0)
+
+
+def _view_terms_kw(opt, iteration, gt_depth, gt_depth_est, surfels):
     """The terms of train_3dgs.py:109-150 / train_2dgs.py:100-139 that apply at this iteration (> depth_from_iter), as
     train_view / train_view2d take them: the conditions and weights of loss.depth_losses, of the depth-normal lines (surfels,
     after depth_from_iter + 1000) and of the isotropic line of the autograd branch."""
@@ -223,15 +225,11 @@ def _stats_components(gaussians):
     return None if owner is None else owner.__dict__.get("_stats_norm_components")
 
 
-def _step_in_view_ok(gaussians, opt, iteration, densify, data_parallel, white_background, fused_step):
+def _step_in_view_ok(gaussians, data_parallel, fused_step, densifies, resets):
     """May this iteration's optimizer step run inside the one-call view?  One replica (no averaging first), a FusedAdam, and
-    neither a densification nor an opacity reset between backward() and step() (train_3dgs.py:183-193)."""
-    will_densify = densify and iteration < opt.densify_until_iter and iteration > opt.densify_from_iter and \
-        iteration % opt.densification_interval == 0
-    will_reset = densify and iteration < opt.densify_until_iter and (
-        iteration % opt.opacity_reset_interval == 0 or (white_background and iteration == opt.densify_from_iter))
-    return bool(fused_step and not data_parallel and not will_densify and not will_reset and
-                hasattr(gaussians.optimizer, "fused_view_pack"))
+    neither a densification nor an opacity reset between backward() and step() (train_3dgs.py:183-193): `densifies` / `resets`
+    are training_iteration's own decisions for this iteration, the ones it then acts on."""
+    return bool(fused_step and not data_parallel and not densifies and not resets and hasattr(gaussians.optimizer, "fused_view_pack"))
 
 
 def _grad_arena(gaussians):
@@ -247,16 +245,6 @@ def _grad_arena(gaussians):
     return arena
 
 
-def _default_view_fn():
-    from .train_view import train_view
-    return train_view
-
-
-def _default_view2d_fn():
-    from .train_view import train_view2d
-    return train_view2d
-
-
 def train(gaussians, cameras, gt_images, opt, pipe=None, iterations=None, background=None, seed=0, data_parallel=False,
           gt_depths=None, gt_depth_ests=None, **kw):
     """Runs `iterations` training iterations over shuffled cameras; returns the list of per-iteration losses.
@@ -270,28 +258,41 @@ def train(gaussians, cameras, gt_images, opt, pipe=None, iterations=None, backgr
     if gaussians.optimizer is None:
         gaussians.training_setup(opt)
     rank, w = world() if data_parallel else (0, 1)
-    rng = random.Random(seed)            # same seed on every rank: identical camera order
-    stack, losses = [], []
-    first_checked, retries = False, 0
-    it = 1
-    while it <= (iterations or opt.iterations):
-        ks = []
-        for _ in range(w):
-            if not stack:
-                stack = list(range(len(cameras)))
-                rng.shuffle(stack)
-            ks.append(stack.pop())
+
+    def iteration(it, ks):
         k = ks[rank]
         if gt_depths is not None:
             kw["gt_depth"] = gt_depths[k]
         if gt_depth_ests is not None:
             kw["gt_depth_est"] = gt_depth_ests[k]
-        loss, _ = training_iteration(gaussians, cameras[k], gt_images[k], opt, pipe, background, it,
-                                     data_parallel=data_parallel and collective(), **kw)
-        if kw.get("fused_view") and not first_checked:
+        return training_iteration(gaussians, cameras[k], gt_images[k], opt, pipe, background, it,
+                                  data_parallel=data_parallel and collective(), **kw)[0]
+    # (the same seed on every rank: identical camera order)
+    return _run_iterations(iteration, iterations or opt.iterations, len(cameras), seed, w, kw.get("fused_view"), gaussians)
+
+
+def _run_iterations(iteration, iterations, n_cameras, seed, group, fused_view, gaussians):
+    """The loop of train() and post_refine(): `iteration(it, ks)` -> loss for it = 1 .. iterations, where `ks` are the next `group`
+    cameras of a shuffled stack (refilled and reshuffled when empty), and with `fused_view` the rule that keeps the reserved pair
+    buffers honest: the first view is checked at once and run again up to three times, every 32nd iteration drains, and so does
+    the end.  Returns the per-iteration losses as floats."""
+    rng = random.Random(seed)
+    stack, losses = [], []
+    first_checked, retries = False, 0
+    it = 1
+    while it <= iterations:
+        ks = []
+        for _ in range(group):
+            if not stack:
+                stack = list(range(n_cameras))
+                rng.shuffle(stack)
+            ks.append(stack.pop())
+        loss = iteration(it, ks)
+        if fused_view and not first_checked:
             # The FIRST fused view of a run sizes the reservation: verified at once (one host synchronisation per run).
             # If it overflowed it was discarded on the device and the reservation has grown: the same views run again,
-            # instead of a context's default being wrong for every iteration up to the first periodic drain.
+            # instead of a context's default being wrong for every iteration up to the first periodic drain (objects that
+            # fill the screen need more than the default four pairs per Gaussian).
             retries += 1
             # (data-parallel replicas take the same decision: the skipped-step count they read is that of the all-reduced word)
             first_checked = _drain_reservation(quiet=retries < 3, optimizer=gaussians.optimizer) or retries >= 3
@@ -299,10 +300,10 @@ def train(gaussians, cameras, gt_images, opt, pipe=None, iterations=None, backgr
                 stack.extend(reversed(ks))
                 continue
         losses.append(loss.detach())
-        if kw.get("fused_view") and it % 32 == 0:
+        if fused_view and it % 32 == 0:
             _drain_reservation(optimizer=gaussians.optimizer)
         it += 1
-    if kw.get("fused_view"):
+    if fused_view:
         _drain_reservation(optimizer=gaussians.optimizer)
     return _to_floats(losses)
 
@@ -368,16 +369,10 @@ def post_refine(gaussians, cameras, gt_images, gt_alphas, opt, iterations=800, p
         gaussians.set_freeze(name, True)
     if fused_view is None:
         fused_view = dev.type == "cuda" and hasattr(gaussians, "raw_leaves") and getattr(pipe, "fused_activations", False)
-    rng = random.Random(seed)
-    stack, losses = [], []
-    sized, retries, it = False, 0, 1
-    while it <= iterations:
-        if not stack:
-            stack = list(range(len(cameras)))
-            rng.shuffle(stack)
-        k = stack.pop()
+
+    def iteration(it, ks):
+        k = ks[0]
         if fused_view:
-            from .train_view import train_view
             pkg = train_view(cameras[k], gaussians, pipe, background, gt_images[k], opt.lambda_dssim, mask=gt_alphas[k])
             loss = pkg["loss"]
             if hasattr(gaussians.optimizer, "skip_flag"):      # a view that overflowed its pair reservation moves nothing
@@ -389,21 +384,8 @@ def post_refine(gaussians, cameras, gt_images, gt_alphas, opt, iterations=800, p
         with torch.no_grad():
             gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
-        if fused_view and not sized:
-            # the first one-call view sizes the pair reservation (see train()): checked at once, run again if it overflowed
-            # (objects that fill the screen need more than the default four pairs per Gaussian)
-            retries += 1
-            sized = _drain_reservation(quiet=retries < 3, optimizer=gaussians.optimizer) or retries >= 3
-            if not sized:
-                stack.append(k)
-                continue
-        losses.append(loss.detach())
-        if fused_view and it % 32 == 0:
-            _drain_reservation(optimizer=gaussians.optimizer)
-        it += 1
-    if fused_view:
-        _drain_reservation(optimizer=gaussians.optimizer)
-    return _to_floats(losses)
+        return loss
+    return _run_iterations(iteration, iterations, len(cameras), seed, 1, fused_view, gaussians)
 
 
 def post_refine_objects(objects, cameras, gt_images, object_alphas, opt, iterations=800, pipe=None, background=None, seed=0,

@@ -109,6 +109,31 @@ class _View:
                 else:
                     p.grad += gp.view_as(p)
 
+    def result(self, loss3, total, header, **own):
+        """What both views return, then the view's `own` keys."""
+        # "overflow": != 0 if this view needed more pairs than were reserved (its images and gradients then come from truncated
+        # tile lists): a device word, so the caller can make the optimizer step conditional without a host sync
+        return {"optimizer_stepped": self.fused_step, "stats_accumulated": self.stats_accumulated, "render": self.color,
+                "viewspace_points": _ViewspaceGrad(self.g_means2D), "radii": self.radii, "loss": total, "l1": loss3[1],
+                "ssim": loss3[2], "overflow": header.view(torch.int32)[1:2], **own}
+
+
+def _any_term(depth_sensor, depth_est, *weights):
+    """Was any term of ScorpGs3dViewTerms / ScorpGs2dViewTerms asked for?  (With none the plain entry point is called.)"""
+    return depth_sensor is not None or depth_est is not None or any(weights)
+
+
+def _depth_maps(c, depth_sensor, depth_est):
+    """The two optional depth maps of a view's terms, checked against the view's size and laid out as the library reads them."""
+    maps = []
+    for t, name in ((depth_sensor, "depth_sensor"), (depth_est, "depth_est")):
+        if t is not None:
+            if t.numel() != c.H * c.W:
+                raise ValueError(f"{name}: {tuple(t.shape)} is not a depth map of the view ({c.H} x {c.W})")
+            t = _prep(t, name)
+        maps.append(t)
+    return maps
+
 
 def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2, mask=None, scaling_modifier=1.0,
                optimizer=None, stats=None, grad_out=None, depth_sensor=None, depth_est=None, lambda_depth_sensor=0.0,
@@ -149,7 +174,7 @@ def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2,
     v.out_depth_raw, v.out_alpha, v.out_depth, v.out_visible = depth_raw.data_ptr(), alpha.data_ptr(), depth.data_ptr(), visible.data_ptr()
     v.out_loss3, v.out_header = loss3.data_ptr(), header.data_ptr()
     terms = None
-    if depth_sensor is not None or depth_est is not None or lambda_depth_sensor or weight_depth_est or lambda_isotropic:
+    if _any_term(depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, lambda_isotropic):
         terms, keep = _view_terms(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, lambda_isotropic)
         _C.check(L.scorp_gs3d_train_view_ex(ctypes.byref(v), ctypes.byref(terms), _stream()), "scorp_gs3d_train_view_ex")
     else:
@@ -161,23 +186,13 @@ def train_view(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.2,
         terms4 = keep[0]
         extra = {"photometric_loss": loss3[0], "depth_sensor_loss": terms4[1], "depth_est_loss": terms4[2], "isotropic_loss": terms4[3]}
         total = loss3[0] + terms4[0]      # the convention of the 2DGS twin: out_loss3[0] + out_terms4[0]
-    return {**extra, "optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": visible.view(torch.bool),
-            "radii": c.radii, "render_depth": depth, "render_alpha": alpha, "loss": total, "l1": loss3[1], "ssim": loss3[2],
-            # != 0 if this view needed more pairs than were reserved (its images and gradients then come from truncated
-            # tile lists): a device word, so the caller can make the optimizer step conditional without a host sync
-            "overflow": header.view(torch.int32)[1:2]}
+    return c.result(loss3, total, header, visibility_filter=visible.view(torch.bool), render_depth=depth, render_alpha=alpha, **extra)
 
 
 def _view_terms(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, lambda_isotropic):
     """The ScorpGs3dViewTerms of one view and the tensors it points to (out_terms4 first)."""
     H, W, N = c.H, c.W, c.N
-    maps = []
-    for t, name in ((depth_sensor, "depth_sensor"), (depth_est, "depth_est")):
-        if t is not None:
-            if t.numel() != H * W:
-                raise ValueError(f"{name}: {tuple(t.shape)} is not a depth map of the view ({H} x {W})")
-            t = _prep(t, name)
-        maps.append(t)
+    maps = _depth_maps(c, depth_sensor, depth_est)
     ws_bytes = L.scorp_gs3d_view_terms_workspace_bytes(W, H, N)
     keep = [c.new((4,)), c.new((ws_bytes,), torch.uint8), *maps]
     t = _C.ScorpGs3dViewTerms()
@@ -236,8 +251,7 @@ def train_view2d(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.
     v.out_loss3, v.out_reg2 = loss5.data_ptr(), loss5[3:].data_ptr()
     v.reg_workspace, v.reg_workspace_bytes = rws.data_ptr(), rws_bytes
     terms = None
-    if (depth_sensor is not None or depth_est is not None or lambda_depth_sensor or weight_depth_est or weight_depth_normal
-            or lambda_isotropic):
+    if _any_term(depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, weight_depth_normal, lambda_isotropic):
         terms, keep, depth = _view_terms2d(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est,
                                            weight_depth_normal, lambda_isotropic)
         _C.check(L.scorp_gs2d_train_view_ex(ctypes.byref(v), ctypes.byref(terms), _stream()), "scorp_gs2d_train_view_ex")
@@ -251,21 +265,13 @@ def train_view2d(viewpoint_camera, pc, pipe, bg_color, gt_image, lambda_dssim=0.
         extra = {"photometric_loss": loss5[0], "depth_sensor_loss": t6[1], "depth_est_loss": t6[2], "depth_normal_loss": t6[3],
                  "render_normal_loss": t6[4], "isotropic_loss": t6[5], "render_depth": depth}
         total = total + t6[0]
-    return {**extra, "optimizer_stepped": c.fused_step, "stats_accumulated": c.stats_accumulated, "render": c.color, "allmap": allmap, "viewspace_points": _ViewspaceGrad(c.g_means2D), "visibility_filter": c.radii > 0,
-            "radii": c.radii, "loss": total, "l1": loss5[1], "ssim": loss5[2],
-            "normal_loss": loss5[3], "dist_loss": loss5[4], "overflow": header.view(torch.int32)[1:2]}
+    return c.result(loss5, total, header, allmap=allmap, visibility_filter=c.radii > 0, normal_loss=loss5[3], dist_loss=loss5[4], **extra)
 
 
 def _view_terms2d(L, c, depth_sensor, depth_est, lambda_depth_sensor, weight_depth_est, weight_depth_normal, lambda_isotropic):
     """The ScorpGs2dViewTerms of one view, the tensors it points to (out_terms6 first) and the surface-depth map (or None)."""
     H, W, N = c.H, c.W, c.N
-    maps = []
-    for t, name in ((depth_sensor, "depth_sensor"), (depth_est, "depth_est")):
-        if t is not None:
-            if t.numel() != H * W:
-                raise ValueError(f"{name}: {tuple(t.shape)} is not a depth map of the view ({H} x {W})")
-            t = _prep(t, name)
-        maps.append(t)
+    maps = _depth_maps(c, depth_sensor, depth_est)
     ws_bytes = L.scorp_gs2d_view_terms_workspace_bytes(W, H, N)
     keep = [c.new((6,)), c.new((ws_bytes,), torch.uint8), *maps]
     t = _C.ScorpGs2dViewTerms()

@@ -327,6 +327,60 @@ def test_an_overflow_on_one_replica_keeps_step_counters_and_parameters_equal():
         assert same, "replicas diverged"
 
 
+# ---- a caller who leaves the fused branch right after a densification: the arena of the old leaves must not be averaged ----
+def _path_change_worker(rank, world_size, port, q):
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world_size)
+    try:
+        import scorp_amd.train as T
+        from scorp_amd.fused_loss import fused_l1_ssim_loss
+        T._drain_reservation = lambda **kw: True       # (the reservation bookkeeping of real views: nothing is pending here)
+        m, opt, cams, gts = _dp_setup()
+        m.training_setup(opt)
+        view, sizes = _overflowing_view(-1, []), []    # (rank -1: never overflows)
+        for it in range(1, 7):
+            k = (2 * it + rank) % len(cams)
+            path = dict(loss_fn=fused_l1_ssim_loss, view_fn=view) if it <= 4 else dict(render_fn=_fake_render, loss_fn=_plain_loss)
+            T.training_iteration(m, cams[k], gts[k], opt, T.PipelineParams(), torch.zeros(3), it, data_parallel=True, fused_view=True, **path)
+            sizes.append(m._xyz.shape[0])
+        flat = torch.cat([p.detach().reshape(-1) for p in (m._xyz, m._features_dc, m._features_rest, m._opacity, m._scaling, m._rotation)])
+        numels = [torch.zeros(1, dtype=torch.int64) for _ in range(world_size)]
+        dist.all_gather(numels, torch.tensor([flat.numel()]))
+        same = len({int(n) for n in numels}) == 1
+        if same:
+            both = [torch.zeros_like(flat) for _ in range(world_size)]
+            dist.all_gather(both, flat)
+            same = bool(torch.equal(both[0], both[1]))
+        q.put((rank, "ok", sizes, [int(n) for n in numels], same))
+    except Exception as e:  # pragma: no cover
+        import traceback
+        q.put((rank, repr(e) + traceback.format_exc(), [], [], False))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_leaving_the_fused_branch_after_a_densification_keeps_replicas_identical():
+    """Iterations 1-4 take the fused branch (the stand-in view writes into the gradient arena), iteration 4 densifies, iterations
+    5-6 take the autograd branch with a caller's render and loss.  The arena cached on the model then belongs to leaves that no
+    longer exist, whose .grad still are its views: an averaging that looked the arena up there reduced that dead buffer and left
+    the live gradients alone, so each replica stepped on its own view (the advisor's round-6 finding).  The averaging uses the
+    arena only in the iteration that filled it: both replicas end with the same number of Gaussians and the same parameter bits."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_path_change_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=240) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+    assert all(r[1] == "ok" for r in res), res
+    for rank, _, sizes, numels, same in res:
+        assert sizes[2] == 40 and sizes[3] != 40, (rank, sizes)     # iteration 4 resized the model: the arena of 1-3 is stale
+        assert len(set(numels)) == 1, (rank, numels)
+        assert same, "replicas diverged"
+
+
 # ---- rotation_sweep itself on two gloo ranks (a stand-in renderer replaces the HIP rasterizer on CPU) ----
 def _standin_render(cam, pc, pipe, bg, **_):
     """Orthographic depth / alpha splat of the points onto a 16x16 grid: enough for the fitness to prefer the planted
