@@ -73,9 +73,19 @@ def _simplify_numpy(v32, col, f, h, quadric):
     return cell.astype(np.int32), positions, colours, t.astype(np.int32).reshape(-1, 3)
 
 
-def _simplify_gpu(verts, colors, faces, lo, h, quadric):
+def check_grid_fits(ends, h):
+    """The host-side extent check of rule 1: `ends` [2, 3] float64, the bounding box; every cell index must be < 2^21."""
+    origin = ends[0] - 0.5 * h
+    if not (np.floor((ends[1] - origin) / h) < CELL_SIDE).all():
+        raise ValueError(f"an extent of {tuple((ends[1] - ends[0]).tolist())} at voxel_size {h} needs more than 2^21 cells on an axis")
+
+
+def cluster_cells_gpu(verts, colors, faces, lo, h, quadric):
+    """Rules 1 - 4 on the GPU: (vertex_cell [Nv] int32, positions [C, 3], colours [C, 3]) of the points `verts` with their
+    `colors`, lo their minimum per axis (a device tensor).  faces may be None with quadric = 0: a bare cloud
+    (cloud.voxel_down_sample)."""
     dev = verts.device
-    Nv, F = verts.shape[0], faces.shape[0]
+    Nv, F = verts.shape[0], 0 if faces is None else faces.shape[0]
     i32 = partial(torch.empty, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         slots = table_slots(Nv, 2)
@@ -96,8 +106,16 @@ def _simplify_gpu(verts, colors, faces, lo, h, quadric):
         positions = torch.empty(C, 3, dtype=torch.float32, device=dev)
         colours = torch.empty(C, 3, dtype=torch.float32, device=dev)
         _C.call("scorp_mesh_simplify_place", acc, cell_ijk, C, lo, h, quadric, positions, colours)
+    return vertex_cell, positions, colours
+
+
+def _simplify_gpu(verts, colors, faces, lo, h, quadric):
+    dev = verts.device
+    Nv, F = verts.shape[0], faces.shape[0]
+    vertex_cell, positions, colours = cluster_cells_gpu(verts, colors, faces, lo, h, quadric)
+    with torch.cuda.device(dev):
         slots = table_slots(F, 2)
-        table, rotated = i32(slots), i32(F, 3)
+        table, rotated = torch.empty(slots, dtype=torch.int32, device=dev), torch.empty(F, 3, dtype=torch.int32, device=dev)
         keep = torch.empty(F, dtype=torch.uint8, device=dev)
         _C.call("scorp_mesh_simplify_faces", faces, F, vertex_cell, Nv, table, slots, rotated, keep)
         return vertex_cell, positions, colours, rotated[keep.bool()]
@@ -113,11 +131,7 @@ def cluster_vertices(mesh, voxel_size, contraction="average"):
     if not (h > 0.0 and np.isfinite(h)):
         raise ValueError(f"voxel_size must be positive and finite; got {voxel_size}")
 
-    def grid_fits(ends):
-        origin = ends[0] - 0.5 * h
-        if not (np.floor((ends[1] - origin) / h) < CELL_SIDE).all():
-            raise ValueError(f"an extent of {tuple((ends[1] - ends[0]).tolist())} at voxel_size {h} needs more than 2^21 cells on an axis")
-    checked = check_mesh(mesh, extent=grid_fits)
+    checked = check_mesh(mesh, extent=partial(check_grid_fits, h=h))
     dev = mesh.vertices.device
     if checked is None:
         return torch.empty(0, dtype=torch.int32, device=dev), empty_mesh(dev)
