@@ -337,6 +337,63 @@ int scorp_cloud_dbscan(const float *points, int32_t n, double eps, int32_t min_p
                        int32_t *out_count, int32_t *out_num_clusters, void *workspace, size_t workspace_bytes,
                        scorp_stream_t stream);
 
+/* ---- global registration from geometry alone: the FPFH descriptor and the nearest-descriptor search (what Open3D's
+ * compute_fpfh_feature and registration_ransac_based_on_feature_matching are used for, next to registration_icp;
+ * scorp_amd/global_registration.py drives them and hands the matched pairs to scorp_pose_ransac) ----
+ * Open3D could not be run where this was written.  The rules below ARE the specification; nothing was compared with
+ * Open3D's own output, and "believed, unchecked" marks what Open3D is believed to do.  tests/fpfh_reference.py restates
+ * the rules as a float64 brute force.
+ *
+ * points[n, 3] and normals[n, 3] are float32, finite (the caller's to check) and only read; the normals are used as given
+ * and NOT normalised.  All arithmetic is float64 from the float32 inputs, every product and sum rounded on its own (no fp
+ * contraction); sqrt and / are correctly rounded.  No float atomics.  Every output is a function of the input alone, and
+ * permuting the input permutes the outputs.
+ *
+ * F1 neighbourhood. d2 is R1 of the cloud block.  N(i) = the first min(max_nn, .) of { j != i : d2(i, j) <= radius radius }
+ *                 in ascending (d2, j); radius radius is one rounded product.  i is left out BY INDEX: a duplicate of i is
+ *                 a member.  m_i = |N(i)|.  Open3D's hybrid search counts the point itself, so its max_nn is believed,
+ *                 unchecked, to be ours + 1.  The grid only prunes (R8).  The list is written once and read by F4 and F5.
+ * F2 pair feature of (i, j), j in N(i).  dp = p_j - p_i (each difference exact), f4 = sqrt(d2); f4 = 0 gives no feature.
+ *                 dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.  a1 = dot(n_i, dp) / f4, a2 = dot(n_j, dp) / f4.  If
+ *                 |a1| < |a2| (strict) then (u, n2, dp, f3) = (n_j, n_i, -dp, -a2), else (u, n2, f3) = (n_i, n_j, a1): Open3D's
+ *                 acos(|a1|) > acos(|a2|) stated without acos, believed equivalent, unchecked.  v = dp x u, each component
+ *                 a difference of two rounded products; |v| = sqrt(dot(v, v)); |v| = 0 gives no feature (Open3D is
+ *                 believed, unchecked, to bin a zero feature instead).  v = v / |v| per component, w = u x v,
+ *                 f2 = dot(v, n2), f1 = atan2(dot(w, n2), dot(u, n2)).
+ * F3 bins.        b1 = floor((11 (f1 + pi)) / (2 pi)), b2 = floor(11 ((f2 + 1) 0.5)), b3 = floor(11 ((f3 + 1) 0.5)), each
+ *                 clamped to [0, 10]; pi is M_PI, 2 pi its exact double.
+ * F4 SPFH.        count_i[11 k + b_k] += 1 for k = 0, 1, 2 per pair that has a feature (integers: the order is free).
+ *                 spfh_i = count_i (100.0 / m_i): one rounded division, one product per bin; m_i = 0 gives a zero row.
+ *                 Pairs without a feature still count in m_i.
+ * F5 FPFH.        s = a zero row of 33.  For j in N(i) IN LIST ORDER with d2(i, j) > 0: s[b] = s[b] + spfh_j[b] / d2(i, j).
+ *                 For each block k of 11: t = the sum of its entries in ascending order from 0.0; if t != 0 the block's
+ *                 entries are multiplied by (100.0 / t).  out_feature[i] = s + spfh_i.
+ *
+ * scorp_cloud_fpfh: out_feature[n, 33] float64; optional (NULL: kept in the workspace) out_spfh_count[n, 33] int32,
+ * out_neighbors[n, max_nn] int32 padded with -1 and out_degree[n] int32 (m_i).  workspace:
+ * scorp_cloud_fpfh_workspace_bytes(n, max_nn), 256-byte aligned.  Does not synchronise.  SCORP_ERR_INVALID: n < 1 or
+ * > 2^30, radius not positive and finite, max_nn outside [1, 64], a NULL points / normals / out_feature, a workspace NULL,
+ * too small or misaligned.
+ *
+ * M1 match.       src[ns, 33] and tgt[nt, 33] are float32 (the descriptor rounded once by the caller).  D2(a, b) = the sum
+ *                 for k = 0 .. 32 in ascending order from 0.0 of (double(a_k) - double(b_k))^2, each difference exact.
+ *                 out_index[i] = the target row of smallest (D2, index), out_d2[i] its D2.  (A source row with a NaN has
+ *                 no smallest D2: index -1, D2 +inf.)
+ * scorp_feature_match: a brute force.  The target's tiles of scorp_feature_match_tile_rows() rows are split over a second
+ * grid dimension, scorp_feature_match_split_rows(ns, nt) rows per split, and the splits' bests are merged by the same rule
+ * in a second kernel: no atomics.  workspace: scorp_feature_match_workspace_bytes(ns, nt), 256-byte aligned (the splits'
+ * partial results).  Does not synchronise.  SCORP_ERR_INVALID: ns or nt < 1 or > 2^30, a NULL pointer, a workspace NULL,
+ * too small or misaligned. */
+size_t scorp_cloud_fpfh_workspace_bytes(int32_t n, int32_t max_nn);
+int scorp_cloud_fpfh(const float *points, const float *normals, int32_t n, double radius, int32_t max_nn, double *out_feature,
+                     int32_t *out_spfh_count, int32_t *out_neighbors, int32_t *out_degree, void *workspace,
+                     size_t workspace_bytes, scorp_stream_t stream);
+int32_t scorp_feature_match_tile_rows(void);
+int32_t scorp_feature_match_split_rows(int32_t ns, int32_t nt);
+size_t scorp_feature_match_workspace_bytes(int32_t ns, int32_t nt);
+int scorp_feature_match(const float *src, int32_t ns, const float *tgt, int32_t nt, int32_t *out_index, double *out_d2,
+                        void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+
 /* ---- pose fit from matched 3-D point pairs (utils/solution.py: pc_align_ransac :476-557 and adam_algorithm_3d3d_9dof
  * :363-446, called once per round and object by the alignment scripts) ----
  * source[n_pairs, 3] and target[n_pairs, 3] are float64 device pointers, row i of one matched to row i of the other; every

@@ -127,6 +127,8 @@ EXPORTS = [
     "scorp_icp_point_to_plane_workspace_bytes", "scorp_icp_point_to_plane",
     "scorp_estimate_normals_workspace_bytes", "scorp_estimate_normals",
     "scorp_cloud_workspace_bytes", "scorp_cloud_knn_distance", "scorp_cloud_radius_count", "scorp_cloud_dbscan",
+    "scorp_cloud_fpfh_workspace_bytes", "scorp_cloud_fpfh", "scorp_feature_match_tile_rows", "scorp_feature_match_split_rows",
+    "scorp_feature_match_workspace_bytes", "scorp_feature_match",
     "scorp_pose_fit_workspace_bytes", "scorp_pose_ransac", "scorp_pose_adam_9dof",
     "scorp_tsdf_fuse", "scorp_isosurface_count_cells", "scorp_isosurface_emit_vertices", "scorp_isosurface_count_faces",
     "scorp_isosurface_emit_faces",
@@ -266,6 +268,16 @@ def lib():
     L.scorp_cloud_knn_distance.argtypes = [vp, i32, i32, vp, vp, vp, sz, vp]
     L.scorp_cloud_radius_count.argtypes = [vp, i32, f64, vp, vp, sz, vp]
     L.scorp_cloud_dbscan.argtypes = [vp, i32, f64, i32, vp, vp, vp, vp, vp, sz, vp]
+    L.scorp_cloud_fpfh_workspace_bytes.restype = sz
+    L.scorp_cloud_fpfh_workspace_bytes.argtypes = [i32, i32]
+    L.scorp_cloud_fpfh.argtypes = [vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, sz, vp]
+    L.scorp_feature_match_tile_rows.restype = i32
+    L.scorp_feature_match_tile_rows.argtypes = []
+    L.scorp_feature_match_split_rows.restype = i32
+    L.scorp_feature_match_split_rows.argtypes = [i32, i32]
+    L.scorp_feature_match_workspace_bytes.restype = sz
+    L.scorp_feature_match_workspace_bytes.argtypes = [i32, i32]
+    L.scorp_feature_match.argtypes = [vp, i32, vp, i32, vp, vp, vp, sz, vp]
     L.scorp_pose_fit_workspace_bytes.restype = sz
     L.scorp_pose_fit_workspace_bytes.argtypes = [i32, i32]
     L.scorp_pose_ransac.argtypes = [vp, vp, i32, vp, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
