@@ -394,6 +394,54 @@ size_t scorp_feature_match_workspace_bytes(int32_t ns, int32_t nt);
 int scorp_feature_match(const float *src, int32_t ns, const float *tgt, int32_t nt, int32_t *out_index, double *out_d2,
                         void *workspace, size_t workspace_bytes, scorp_stream_t stream);
 
+/* ---- consistent orientation of a cloud's normals: signs propagated along the minimum spanning forest of the neighbour
+ * graph (what Open3D's orient_normals_consistent_tangent_plane is used for; the descriptor above is built from Darboux
+ * frames and depends on the sign of every normal).  The rules below ARE the specification and are this project's own:
+ * nothing was compared with Open3D, whose Riemannian graph adds the edges of a Euclidean spanning tree; those are not
+ * built.  tests/orient_reference.py restates the rules in float64 numpy (Kruskal in O3's order).
+ *
+ * points[n, 3] and normals[n, 3] are float32, finite (the caller's to check) and only read; the normals are used as given
+ * and NOT normalised.  neighbors[n, k] is int32.  Every pointer but `center` is a device pointer.
+ *
+ * O1 graph.       The vertices are the n points.  {i, j}, i != j, is an edge when j is in row i of the list or i is in row
+ *                 j.  1 <= k <= 64.  An entry < 0 is padding, an entry equal to its row index is ignored, duplicates are
+ *                 harmless.  An entry >= n is an error that the CALLER rejects before the call (the Python wrapper does and
+ *                 raises); the kernels skip such an entry and never follow it.  n <= 2^30.
+ * O2 weight.      dot(i, j) = (nx_i nx_j + ny_i ny_j) + nz_i nz_j in float64 on the float32 normals, every product and sum
+ *                 rounded on its own (no fp contraction); w = 1 - |dot|.  w may be negative for normals longer than 1.
+ * O3 order.       Edges are ordered by (w, min(i, j), max(i, j)), lexicographically: a strict total order, so the minimum
+ *                 spanning forest is unique.
+ * O4 propagation. Along an edge of the forest the two ends agree when dot >= 0 and are opposite when dot < 0; a dot of
+ *                 exactly 0 is not a flip.  rel(x) is the parity of x relative to the smallest index m of its component,
+ *                 rel(m) = 0.
+ * O5 component sign.  SCORP_ORIENT_MAJORITY_AWAY: c = center[3] (HOST float64, finite), or for a NULL center the float64
+ *                 mean of the points by this fixed order of additions: S_g, g < 16384, = the sum from 0.0 of the points
+ *                 g, g + 16384, g + 32768, ... in ascending order; T_t, t < 256, = the sum from 0.0 of S_64t .. S_64t+63
+ *                 in ascending order; c = (the sum from 0.0 of T_0 .. T_255 in ascending order) / n, per coordinate.  For
+ *                 each member with its O4 sign, d = p - c (one rounded difference per coordinate) and
+ *                 dd = (n.x d.x + n.y d.y) + n.z d.z in float64; votes = #(dd > 0) - #(dd < 0), counted with integer
+ *                 atomics.  The component is flipped when votes < 0; a tie leaves it.  SCORP_ORIENT_FIRST: no vote, m keeps
+ *                 its given normal.
+ * O6 outputs.     out_normals[n, 3] float32: each row is the input row or its IEEE negation bit for bit (a zero becomes
+ *                 -0.0).  Optional (NULL: skipped) out_flip[n] one byte per point, out_label[n] int32 = m, out_tree[n, 2]
+ *                 int32 = the forest's edges as (lo, hi), (-1, -1) in unused rows, the order of the rows unspecified.
+ *                 out_counts[2] int32 = {components, edges of the forest}.
+ *
+ * scorp_cloud_orient_normals: Boruvka rounds of four launches (smallest weight per component and smallest (lo, hi) among
+ * its edges by two 64-bit atomicMin passes, one hook per root, one compression), ceil(log2 n) + 1 of them launched
+ * unconditionally, a round with nothing to do returning on a device flag.  Only integer atomics whose result does not
+ * depend on their order: two calls give the same bits and every output is a function of the input alone.  workspace:
+ * scorp_cloud_orient_workspace_bytes(n, k), 256-byte aligned.  Does not synchronise and reads nothing back.
+ * SCORP_ERR_INVALID: n < 1 or > 2^30, k outside [1, 64], an unknown component_sign, a center that is not finite, a NULL
+ * points / normals / neighbors / out_normals / out_counts, a workspace NULL, too small or misaligned. */
+#define SCORP_ORIENT_MAJORITY_AWAY 0
+#define SCORP_ORIENT_FIRST 1
+size_t scorp_cloud_orient_workspace_bytes(int32_t n, int32_t k);
+int scorp_cloud_orient_normals(const float *points, const float *normals, const int32_t *neighbors, int32_t n, int32_t k,
+                               const double *center, int32_t component_sign, float *out_normals, uint8_t *out_flip,
+                               int32_t *out_label, int32_t *out_tree, int32_t *out_counts, void *workspace,
+                               size_t workspace_bytes, scorp_stream_t stream);
+
 /* ---- pose fit from matched 3-D point pairs (utils/solution.py: pc_align_ransac :476-557 and adam_algorithm_3d3d_9dof
  * :363-446, called once per round and object by the alignment scripts) ----
  * source[n_pairs, 3] and target[n_pairs, 3] are float64 device pointers, row i of one matched to row i of the other; every

@@ -129,6 +129,7 @@ EXPORTS = [
     "scorp_cloud_workspace_bytes", "scorp_cloud_knn_distance", "scorp_cloud_radius_count", "scorp_cloud_dbscan",
     "scorp_cloud_fpfh_workspace_bytes", "scorp_cloud_fpfh", "scorp_feature_match_tile_rows", "scorp_feature_match_split_rows",
     "scorp_feature_match_workspace_bytes", "scorp_feature_match",
+    "scorp_cloud_orient_workspace_bytes", "scorp_cloud_orient_normals",
     "scorp_pose_fit_workspace_bytes", "scorp_pose_ransac", "scorp_pose_adam_9dof",
     "scorp_tsdf_fuse", "scorp_isosurface_count_cells", "scorp_isosurface_emit_vertices", "scorp_isosurface_count_faces",
     "scorp_isosurface_emit_faces",
@@ -158,6 +159,7 @@ POSE_UMEYAMA, POSE_KABSCH = 0, 1   # methods of scorp_pose_ransac
 MESH_RENDER_CULL_BACKFACES = 1   # flag of scorp_mesh_render (include/scorp_gs.h)
 MESH_NORMALS_AREA, MESH_NORMALS_UNIFORM = 0, 1   # weightings of scorp_mesh_vertex_normals
 MESH_SMOOTH_UNIFORM, MESH_SMOOTH_INVERSE_DISTANCE = 0, 1   # weights of scorp_mesh_smooth
+ORIENT_MAJORITY_AWAY, ORIENT_FIRST = 0, 1   # component_sign of scorp_cloud_orient_normals
 ERR_INVALID, ERR_NO_INLIERS = -1, -4   # return codes the Python layer tells apart (include/scorp_gs.h)
 
 _lib = None
@@ -278,6 +280,9 @@ def lib():
     L.scorp_feature_match_workspace_bytes.restype = sz
     L.scorp_feature_match_workspace_bytes.argtypes = [i32, i32]
     L.scorp_feature_match.argtypes = [vp, i32, vp, i32, vp, vp, vp, sz, vp]
+    L.scorp_cloud_orient_workspace_bytes.restype = sz
+    L.scorp_cloud_orient_workspace_bytes.argtypes = [i32, i32]
+    L.scorp_cloud_orient_normals.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(f64), i32, vp, vp, vp, vp, vp, vp, sz, vp]
     L.scorp_pose_fit_workspace_bytes.restype = sz
     L.scorp_pose_fit_workspace_bytes.argtypes = [i32, i32]
     L.scorp_pose_ransac.argtypes = [vp, vp, i32, vp, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]

@@ -10,14 +10,20 @@ The descriptor and its neighbour search are csrc/cloud_fpfh.hip (scorp_cloud_fpf
 is csrc/feature_match.hip (scorp_feature_match); the pose fit is scorp_pose_ransac as it stands and the refinement is
 registration_icp.  The rules F1 - F5 and M1 are in include/scorp_gs.h; they are this project's own.  Open3D was never run
 where this was written: where a rule follows what Open3D is believed to do, that is believed, unchecked.
+
+The descriptor depends on the sign of every normal.  orient_normals_away_from is the cheap orientation, right on
+star-shaped objects; orient_normals_consistent_tangent_plane (csrc/cloud_orient.hip, scorp_cloud_orient_normals, rules
+O1 - O6) propagates signs along the minimum spanning forest of the neighbour graph and is the one for cups and shelves:
+get_FPFH_fitting_transformation(..., orientation="tangent_plane").
 """
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _C
-from .cloud import _at_least, _cloud, _positive, voxel_down_sample
+from .cloud import _at_least, _cloud, _positive, knn_mean_distance, voxel_down_sample
 from .icp import _check_finite, _device, _points, downsample_indices, estimate_normals, registration_icp
 from .pose_fit import MAX_HYPOTHESES, ransac_fit
 
@@ -49,7 +55,9 @@ def orient_normals_away_from(points, normals, center=None):
     """normals with every n flipped for which dot(n, p - c) < 0, c the float64 mean of the points unless `center` is
     given; a zero dot leaves n unchanged.  Plain torch, the dot in float64; returns a tensor of the normals' dtype on
     their device.  The cheap orientation the descriptor needs on a star-shaped object: estimate_normals signs by the
-    largest component, which is not equivariant under rotation.  Consistent-tangent-plane orientation is not built."""
+    largest component, which is not equivariant under rotation.  Right only for an object that is roughly star-shaped
+    about c: the inner wall of a cup points away from the centroid and is signed inwards.  For everything else there is
+    orient_normals_consistent_tangent_plane."""
     N = normals if isinstance(normals, torch.Tensor) else torch.as_tensor(np.asarray(normals))
     P = points if isinstance(points, torch.Tensor) else torch.as_tensor(np.asarray(points))
     if P.dim() != 2 or P.shape[1] != 3 or P.shape[0] == 0:
@@ -68,6 +76,96 @@ def orient_normals_away_from(points, normals, center=None):
     n64 = N.to(torch.float64)
     dot = (n64[:, 0] * d[:, 0] + n64[:, 1] * d[:, 1]) + n64[:, 2] * d[:, 2]
     return torch.where((dot < 0)[:, None], -N, N)
+
+
+COMPONENT_SIGNS = {"majority_away": _C.ORIENT_MAJORITY_AWAY, "first": _C.ORIENT_FIRST}
+ORIENT_MAX_K = 64       # columns of a neighbour list scorp_cloud_orient_normals takes
+ORIENT_ROUTE_K = 12     # columns of the estimate_normals list the route orients over
+
+
+def orient_normals_consistent_tangent_plane(points, normals, k=12, neighbors=None, center=None, component_sign="majority_away",
+                                            return_info=False):
+    """normals with signs made consistent between neighbouring tangent planes (rules O1 - O6 of include/scorp_gs.h): the
+    signs are propagated along the minimum spanning forest of the neighbour graph, edge weight 1 - |n_i . n_j|, and each
+    connected component is then signed as a whole - with component_sign="majority_away" so that most of its normals point
+    away from `center` (default: the float64 mean of the points), with "first" so that its smallest index keeps its normal.
+    One call of scorp_cloud_orient_normals (csrc/cloud_orient.hip), no read-back inside it; every output is a function of
+    the input alone.
+
+    Without `neighbors` the graph is cloud.knn_mean_distance(points, min(k + 1, 32), return_neighbors=True)[1]: the exact
+    k nearest, the point itself included (and ignored).  With `neighbors` any [n, <= 64] int32 list is taken as it is:
+    estimate_normals(..., return_neighbors=True), the FPFH list, or their first columns; entries < 0 are padding, an entry
+    >= n raises ValueError.  Returns the normals in their dtype on their device; with return_info a tuple (normals, info),
+    info a dict of flip [n] bool, label [n] int32 (the smallest index of the point's component), tree [t, 2] int64 (the
+    forest's edges (lo, hi), sorted) and n_components.
+
+    The limit: a wall thinner than the neighbourhood radius joins its two sides by edges of weight near 0 (antiparallel
+    normals have |dot| = 1) and is oriented wrongly.  Keep k small (the default 12) on thin-walled objects."""
+    if component_sign not in COMPONENT_SIGNS:
+        raise ValueError(f"unknown component_sign {component_sign!r}: expected one of {sorted(COMPONENT_SIGNS)}")
+    shape = tuple(np.shape(points))
+    if len(shape) != 2 or shape[1] != 3 or shape[0] == 0:
+        raise ValueError(f"points must be [n, 3] with n >= 1; got {shape}")
+    if shape[0] > 2 ** 30:
+        raise ValueError("points has more than 2^30 points")
+    if tuple(np.shape(normals)) != shape:
+        raise ValueError(f"normals must have the points' shape {shape}; got {tuple(np.shape(normals))}")
+    n = shape[0]
+    if neighbors is None:
+        k = _at_least("k", k, 1)
+        if k > ORIENT_MAX_K:
+            raise ValueError(f"k must be in [1, {ORIENT_MAX_K}]; got {k}")
+    else:
+        nshape = tuple(np.shape(neighbors))
+        if len(nshape) != 2 or nshape[0] != n or not 1 <= nshape[1] <= ORIENT_MAX_K:
+            raise ValueError(f"neighbors must be [{n}, 1 .. {ORIENT_MAX_K}]; got {nshape}")
+        dt = neighbors.dtype if isinstance(neighbors, torch.Tensor) else np.asarray(neighbors).dtype
+        if dt != (torch.int32 if isinstance(neighbors, torch.Tensor) else np.int32):
+            raise ValueError(f"neighbors must be int32; got {dt}")
+    c = None
+    if center is not None:
+        c = np.asarray(center.detach().cpu() if isinstance(center, torch.Tensor) else center, dtype=np.float64)
+        if tuple(c.shape) != (3,):
+            raise ValueError(f"center must be [3]; got {tuple(c.shape)}")
+        if not np.isfinite(c).all():
+            raise ValueError("center must be finite")
+        c = (ctypes.c_double * 3)(*c.tolist())
+    _check_finite("points", points)
+    _check_finite("normals", normals)
+    given = normals.detach() if isinstance(normals, torch.Tensor) else torch.as_tensor(np.asarray(normals))
+    dev = _device(points, normals, neighbors)
+    P = _points("points", points, dev)
+    N = _points("normals", given, dev)
+    if neighbors is None:
+        nb = knn_mean_distance(P, min(k + 1, 32), return_neighbors=True)[1]
+    else:
+        nb = (neighbors.detach() if isinstance(neighbors, torch.Tensor) else torch.as_tensor(np.asarray(neighbors))).to(dev).contiguous()
+        if int(nb.max()) >= n:
+            raise ValueError(f"neighbors holds an index >= n = {n}")
+    kk = nb.shape[1]
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    flip = label = tree = None
+    if return_info or out.dtype != given.dtype or given.device != dev:
+        flip = torch.empty(n, dtype=torch.uint8, device=dev)
+    if return_info:
+        label = torch.empty(n, dtype=torch.int32, device=dev)
+        tree = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        size = _C.lib().scorp_cloud_orient_workspace_bytes(n, kk)
+        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
+        _C.call("scorp_cloud_orient_normals", P, N, nb, n, kk, c, COMPONENT_SIGNS[component_sign], out, flip, label, tree, counts,
+                workspace, size)
+    if given.dtype != torch.float32 or given.device != dev:   # the caller's dtype and device: a negation is exact in every float type
+        out = torch.where(flip.to(given.device).bool()[:, None], -given, given)
+    if not return_info:
+        return out
+    edges = tree[tree[:, 0] >= 0].to(torch.int64).cpu().numpy()
+    edges = edges[np.lexsort((edges[:, 1], edges[:, 0]))]
+    n_components, n_edges = (int(v) for v in counts.cpu())
+    if not len(edges) == n_edges == n - n_components:
+        raise RuntimeError(f"scorp_cloud_orient_normals: {len(edges)} tree rows, counts {n_components} components / {n_edges} edges of {n} points")
+    return out, {"flip": flip.bool(), "label": label, "tree": torch.from_numpy(edges), "n_components": n_components}
 
 
 def compute_fpfh_feature(points, normals, radius, max_nn=64, return_neighbors=False):
@@ -238,7 +336,7 @@ def default_voxel_size(points):
 
 
 def get_FPFH_fitting_transformation(pc_xyz_original, pc_xyz_refined, threshold, *, voxel_size=None, max_iteration=400,
-                                    estimation="point_to_point", seed=0, return_icp=False):
+                                    estimation="point_to_point", seed=0, return_icp=False, orientation="away_from"):
     """The 4x4 float64 transform (refined -> original), the convention of get_ICP_fitting_transformation_best, from one
     global registration and ONE ICP run instead of a sweep over tabulated rotations.
 
@@ -247,7 +345,13 @@ def get_FPFH_fitting_transformation(pc_xyz_original, pc_xyz_refined, threshold, 
     star-shaped about its centroid); FPFH with radius 5 voxel_size and max_nn 64; RANSAC with distance 1.5 voxel_size; then
     one registration_icp from that pose at `threshold` on the full clouds, the refined one thinned by downsample_indices
     as the sweep thins it.  The 5 x and 1.5 x ratios are the customary ones of Open3D's global-registration example; they
-    are UNMEASURED on real objects.  With return_icp a tuple (transform, ICPResult of the one run)."""
+    are UNMEASURED on real objects.  With return_icp a tuple (transform, ICPResult of the one run).
+
+    orientation="tangent_plane": the normals are signed by orient_normals_consistent_tangent_plane over the first 12 columns
+    of estimate_normals' own neighbour list instead, for objects that are not star-shaped (cups, shelves).  The default
+    stays "away_from": no existing call changes its result."""
+    if orientation not in ("away_from", "tangent_plane"):
+        raise ValueError(f"unknown orientation {orientation!r}: expected 'away_from' or 'tangent_plane'")
     threshold = _positive("threshold", threshold)
     orig, ref = np.asarray(pc_xyz_original), np.asarray(pc_xyz_refined)
     for name, a in (("pc_xyz_original", orig), ("pc_xyz_refined", ref)):
@@ -260,7 +364,12 @@ def get_FPFH_fitting_transformation(pc_xyz_original, pc_xyz_refined, threshold, 
     down, feat = [], []
     for a in (ref, orig):
         P = voxel_down_sample(a, voxel)
-        N = orient_normals_away_from(P, estimate_normals(P, knn=min(30, max(3, P.shape[0]))))
+        knn = min(30, max(3, P.shape[0]))
+        if orientation == "tangent_plane":
+            N, nb = estimate_normals(P, knn=knn, return_neighbors=True)
+            N = orient_normals_consistent_tangent_plane(P, N, neighbors=nb[:, :ORIENT_ROUTE_K])
+        else:
+            N = orient_normals_away_from(P, estimate_normals(P, knn=knn))
         down.append(P)
         feat.append(compute_fpfh_feature(P, N, 5.0 * voxel, MAX_NN))
     reg = registration_ransac_based_on_feature_matching(down[0], down[1], feat[0], feat[1], 1.5 * voxel, seed=seed)
