@@ -270,6 +270,34 @@ int scorp_icp_point_to_plane(const float *source, int32_t n_source, const float 
                              double *out_transformation, double *out_fitness, double *out_inlier_rmse,
                              int32_t *out_iterations, void *workspace, size_t workspace_bytes, scorp_stream_t stream);
 
+/* ---- multi-start generalized ICP (Segal, Haehnel, Thrun 2009; what Open3D's registration_generalized_icp is used for:
+ * two independent samplings of one surface, every point with a covariance; from every init of a batch) ----
+ * Open3D could not be run where this was written: the rules below ARE the specification.
+ * Inputs, outputs, pass(T), the loop, the stop rule, the precision of the search, the determinism and the error codes are
+ * those of scorp_icp_point_to_point; inlier_rmse stays the Euclidean sqrt(sum |x - q|^2 / c).  source_covariances
+ * [n_source, 6] and target_covariances[n_target, 6] fp32 (device) are added: the upper triangle xx, xy, xz, yy, yz, zz of
+ * the covariance C_p of source point p and C_q of target point q.  They are used as given, not normalised and not
+ * regularised.  A NULL covariance pointer is SCORP_ERR_INVALID.
+ *   update:    from the c pairs (x, q, C_p, C_q) of a pass, in float64, every coordinate relative to c_t, with s as for
+ *              point-to-plane and A_T the upper-left 3x3 of the init's cumulative T as stored:
+ *                u = x - q, M = C_q + A_T C_p A_T^T (symmetric, from the six values of each covariance);
+ *                a pair enters the update only if M is finite and positive definite by Sylvester's test (M00 > 0,
+ *                M00 M11 - M01^2 > 0, det M > 0); any other pair adds nothing to A and b (it still counts in c, fitness
+ *                and inlier_rmse, as a zero normal does for point-to-plane);
+ *                W = M^-1 by cofactors over det M, J = [ -[x]x / s | I ] (3 x 6),
+ *                A = sum J^T W J, b = sum J^T W u = sum [ (x cross (W u)) / s ; W u ];
+ *              everything after that is the point-to-plane update unchanged: Jacobi on A, the minimum-norm step over the
+ *              eigenvalues above 1e-12 l_max, the identity when c = 0 or l_max = 0, omega = xi[0:3] / s, tau = xi[3:6],
+ *              R = Rz Ry Rx, composed about c_t.  With W = n n^T these are the point-to-plane sums term for term.
+ * workspace: scorp_icp_generalized_workspace_bytes (the point-to-plane workspace and the source's covariances in its
+ * sorted order), 256-byte aligned. */
+size_t scorp_icp_generalized_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init);
+int scorp_icp_generalized(const float *source, const float *source_covariances, int32_t n_source, const float *target,
+                          const float *target_covariances, int32_t n_target, const double *inits, int32_t n_init,
+                          double max_correspondence_distance, int32_t max_iteration, double relative_fitness,
+                          double relative_rmse, double *out_transformation, double *out_fitness, double *out_inlier_rmse,
+                          int32_t *out_iterations, void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+
 /* Normals of a cloud that brings none (3DGS centres).  points[n, 3] fp32, out_normals[n, 3] fp32 and the optional
  * out_neighbors[n, knn] int32 (NULL: skipped) are device pointers.  Per point:
  *   neighbours: its k = min(knn, n) exact nearest points, itself included, ordered by (d^2, index): ties go to the lower

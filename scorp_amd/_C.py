@@ -125,6 +125,7 @@ EXPORTS = [
     "scorp_mask_vote_scratch_bytes", "scorp_gs3d_mask_vote", "scorp_gs2d_mask_vote",
     "scorp_icp_workspace_bytes", "scorp_icp_point_to_point",
     "scorp_icp_point_to_plane_workspace_bytes", "scorp_icp_point_to_plane",
+    "scorp_icp_generalized_workspace_bytes", "scorp_icp_generalized",
     "scorp_estimate_normals_workspace_bytes", "scorp_estimate_normals",
     "scorp_cloud_workspace_bytes", "scorp_cloud_knn_distance", "scorp_cloud_radius_count", "scorp_cloud_dbscan",
     "scorp_cloud_fpfh_workspace_bytes", "scorp_cloud_fpfh", "scorp_feature_match_tile_rows", "scorp_feature_match_split_rows",
@@ -262,6 +263,9 @@ def lib():
     L.scorp_icp_point_to_plane_workspace_bytes.restype = sz
     L.scorp_icp_point_to_plane_workspace_bytes.argtypes = [i32, i32, i32]
     L.scorp_icp_point_to_plane.argtypes = [vp, i32, vp, vp, i32, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
+    L.scorp_icp_generalized_workspace_bytes.restype = sz
+    L.scorp_icp_generalized_workspace_bytes.argtypes = [i32, i32, i32]
+    L.scorp_icp_generalized.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, sz, vp]
     L.scorp_estimate_normals_workspace_bytes.restype = sz
     L.scorp_estimate_normals_workspace_bytes.argtypes = [i32]
     L.scorp_estimate_normals.argtypes = [vp, i32, i32, vp, vp, vp, sz, vp]

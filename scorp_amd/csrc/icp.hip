@@ -1,5 +1,5 @@
-// icp.hip — multi-start ICP (Open3D registration_icp, every init of a call in one batch) with either estimator, and the
-// normal estimation that feeds the second one when the target brings no normals.  The rules are written down in
+// icp.hip — multi-start ICP (Open3D registration_icp, every init of a call in one batch) with one of three estimators, and
+// the normal estimation that feeds the second one when the target brings no normals.  The rules are written down in
 // include/scorp_gs.h.  The reference's alignment scripts run the point-to-point form from 67 initial poses with
 // max_iteration = 400 (align_3dgs_clpe_9dof.py:42-115 get_ICP_fitting_transformation_best).
 //
@@ -7,13 +7,14 @@
 //   * the target Q in a uniform grid (cell edge from the point density, not from r), its points sorted by cell (a stable
 //     LSD radix sort on the cell id) as float4 {q - c_t (fp32), original index};
 //   * the source P sorted by a 30-bit Morton code over its own bounding box (same sort), so that the 64 queries of a wave
-//     stay neighbours under every rigid T_i and the target cells they visit are shared through L2.
+//     stay neighbours under every rigid T_i and the target cells they visit are shared through L2; the generalized
+//     estimator's source covariances are gathered into that order once, behind the shared workspace.
 // Per iteration (no host synchronisation; the host reads the active flags every kIcpPollEvery iterations), one body each
-// for both estimators (icp_pass, icp_solve) behind two thin kernels each:
-//   * icp_pass_kernel / icp_plane_pass_kernel, grid (source blocks, inits): x = T_i p in float64 (the cumulative transform
+// for every estimator (icp_pass, icp_solve) behind thin kernels:
+//   * icp_pass_kernel / icp_plane_pass_kernel / icp_generalized_pass_kernel, grid (source blocks, inits): x = T_i p in float64 (the cumulative transform
 //     on the original point), exact nearest target point q within r by an outward ring search over the grid in fp32, the
 //     chosen pair's d^2 in float64 relative to c_t, then the estimator's sums: one fixed row per block, no float atomics;
-//   * icp_solve_kernel / icp_plane_solve_kernel, one wave per init: the rows reduced in a fixed order, fitness / rmse, the
+//   * icp_solve_kernel / icp_plane_solve_kernel (the generalized estimator's too), one wave per init: the rows reduced in a fixed order, fitness / rmse, the
 //     stop rule, the estimator's update [R | tau] about c_t, composed onto T in float64.
 // The estimators differ in their sums and their update alone:
 //   * PointToPoint (TransformationEstimationPointToPoint, no scaling): 17 sums (c, sum d^2, the first and second moments
@@ -21,7 +22,10 @@
 //   * PointToPlane (TransformationEstimationPointToPlane, no robust kernel): with the normal n of q, J = [(x x n) / s ; n],
 //     rho = n . (x - q), 29 sums (c, sum d^2, the 21 of the upper triangle of J J^T, the 6 of J rho); A = V L V^T by
 //     cyclic Jacobi in float64 (A and V in LDS), the minimum-norm step over the eigenvalues above 1e-12 of the largest,
-//     R = Rz Ry Rx.
+//     R = Rz Ry Rx;
+//   * Generalized (Segal et al. 2009): with the covariances C_p, C_q of the pair, W = (C_q + A_T C_p A_T^T)^-1 by cofactors
+//     where that matrix is positive definite, J = [-[x]x / s | I], the same 29 sums (J^T W J, J^T W (x - q)) and
+//     PointToPlane's solve; W = n n^T would give PointToPlane's sums.
 // A block's row depends only on (its source range, its init's T), and the rows are reduced in a fixed order: two calls
 // give the same bits, and init j run alone gives the bits of row j of a batch.
 // scorp_estimate_normals, one thread per point: its k exact nearest neighbours by the same outward ring walk, the list of
@@ -44,12 +48,12 @@ constexpr int kNormalsMaxK = 32;
 // Row layout: [c, sum d^2, sum x (3), sum q (3), sum x_a q_b (9, a-major), pad]
 struct PointToPoint {
   static constexpr int kSums = 17, kRow = 18;
-  static constexpr bool kNormals = false;
+  static constexpr bool kNormals = false, kCovariances = false;
   static constexpr const char *kWho = "icp";
-  __device__ explicit PointToPoint(const IcpGrid *) {}
+  __device__ PointToPoint(const IcpGrid *, const double *, const float *) {}
 
   __device__ __forceinline__ void accumulate(double (&acc)[kSums], const double x[3], const double q[3], const double[3], double d2,
-                                             const float *, int) const {
+                                             const float *, int, int) const {
     acc[0] += 1.0;
     acc[1] += d2;
     acc[2] += x[0]; acc[3] += x[1]; acc[4] += x[2];
@@ -93,10 +97,10 @@ struct PointToPoint {
 // Row layout: [c, sum d^2, A_00 A_01 .. A_05 A_11 .. A_55 (21), b (6), pad]
 struct PointToPlane {
   static constexpr int kSums = 29, kRow = 30;
-  static constexpr bool kNormals = true;
+  static constexpr bool kNormals = true, kCovariances = false;
   static constexpr const char *kWho = "icp point-to-plane";
   double s;
-  __device__ explicit PointToPlane(const IcpGrid *g) : s(scale(g)) {}
+  __device__ PointToPlane(const IcpGrid *g, const double *, const float *) : s(scale(g)) {}
 
   // s: half the largest edge of the target's bounding box, 1 if that is 0 (it brings the rotational part of J to the
   // magnitude of the translational one)
@@ -107,7 +111,7 @@ struct PointToPlane {
   }
 
   __device__ __forceinline__ void accumulate(double (&acc)[kSums], const double x[3], const double[3], const double u[3], double d2,
-                                             const float *__restrict__ tn, int id) const {
+                                             const float *__restrict__ tn, int id, int) const {
     const double n0 = tn[(size_t)id * 3 + 0], n1 = tn[(size_t)id * 3 + 1], n2 = tn[(size_t)id * 3 + 2];
     double J[6];
     J[0] = (x[1] * n2 - x[2] * n1) / s;
@@ -201,12 +205,92 @@ struct PointToPlane {
   }
 };
 
+// Row layout and solve: PointToPlane's (the 21 sums of J^T W J, the 6 of J^T W u; icp_plane_solve_kernel reduces them).
+// sc: the source's covariances in the order of W.sp; the target's come by the pair's original index, as normals do.
+struct Generalized {
+  static constexpr int kSums = PointToPlane::kSums, kRow = PointToPlane::kRow;
+  static constexpr bool kNormals = true, kCovariances = true;
+  static constexpr const char *kWho = "icp generalized";
+  double s;
+  double a00, a01, a02, a10, a11, a12, a20, a21, a22;   // A_T: the rotation block of the init's T, uniform per block
+  const float *__restrict__ sc;
+  __device__ Generalized(const IcpGrid *g, const double *M, const float *source_covariances)
+      : s(PointToPlane::scale(g)), a00(M[0]), a01(M[1]), a02(M[2]), a10(M[4]), a11(M[5]), a12(M[6]), a20(M[8]), a21(M[9]),
+        a22(M[10]), sc(source_covariances) {}
+
+  static constexpr int at(int a, int b) { return 2 + a * 6 - a * (a - 1) / 2 + (b - a); }   // A_ab, a <= b, in the row
+
+  __device__ __forceinline__ void accumulate(double (&acc)[kSums], const double x[3], const double[3], const double u[3], double d2,
+                                             const float *__restrict__ tc, int id, int i) const {
+    acc[0] += 1.0;
+    acc[1] += d2;
+    double w00, w01, w02, w11, w12, w22;
+    {
+      const float *__restrict__ cp = sc + (size_t)i * 6, *__restrict__ cq = tc + (size_t)id * 6;
+      const double p0 = cp[0], p1 = cp[1], p2 = cp[2], p3 = cp[3], p4 = cp[4], p5 = cp[5];
+      // B = A_T C_p, then the upper triangle of M = C_q + B A_T^T
+      const double b00 = fma(a00, p0, fma(a01, p1, a02 * p2)), b01 = fma(a00, p1, fma(a01, p3, a02 * p4)),
+                   b02 = fma(a00, p2, fma(a01, p4, a02 * p5));
+      const double b10 = fma(a10, p0, fma(a11, p1, a12 * p2)), b11 = fma(a10, p1, fma(a11, p3, a12 * p4)),
+                   b12 = fma(a10, p2, fma(a11, p4, a12 * p5));
+      const double b20 = fma(a20, p0, fma(a21, p1, a22 * p2)), b21 = fma(a20, p1, fma(a21, p3, a22 * p4)),
+                   b22 = fma(a20, p2, fma(a21, p4, a22 * p5));
+      const double m00 = (double)cq[0] + fma(b00, a00, fma(b01, a01, b02 * a02));
+      const double m01 = (double)cq[1] + fma(b00, a10, fma(b01, a11, b02 * a12));
+      const double m02 = (double)cq[2] + fma(b00, a20, fma(b01, a21, b02 * a22));
+      const double m11 = (double)cq[3] + fma(b10, a10, fma(b11, a11, b12 * a12));
+      const double m12 = (double)cq[4] + fma(b10, a20, fma(b11, a21, b12 * a22));
+      const double m22 = (double)cq[5] + fma(b20, a20, fma(b21, a21, b22 * a22));
+      // W = M^-1 by cofactors; M must be finite and positive definite (Sylvester), or the pair adds nothing more
+      const double k00 = m11 * m22 - m12 * m12, k01 = m02 * m12 - m01 * m22, k02 = m01 * m12 - m02 * m11;
+      const double k11 = m00 * m22 - m02 * m02, k12 = m01 * m02 - m00 * m12, k22 = m00 * m11 - m01 * m01;
+      const double det = fma(m00, k00, fma(m01, k01, m02 * k02));
+      const bool finite = isfinite(m00) && isfinite(m01) && isfinite(m02) && isfinite(m11) && isfinite(m12) && isfinite(m22);
+      if (!(finite && m00 > 0.0 && k22 > 0.0 && det > 0.0)) return;
+      w00 = k00 / det; w01 = k01 / det; w02 = k02 / det; w11 = k11 / det; w12 = k12 / det; w22 = k22 / det;
+    }
+    // J = [ -[x]x / s | I ]: with y = x / s its rotational columns are g_a = e_a cross y
+    const double y0 = x[0] / s, y1 = x[1] / s, y2 = x[2] / s;
+    {  // b = J^T W u = [ y cross (W u) ; W u ]
+      const double v0 = fma(w00, u[0], fma(w01, u[1], w02 * u[2])), v1 = fma(w01, u[0], fma(w11, u[1], w12 * u[2])),
+                   v2 = fma(w02, u[0], fma(w12, u[1], w22 * u[2]));
+      acc[23] += y1 * v2 - y2 * v1;
+      acc[24] += y2 * v0 - y0 * v2;
+      acc[25] += y0 * v1 - y1 * v0;
+      acc[26] += v0; acc[27] += v1; acc[28] += v2;
+    }
+    // A = J^T W J, a column k = W g_a of W J at a time: A_ba = g_b . k for b <= a, A_a(3+c) = k_c, the last block W
+    {
+      const double k0 = y1 * w02 - y2 * w01, k1 = y1 * w12 - y2 * w11, k2 = y1 * w22 - y2 * w12;   // g_0 = (0, -y2, y1)
+      acc[at(0, 0)] += y1 * k2 - y2 * k1;
+      acc[at(0, 3)] += k0; acc[at(0, 4)] += k1; acc[at(0, 5)] += k2;
+    }
+    {
+      const double k0 = y2 * w00 - y0 * w02, k1 = y2 * w01 - y0 * w12, k2 = y2 * w02 - y0 * w22;   // g_1 = (y2, 0, -y0)
+      acc[at(0, 1)] += y1 * k2 - y2 * k1;
+      acc[at(1, 1)] += y2 * k0 - y0 * k2;
+      acc[at(1, 3)] += k0; acc[at(1, 4)] += k1; acc[at(1, 5)] += k2;
+    }
+    {
+      const double k0 = y0 * w01 - y1 * w00, k1 = y0 * w11 - y1 * w01, k2 = y0 * w12 - y1 * w02;   // g_2 = (-y1, y0, 0)
+      acc[at(0, 2)] += y1 * k2 - y2 * k1;
+      acc[at(1, 2)] += y2 * k0 - y0 * k2;
+      acc[at(2, 2)] += y0 * k1 - y1 * k0;
+      acc[at(2, 3)] += k0; acc[at(2, 4)] += k1; acc[at(2, 5)] += k2;
+    }
+    acc[at(3, 3)] += w00; acc[at(3, 4)] += w01; acc[at(3, 5)] += w02;
+    acc[at(4, 4)] += w11; acc[at(4, 5)] += w12;
+    acc[at(5, 5)] += w22;
+  }
+};
+
 // ---- the correspondence pass ----
 
-// grid (source blocks, inits); tn: the target's normals where Est::kNormals
+// grid (source blocks, inits); tn: the target's normals or covariances where Est::kNormals; sc: the source's covariances
+// in sp's order where Est::kCovariances
 template <class Est>
-__device__ __forceinline__ void icp_pass(const float4 *__restrict__ sp, int ns, const float4 *__restrict__ tq,
-                                         const float *__restrict__ tgt, const float *__restrict__ tn,
+__device__ __forceinline__ void icp_pass(const float4 *__restrict__ sp, const float *__restrict__ sc, int ns,
+                                         const float4 *__restrict__ tq, const float *__restrict__ tgt, const float *__restrict__ tn,
                                          const uint32_t *__restrict__ cell_start, const IcpGrid *__restrict__ g,
                                          const double *__restrict__ T, const int32_t *__restrict__ active, double r2, float r2f,
                                          double *__restrict__ rows) {
@@ -217,7 +301,7 @@ __device__ __forceinline__ void icp_pass(const float4 *__restrict__ sp, int ns, 
   const double m10 = M[4], m11 = M[5], m12 = M[6], m13 = M[7] - g->ct[1];
   const double m20 = M[8], m21 = M[9], m22 = M[10], m23 = M[11] - g->ct[2];
   const double c0 = g->ct[0], c1 = g->ct[1], c2 = g->ct[2];
-  const Est est(g);
+  const Est est(g, M, sc);
   double acc[Est::kSums];
 #pragma unroll
   for (int a = 0; a < Est::kSums; a++) acc[a] = 0.0;
@@ -237,7 +321,7 @@ __device__ __forceinline__ void icp_pass(const float4 *__restrict__ sp, int ns, 
     const double u[3] = {x[0] - q[0], x[1] - q[1], x[2] - q[2]};
     const double d2 = fma(u[0], u[0], fma(u[1], u[1], u[2] * u[2]));
     if (!(d2 <= r2)) continue;
-    est.accumulate(acc, x, q, u, d2, tn, id);
+    est.accumulate(acc, x, q, u, d2, tn, id, i);
   }
   __shared__ double part[kIcpThreads / 64][Est::kSums];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -259,7 +343,7 @@ __global__ void __launch_bounds__(kIcpThreads) icp_pass_kernel(const float4 *__r
                                                                const IcpGrid *__restrict__ g, const double *__restrict__ T,
                                                                const int32_t *__restrict__ active, double r2, float r2f,
                                                                double *__restrict__ rows) {
-  icp_pass<PointToPoint>(sp, ns, tq, tgt, nullptr, cell_start, g, T, active, r2, r2f, rows);
+  icp_pass<PointToPoint>(sp, nullptr, ns, tq, tgt, nullptr, cell_start, g, T, active, r2, r2f, rows);
 }
 
 __global__ void __launch_bounds__(kIcpThreads) icp_plane_pass_kernel(const float4 *__restrict__ sp, int ns, const float4 *__restrict__ tq,
@@ -268,7 +352,23 @@ __global__ void __launch_bounds__(kIcpThreads) icp_plane_pass_kernel(const float
                                                                      const IcpGrid *__restrict__ g, const double *__restrict__ T,
                                                                      const int32_t *__restrict__ active, double r2, float r2f,
                                                                      double *__restrict__ rows) {
-  icp_pass<PointToPlane>(sp, ns, tq, tgt, tn, cell_start, g, T, active, r2, r2f, rows);
+  icp_pass<PointToPlane>(sp, nullptr, ns, tq, tgt, tn, cell_start, g, T, active, r2, r2f, rows);
+}
+
+__global__ void __launch_bounds__(kIcpThreads) icp_generalized_pass_kernel(
+    const float4 *__restrict__ sp, const float *__restrict__ sc, int ns, const float4 *__restrict__ tq, const float *__restrict__ tgt,
+    const float *__restrict__ tc, const uint32_t *__restrict__ cell_start, const IcpGrid *__restrict__ g, const double *__restrict__ T,
+    const int32_t *__restrict__ active, double r2, float r2f, double *__restrict__ rows) {
+  icp_pass<Generalized>(sp, sc, ns, tq, tgt, tc, cell_start, g, T, active, r2, r2f, rows);
+}
+
+// the source's covariances [ns, 6] in the Morton order of W.sp
+__global__ void __launch_bounds__(256) icp_gather_covariances_kernel(const float *__restrict__ cov, const uint32_t *__restrict__ order,
+                                                                     int ns, float *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns) return;
+  const float *c = cov + (size_t)order[i] * 6;
+  for (int e = 0; e < 6; e++) out[(size_t)i * 6 + e] = c[e];
 }
 
 // ---- the solve ----
@@ -417,18 +517,32 @@ __global__ void __launch_bounds__(kNormalsThreads) icp_normals_kernel(const floa
 
 // ---- host ----
 
+// what a Generalized call needs after IcpLayout::total: the source's covariances in sorted order
+size_t icp_sorted_covariances_bytes(int64_t ns) { return align_up((size_t)(ns > 0 ? ns : 1) * 6 * 4, 256); }
+
+// normals: the target's per-point attribute where Est::kNormals (normals, or covariances); source_covariances where
+// Est::kCovariances
 template <class Est>
-int icp_run(const float *source, int32_t ns, const float *target, const float *normals, int32_t nt, const double *inits, int32_t ni,
+int icp_run(const float *source, const float *source_covariances, int32_t ns, const float *target, const float *normals, int32_t nt,
+            const double *inits, int32_t ni,
             double r, int32_t max_iteration, double rel_fitness, double rel_rmse, double *out_T, double *out_fitness,
             double *out_rmse, int32_t *out_iters, void *workspace, size_t workspace_bytes, hipStream_t stream) {
   if (int e = icp_check_args(Est::kWho, r, ns, nt, max_iteration, ni,
-                             source && target && (normals || !Est::kNormals) && inits && out_T && out_fitness && out_rmse && out_iters))
+                             source && target && (normals || !Est::kNormals) && (source_covariances || !Est::kCovariances) && inits && out_T && out_fitness && out_rmse && out_iters))
     return e;
   const IcpLayout L(ns, nt, ni, Est::kRow);
-  if (int e = check_workspace(Est::kWho, workspace, workspace_bytes, L.total)) return e;
+  if (int e = check_workspace(Est::kWho, workspace, workspace_bytes,
+                              L.total + (Est::kCovariances ? icp_sorted_covariances_bytes(ns) : 0)))
+    return e;
   const IcpWorkspace W(workspace, L);
   if (int e = icp_build_target(target, nt, L, W, stream)) return e;
-  if (int e = icp_build_source(source, ns, L, W, stream)) return e;
+  const uint32_t *order;
+  if (int e = icp_build_source(source, ns, L, W, stream, &order)) return e;
+  float *sc = (float *)((char *)workspace + L.total);
+  if constexpr (Est::kCovariances) {
+    icp_gather_covariances_kernel<<<(ns + 255) / 256, 256, 0, stream>>>(source_covariances, order, ns, sc);
+    SCORP_KERNEL_CHECK("icp_gather_covariances", 0, stream);
+  }
   icp_init_kernel<<<(ni + 63) / 64, 64, 0, stream>>>(inits, ni, out_T, out_fitness, out_rmse, out_iters, W.active);
   SCORP_KERNEL_CHECK("icp_init", 0, stream);
 
@@ -437,7 +551,10 @@ int icp_run(const float *source, int32_t ns, const float *target, const float *n
   const float r2f = (float)r2 * (1.0f + 1e-5f);   // the fp32 search keeps slightly more; the pair test is float64
   return icp_iterate(ni, max_iteration, W.active, stream, [&](int k) -> int {
     const dim3 grid(nblk, ni);
-    if constexpr (Est::kNormals)
+    if constexpr (Est::kCovariances)
+      icp_generalized_pass_kernel<<<grid, kIcpThreads, 0, stream>>>(W.sp, sc, ns, W.tq, target, normals, W.cell_start, W.g, out_T,
+                                                                    W.active, r2, r2f, W.rows);
+    else if constexpr (Est::kNormals)
       icp_plane_pass_kernel<<<grid, kIcpThreads, 0, stream>>>(W.sp, ns, W.tq, target, normals, W.cell_start, W.g, out_T, W.active, r2,
                                                               r2f, W.rows);
     else
@@ -482,7 +599,7 @@ extern "C" int scorp_icp_point_to_point(const float *source, int32_t n_source, c
                                         double *out_transformation, double *out_fitness, double *out_inlier_rmse,
                                         int32_t *out_iterations, void *workspace, size_t workspace_bytes,
                                         scorp_stream_t stream) {
-  return icp_run<PointToPoint>(source, n_source, target, nullptr, n_target, inits, n_init, max_correspondence_distance, max_iteration,
+  return icp_run<PointToPoint>(source, nullptr, n_source, target, nullptr, n_target, inits, n_init, max_correspondence_distance, max_iteration,
                                relative_fitness, relative_rmse, out_transformation, out_fitness, out_inlier_rmse, out_iterations,
                                workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -497,9 +614,23 @@ extern "C" int scorp_icp_point_to_plane(const float *source, int32_t n_source, c
                                         double relative_rmse, double *out_transformation, double *out_fitness,
                                         double *out_inlier_rmse, int32_t *out_iterations, void *workspace,
                                         size_t workspace_bytes, scorp_stream_t stream) {
-  return icp_run<PointToPlane>(source, n_source, target, target_normals, n_target, inits, n_init, max_correspondence_distance,
+  return icp_run<PointToPlane>(source, nullptr, n_source, target, target_normals, n_target, inits, n_init, max_correspondence_distance,
                                max_iteration, relative_fitness, relative_rmse, out_transformation, out_fitness, out_inlier_rmse,
                                out_iterations, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t scorp_icp_generalized_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init) {
+  return IcpLayout(n_source, n_target, n_init, Generalized::kRow).total + icp_sorted_covariances_bytes(n_source);
+}
+
+extern "C" int scorp_icp_generalized(const float *source, const float *source_covariances, int32_t n_source, const float *target,
+                                     const float *target_covariances, int32_t n_target, const double *inits, int32_t n_init,
+                                     double max_correspondence_distance, int32_t max_iteration, double relative_fitness,
+                                     double relative_rmse, double *out_transformation, double *out_fitness, double *out_inlier_rmse,
+                                     int32_t *out_iterations, void *workspace, size_t workspace_bytes, scorp_stream_t stream) {
+  return icp_run<Generalized>(source, source_covariances, n_source, target, target_covariances, n_target, inits, n_init,
+                              max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, out_transformation,
+                              out_fitness, out_inlier_rmse, out_iterations, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" size_t scorp_estimate_normals_workspace_bytes(int32_t n) { return IcpLayout(0, n, 0, PointToPlane::kRow).total; }

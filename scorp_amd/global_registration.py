@@ -346,6 +346,7 @@ def get_FPFH_fitting_transformation(pc_xyz_original, pc_xyz_refined, threshold, 
     one registration_icp from that pose at `threshold` on the full clouds, the refined one thinned by downsample_indices
     as the sweep thins it.  The 5 x and 1.5 x ratios are the customary ones of Open3D's global-registration example; they
     are UNMEASURED on real objects.  With return_icp a tuple (transform, ICPResult of the one run).
+    estimation="generalized" refines with generalized ICP on estimate_covariances of the two clouds that run registers.
 
     orientation="tangent_plane": the normals are signed by orient_normals_consistent_tangent_plane over the first 12 columns
     of estimate_normals' own neighbour list instead, for objects that are not star-shaped (cups, shelves).  The default

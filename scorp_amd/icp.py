@@ -1,11 +1,14 @@
-"""Multi-start ICP on the GPU, point-to-point or point-to-plane: the alignment scripts' get_ICP_fitting_transformation_best
-(align_3dgs_clpe_9dof.py:42-115, align_2dgs_clpe_9dof.py:48-121) without Open3D.
+"""Multi-start ICP on the GPU, point-to-point, point-to-plane or generalized: the alignment scripts'
+get_ICP_fitting_transformation_best (align_3dgs_clpe_9dof.py:42-115, align_2dgs_clpe_9dof.py:48-121) without Open3D.
 
 The reference runs Open3D's registration_icp (TransformationEstimationPointToPoint, no scaling, max_iteration=400) once
 per initial pose, 67 poses by default.  Here every init runs in one batch through scorp_icp_point_to_point
 (csrc/icp.hip): one launch per iteration covers all inits still running.  estimation="point_to_plane" runs the same
 batch through scorp_icp_point_to_plane (the same file, the other estimator) on the target's normals:
-model_normals(gaussians) for a trained model, estimate_normals(points) for a bare cloud.  Swap it in with one import:
+model_normals(gaussians) for a trained model, estimate_normals(points) for a bare cloud.  estimation="generalized" runs
+it through scorp_icp_generalized on a covariance per point of both clouds (Segal et al. 2009; the estimator for two
+independent samplings of one surface): model_covariances(gaussians) for a trained model, estimate_covariances(points) for
+a bare cloud.  Swap it in with one import:
 
     from scorp_amd.icp import get_ICP_fitting_transformation_best
 """
@@ -61,7 +64,7 @@ def _device(*arrays):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-ESTIMATIONS = ("point_to_point", "point_to_plane")
+ESTIMATIONS = ("point_to_point", "point_to_plane", "generalized")
 
 
 def _check_estimation(estimation):
@@ -105,13 +108,78 @@ def model_normals(gaussians):
         return torch.gather(R, 2, axis[:, None, None].expand(-1, 3, 1))[:, :, 0].contiguous()
 
 
+_TRIU = ([0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2])   # (row, column) of the six packed values
+
+
+def covariances_from_normals(normals, epsilon=1e-3):
+    """Covariances [n, 6] fp32 (xx, xy, xz, yy, yz, zz) from normals [n, 3], Open3D's rule for generalized ICP: unit
+    variance in the tangent plane and `epsilon` along the normal, I - (1 - epsilon) n n^T, computed in float64 and then
+    rounded.  The normals are used as given; a zero normal gives I.  Plain torch, on the normals' device."""
+    n = normals if isinstance(normals, torch.Tensor) else torch.as_tensor(np.array(normals))
+    if n.ndim != 2 or n.shape[1] != 3:
+        raise ValueError(f"normals must be [n, 3]; got {tuple(n.shape)}")
+    n = n.to(torch.float64)
+    f = 1.0 - float(epsilon)
+    ia, ib = _TRIU
+    C = -f * n[:, ia] * n[:, ib]
+    C[:, [0, 3, 5]] += 1.0
+    return C.to(torch.float32).contiguous()
+
+
+def estimate_covariances(points, knn=30, epsilon=1e-3):
+    """covariances_from_normals(estimate_normals(points, knn), epsilon): the covariances of a bare cloud, [n, 6] fp32 on
+    the device."""
+    return covariances_from_normals(estimate_normals(points, knn=knn), epsilon)
+
+
+def model_covariances(gaussians, mode="plane", epsilon=1e-3):
+    """Per-Gaussian covariances [N, 6] fp32 of a trained model, for source_covariances / target_covariances.
+    mode="plane": covariances_from_normals(model_normals(gaussians), epsilon).  mode="full": the Gaussian's own
+    R diag(sigma^2) R^T of its activated scales; a surfel's missing third variance, and any variance below epsilon times
+    that Gaussian's largest, is raised to epsilon times the largest, so that no covariance has a condition number above
+    1 / epsilon.  Plain torch, once per object."""
+    if mode not in ("plane", "full"):
+        raise ValueError(f"unknown mode {mode!r}: expected 'plane' or 'full'")
+    if mode == "plane":
+        return covariances_from_normals(model_normals(gaussians), epsilon)
+    from .gaussian_model import build_rotation
+    with torch.no_grad():
+        R = build_rotation(gaussians._rotation).to(torch.float64)
+        var = gaussians.get_scaling.to(torch.float64) ** 2
+        if var.shape[1] == 2:
+            var = torch.cat([var, torch.zeros_like(var[:, :1])], dim=1)
+        var = torch.maximum(var, float(epsilon) * var.max(dim=1, keepdim=True).values)
+        C = (R * var[:, None, :]) @ R.transpose(1, 2)
+        ia, ib = _TRIU
+        return (0.5 * (C[:, ia, ib] + C[:, ib, ia])).to(torch.float32).contiguous()
+
+
+def _covariances(name, a, n, device):
+    """A covariance argument, [n, 6] or [n, 3, 3] (numpy or torch), as [n, 6] fp32 on the device."""
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.array(a))
+    shape = tuple(t.shape)
+    if shape not in ((n, 6), (n, 3, 3)):
+        raise ValueError(f"{name} must be [{n}, 6] or [{n}, 3, 3]; got {shape}")
+    _check_finite(name, t)
+    if t.ndim == 3:
+        big = t.abs().amax(dim=(1, 2))
+        if bool(((t - t.transpose(1, 2)).abs().amax(dim=(1, 2)) > 1e-6 * big).any()):
+            raise ValueError(f"{name} holds a 3x3 that is not symmetric")
+        ia, ib = _TRIU
+        t = t[:, ia, ib]
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
 def registration_icp(source, target, max_correspondence_distance, inits, max_iteration=30, relative_fitness=1e-6,
-                     relative_rmse=1e-6, estimation="point_to_point", target_normals=None):
+                     relative_rmse=1e-6, estimation="point_to_point", target_normals=None, source_covariances=None,
+                     target_covariances=None):
     """Open3D's registration_icp(source, target, r, init, TransformationEstimationPointToPoint(),
     ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)) from every init of `inits` ([4, 4] or
     [n_init, 4, 4]) at once.  source [n, 3] and target [m, 3]: numpy arrays or torch tensors (searched in fp32; pair
     distances, moments and transforms in float64).  estimation="point_to_plane" is TransformationEstimationPointToPlane
     (no robust kernel) on target_normals [m, 3]; without them the normals are estimate_normals(target, knn=30).
+    estimation="generalized" is generalized ICP (the rules of include/scorp_gs.h) on source_covariances and
+    target_covariances, each [n, 6] (xx, xy, xz, yy, yz, zz) or [n, 3, 3]; one left out is estimate_covariances(cloud).
     Returns an ICPResult of numpy arrays."""
     _check_estimation(estimation)
     r = float(max_correspondence_distance)
@@ -122,6 +190,7 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     _check_finite("source", source)
     _check_finite("target", target)
     plane = estimation == "point_to_plane"
+    gicp = estimation == "generalized"
     if plane and target_normals is not None:
         if tuple(np.shape(target_normals)) != tuple(np.shape(target)):
             raise ValueError(f"target_normals must have the target's shape {tuple(np.shape(target))}; "
@@ -140,7 +209,13 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     L = _C.lib()
     if plane:
         Nq = estimate_normals(Q, knn=30) if target_normals is None else _points("target_normals", target_normals, dev)
-    size = (L.scorp_icp_point_to_plane_workspace_bytes if plane else L.scorp_icp_workspace_bytes)(P.shape[0], Q.shape[0], ni)
+    if gicp:
+        Cp = (estimate_covariances(P) if source_covariances is None
+              else _covariances("source_covariances", source_covariances, P.shape[0], dev))
+        Cq = (estimate_covariances(Q) if target_covariances is None
+              else _covariances("target_covariances", target_covariances, Q.shape[0], dev))
+    size = (L.scorp_icp_generalized_workspace_bytes if gicp else L.scorp_icp_point_to_plane_workspace_bytes if plane
+            else L.scorp_icp_workspace_bytes)(P.shape[0], Q.shape[0], ni)
     T_in = torch.as_tensor(np.ascontiguousarray(T0), device=dev)
     T_out = torch.empty_like(T_in)
     fit = torch.empty(ni, dtype=torch.float64, device=dev)
@@ -148,8 +223,9 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     iters = torch.empty(ni, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-        _C.call("scorp_icp_point_to_plane" if plane else "scorp_icp_point_to_point", P, P.shape[0], Q, *((Nq,) if plane else ()),
-                Q.shape[0], T_in, ni, r, int(max_iteration), float(relative_fitness), float(relative_rmse), T_out, fit, rmse, iters,
+        name = "scorp_icp_generalized" if gicp else "scorp_icp_point_to_plane" if plane else "scorp_icp_point_to_point"
+        _C.call(name, P, *((Cp,) if gicp else ()), P.shape[0], Q, *((Cq,) if gicp else (Nq,) if plane else ()), Q.shape[0],
+                T_in, ni, r, int(max_iteration), float(relative_fitness), float(relative_rmse), T_out, fit, rmse, iters,
                 workspace, size)
     return ICPResult(T_out.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy())
 
@@ -178,11 +254,14 @@ def icp_inits(rotations, center_original, center_refined):
 
 def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refined: np.ndarray, rotations: np.ndarray,
                                         threshold: float, *, estimation="point_to_point", target_normals=None,
-                                        max_iteration=400) -> np.ndarray:
+                                        max_iteration=400, source_covariances=None, target_covariances=None) -> np.ndarray:
     """The reference's function of the same name, statement for statement, with every ICP run on the GPU in one batch:
     the 4x4 float64 transform (refined -> original) of the FIRST init with the highest fitness.  The keyword-only
     arguments are this project's: estimation="point_to_plane" with target_normals [len(pc_xyz_original), 3] (a surfel
-    model's come from model_normals; None estimates them from the cloud) normally needs far fewer updates."""
+    model's come from model_normals; None estimates them from the cloud) normally needs far fewer updates;
+    estimation="generalized" with source_covariances for pc_xyz_refined (subsampled here with its points) and
+    target_covariances for pc_xyz_original (a trained model's come from model_covariances; None estimates them from the
+    cloud that is registered) weighs every pair by both."""
     _check_estimation(estimation)
     if np.any(np.isnan(pc_xyz_original)) or np.any(np.isnan(pc_xyz_refined)):
         raise ValueError("Point clouds contain NaN values")
@@ -192,9 +271,16 @@ def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refi
     ref = np.asarray(pc_xyz_refined)
     center_original = orig.mean(axis=0)   # get_centroid(., method="mean"), in the clouds' own dtype as there
     center_refined = ref.mean(axis=0)
-    src = ref[downsample_indices(len(orig), len(ref))]
+    keep = downsample_indices(len(orig), len(ref))
+    src = ref[keep]
+    if estimation == "generalized" and source_covariances is not None:
+        if len(source_covariances) != len(ref):
+            raise ValueError(f"source_covariances must have one entry per point of pc_xyz_refined ({len(ref)}); "
+                             f"got {len(source_covariances)}")
+        source_covariances = source_covariances[keep]
     inits = icp_inits(rotations, center_original, center_refined)
     res = registration_icp(src, orig, threshold, inits, max_iteration=max_iteration, estimation=estimation,
-                           target_normals=target_normals)
+                           target_normals=target_normals, source_covariances=source_covariances,
+                           target_covariances=target_covariances)
     best = int(np.argmax(res.fitness))   # the first maximum: the reference keeps a pose only on a strictly higher fitness
     return res.transformation[best].copy()

@@ -3,10 +3,18 @@
 threshold).  Prints one JSON line: total ms per call (median of --reps after a warm-up call), iterations per init, and
 the 16-thread scipy cKDTree correspondence pass of the yardstick on the same machine.  --estimation point_to_plane runs
 the same fixture through scorp_icp_point_to_plane on normals estimated from the target (knn 30), and times that
-estimation too.  The per-pass kernel time comes from a run under `rocprofv3 --kernel-trace` (icp_pass_kernel /
-icp_solve_kernel, icp_plane_pass_kernel / icp_plane_solve_kernel, the four thin kernels of csrc/icp.hip around its one
-pass body and one solve body: the first launch has every init active, the last ones a single init)."""
+estimation too.  --estimation generalized runs it through scorp_icp_generalized on covariances estimated from both
+clouds (estimate_covariances: normals at knn 30, then the epsilon rule), timed apart in the same way.  The per-pass kernel
+time comes from a run under `rocprofv3 --kernel-trace` (icp_pass_kernel / icp_solve_kernel, icp_plane_pass_kernel /
+icp_plane_solve_kernel, icp_generalized_pass_kernel with the plane solve: the thin kernels of csrc/icp.hip around its one
+pass body and one solve body: the first launch has every init active, the last ones a single init):
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python scripts/time_icp.py --estimation E --reps 1 --scipy-passes 0
+    python scripts/time_icp.py --estimation E --kernel-stats <dir>/.../*_kernel_stats.csv
+
+The second command folds the pass, solve and set-up kernels of that run into one JSON line."""
 import argparse
+import csv
 import json
 import os
 import sys
@@ -18,6 +26,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def fold_kernel_stats(path):
+    """{kernel: calls, total ms, mean / min / max microseconds} of the ICP kernels in a rocprofv3 kernel-stats CSV"""
+    out = {}
+    for r in csv.DictReader(open(path)):
+        name = r.get("Name") or r.get("KernelName") or ""
+        for frag in ("icp_pass_kernel", "icp_plane_pass_kernel", "icp_generalized_pass_kernel", "icp_solve_kernel",
+                     "icp_plane_solve_kernel", "icp_normals_kernel", "icp_gather_covariances_kernel"):
+            if frag in name:
+                out[frag] = {"calls": int(r.get("Calls") or 0), "total_ms": float(r.get("TotalDurationNs") or 0.0) / 1e6,
+                             "mean_us": float(r.get("AverageNs") or 0.0) / 1e3, "min_us": float(r.get("MinNs") or 0.0) / 1e3,
+                             "max_us": float(r.get("MaxNs") or 0.0) / 1e3}
+    if not out:
+        raise SystemExit(f"no ICP kernel in {path}")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--target", type=int, default=100_000)
@@ -25,8 +49,13 @@ def main():
     ap.add_argument("--max-iteration", type=int, default=400)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--scipy-passes", type=int, default=5, help="yardstick passes to time (0: skip)")
-    ap.add_argument("--estimation", choices=["point_to_point", "point_to_plane"], default="point_to_point")
+    ap.add_argument("--estimation", choices=["point_to_point", "point_to_plane", "generalized"], default="point_to_point")
+    ap.add_argument("--kernel-stats", help="fold a rocprofv3 kernel-stats CSV of a run of this script into one line and exit")
     a = ap.parse_args()
+    if a.kernel_stats:
+        print(json.dumps({"estimation": a.estimation, "source": "rocprofv3 --kernel-trace --stats", "reps": a.reps,
+                          "kernels": fold_kernel_stats(a.kernel_stats)}))
+        return
     import torch
     from scipy.spatial import cKDTree
     from scorp_amd import icp
@@ -55,6 +84,18 @@ def main():
             ts.append((time.perf_counter() - t0) * 1e3)
         normals_ms = float(np.median(ts))
         kw = {"estimation": "point_to_plane", "target_normals": N}
+    covariances_ms = None
+    if a.estimation == "generalized":
+        icp.estimate_covariances(Q)   # warm-up
+        ts = []
+        for _ in range(a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            Cp, Cq = icp.estimate_covariances(S), icp.estimate_covariances(Q)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        covariances_ms = float(np.median(ts))
+        kw = {"estimation": "generalized", "source_covariances": Cp, "target_covariances": Cq}
     res = icp.registration_icp(S, Q, r, inits, max_iteration=a.max_iteration, **kw)   # warm-up
     times = []
     for _ in range(a.reps):
@@ -72,6 +113,8 @@ def main():
            "best_rmse": float(res.inlier_rmse[int(np.argmax(res.fitness))])}
     if normals_ms is not None:
         out["estimate_normals_ms_knn30"] = normals_ms
+    if covariances_ms is not None:
+        out["estimate_covariances_ms_both_clouds_knn30"] = covariances_ms
     if a.scipy_passes > 0:
         tree = cKDTree(tgt.astype(np.float64))
         src64 = src.astype(np.float64)
