@@ -397,3 +397,15 @@ def call(name, *args):
     import torch
     check(getattr(lib(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
                                  for a in args], current_stream_ptr()), name)
+
+
+def call_with_workspace(name, size_name, size_args, *args):
+    """call(name, *args, workspace, size) for the entry points that take a one-call workspace as their last two arguments:
+    size = lib().<size_name>(*size_args) bytes, allocated as a uint8 tensor on the device of the first tensor of args, under
+    that device's guard."""
+    import torch
+    dev = next(a.device for a in args if isinstance(a, torch.Tensor))
+    with torch.cuda.device(dev):
+        size = getattr(lib(), size_name)(*size_args)
+        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
+        call(name, *args, workspace, size)

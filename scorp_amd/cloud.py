@@ -17,40 +17,15 @@ import numpy as np
 import torch
 
 from . import _C
-from .icp import _check_finite, _check_shape, _device, _points
+from ._points import _at_least, _cloud, _positive
 
 MAX_KNN = 32
 METHODS = ("dbscan", "statistical", "radius")
 
 
-def _positive(name, v):
-    v = float(v)
-    if not (v > 0.0 and np.isfinite(v)):
-        raise ValueError(f"{name} must be positive and finite; got {v}")
-    return v
-
-
-def _at_least(name, v, least):
-    if int(v) != v or int(v) < least:
-        raise ValueError(f"{name} must be an integer >= {least}; got {v}")
-    return int(v)
-
-
-def _cloud(points):
-    """The checked cloud as a contiguous fp32 device tensor."""
-    _check_shape("points", points)
-    if np.shape(points)[0] > 2 ** 30:
-        raise ValueError("points has more than 2^30 points")
-    _check_finite("points", points)
-    return _points("points", points, _device(points))
-
-
 def _call(name, P, *args):
-    n, dev = P.shape[0], P.device
-    with torch.cuda.device(dev):
-        size = _C.lib().scorp_cloud_workspace_bytes(n)
-        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-        _C.call(name, P, n, *args, workspace, size)
+    n = P.shape[0]
+    _C.call_with_workspace(name, "scorp_cloud_workspace_bytes", (n,), P, n, *args)
 
 
 def knn_mean_distance(points, nb_neighbors=20, return_neighbors=False):

@@ -5,9 +5,11 @@
 //
 // Every kernel below has one thread per point, in cell order (thread t takes sorted point t, so a wave's queries are
 // neighbours), and walks the rings of cells around the point's own cell:
-//   knn      the k best (float64 d^2, index) so far sit sorted in the lane's column of two LDS arrays, as in
-//            icp_normals_kernel (a runtime-indexed per-thread array would go to scratch).  The arrays are sized by k at the
-//            launch: 768 k bytes per workgroup of 64 lanes, 15 KB at k = 20 and 24 KB at k = 32.
+//   knn      the k best (float64 d^2, index) so far sit sorted in the lane's column of two LDS arrays (a runtime-indexed
+//            per-thread array would go to scratch).  The arrays are sized by k at the launch: 768 k bytes per workgroup
+//            of 64 lanes, 15 KB at k = 20 and 24 KB at k = 32.  The list is icp_search.hpp's KBest WRITTEN OUT, statement
+//            for statement: with its three counters members of a struct this kernel (alone of the three that keep such
+//            a list) compiled to other code and ran 1 % slower, so it keeps them as locals.  Change the two together.
 //   count    |N_r(i)|, and for DBSCAN the core flag and parent[i] = i.
 //   link     every core point unites itself with its core neighbours of lower index.
 //   roots    root and "is a root" per core point once every hook has landed; icp_scan_kernel numbers the roots.
@@ -52,12 +54,11 @@ __global__ void __launch_bounds__(kCloudKnnThreads) cloud_knn_kernel(const float
   double kth = __builtin_inf();   // d^2 of the k-th best once the list is full
   uint32_t kth_id = 0xFFFFFFFFu;
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) {
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) {
       const float4 q = tp[t];
       const double d2 = cloud_d2(me, q);
       const uint32_t id = __float_as_uint(q.w);
-      if (cnt == k && !(d2 < kth || (d2 == kth && id < kth_id))) continue;
+      if (cnt == k && !(d2 < kth || (d2 == kth && id < kth_id))) return;
       int pos = cnt < k ? cnt : k - 1;   // the free slot, or the last entry, which leaves
       while (pos > 0) {
         const double pd = nd[pos - 1][lane];
@@ -71,7 +72,7 @@ __global__ void __launch_bounds__(kCloudKnnThreads) cloud_knn_kernel(const float
       ni[pos][lane] = id;
       if (cnt < k) cnt++;
       if (cnt == k) { kth = nd[k - 1][lane]; kth_id = ni[k - 1][lane]; }
-    }
+    });
   };
   walk.run(visit, [&]() { return cnt == k ? walk.reach(kth) : (float)__builtin_inf(); });
   double sum = 0.0;
@@ -96,8 +97,7 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_count_kernel(const float4
   const float reach = walk.reach(r2);
   int cnt = 0;
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) cnt += cloud_d2(me, tp[t]) <= r2;
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) { cnt += cloud_d2(me, tp[t]) <= r2; });
   };
   walk.run(visit, [&]() { return reach; });
   if (out_count) out_count[self] = cnt;
@@ -120,13 +120,12 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_link_kernel(const float4 
   const CloudWalk walk(tq[i], g);
   const float reach = walk.reach(r2);
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) {
-      if (!core_sorted[t]) continue;
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) {
+      if (!core_sorted[t]) return;
       const float4 q = tp[t];
       const uint32_t id = __float_as_uint(q.w);
       if (id < self && cloud_d2(me, q) <= r2) unite(parent, (int32_t)self, (int32_t)id);
-    }
+    });
   };
   walk.run(visit, [&]() { return reach; });
 }
@@ -166,14 +165,13 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_border_kernel(const float
   double best = __builtin_inf();
   uint32_t bidx = 0xFFFFFFFFu;
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) {
-      if (!core_sorted[t]) continue;
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) {
+      if (!core_sorted[t]) return;
       const float4 q = tp[t];
       const double d2 = cloud_d2(me, q);
       const uint32_t id = __float_as_uint(q.w);
       if (d2 <= r2 && (d2 < best || (d2 == best && id < bidx))) { best = d2; bidx = id; }
-    }
+    });
   };
   walk.run(visit, [&]() { return reach; });
   out_labels[self] = bidx == 0xFFFFFFFFu ? -1 : (int32_t)number[root[bidx]];

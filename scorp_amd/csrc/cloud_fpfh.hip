@@ -5,10 +5,10 @@
 //
 // Three kernels:
 //   search   one thread per point in cell order.  The max_nn best (float64 d^2, index) within the radius, the point itself
-//            left out by index, sit sorted in the lane's column of two LDS arrays sized at the launch, as in cloud_knn_kernel
-//            (768 max_nn bytes per workgroup of 64 lanes, 48 KB at 64; a runtime-indexed per-thread array would go to
-//            scratch).  The walk's reach is the radius until the list is full and the max_nn-th d^2 after that.  It writes
-//            the neighbour list [n, max_nn] and the degree, ONCE; both later passes read them.
+//            left out by index, sit sorted in the lane's column of two LDS arrays sized at the launch: icp_search.hpp's
+//            KBest, icp_normals_kernel's list (768 max_nn bytes per workgroup of 64 lanes, 48 KB at 64).  The walk's reach
+//            is the radius until the list is full and the max_nn-th d^2 after that.  It writes the neighbour list
+//            [n, max_nn] and the degree, ONCE; both later passes read them.
 //   spfh     one lane per (point, slot of its list).  The pair feature of F2, its three bins of F3, and three integer
 //            atomic increments straight into the point's 33 global int32 counts (zeroed by a memset): integers, so the
 //            order of arrival is free.
@@ -28,7 +28,7 @@
 namespace scorp {
 namespace {
 
-constexpr int kFpfhSearchThreads = 64;
+constexpr int kFpfhSearchThreads = kKBestLanes;
 constexpr int kFpfhMaxNn = 64;
 constexpr int kFpfhBins = 11, kFpfhDim = 33;
 constexpr int kFpfhThreads = 256;
@@ -74,36 +74,19 @@ __global__ void __launch_bounds__(kFpfhSearchThreads) fpfh_search_kernel(const f
   const uint32_t self = __float_as_uint(me.w);
   const CloudWalk walk(tq[i], g);
   const float reach_r = walk.reach(r2);
-  const int k = max_nn;
-  int cnt = 0;
-  double kth = __builtin_inf();   // d^2 of the k-th best once the list is full (never above r2)
-  uint32_t kth_id = 0xFFFFFFFFu;
+  KBest<double> best(nd, ni, lane, max_nn, __builtin_inf());   // (its k-th d^2 is never above r2)
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) {
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) {
       const float4 q = tp[t];
       const uint32_t id = __float_as_uint(q.w);
       const double d2 = cloud_d2(me, q);
-      if (id == self || !(d2 <= r2)) continue;
-      if (cnt == k && !(d2 < kth || (d2 == kth && id < kth_id))) continue;
-      int pos = cnt < k ? cnt : k - 1;   // the free slot, or the last entry, which leaves
-      while (pos > 0) {
-        const double pd = nd[pos - 1][lane];
-        const uint32_t pi = ni[pos - 1][lane];
-        if (!(pd > d2 || (pd == d2 && pi > id))) break;
-        nd[pos][lane] = pd;
-        ni[pos][lane] = pi;
-        pos--;
-      }
-      nd[pos][lane] = d2;
-      ni[pos][lane] = id;
-      if (cnt < k) cnt++;
-      if (cnt == k) { kth = nd[k - 1][lane]; kth_id = ni[k - 1][lane]; }
-    }
+      if (id == self || !(d2 <= r2)) return;
+      best.offer(d2, id);
+    });
   };
-  walk.run(visit, [&]() { return cnt == k ? walk.reach(kth) : reach_r; });
-  for (int a = 0; a < max_nn; a++) nbr[(size_t)self * max_nn + a] = a < cnt ? (int32_t)ni[a][lane] : -1;
-  deg[self] = cnt;
+  walk.run(visit, [&]() { return best.full() ? walk.reach(best.kth()) : reach_r; });
+  best.write_neighbors(nbr, self, max_nn);
+  deg[self] = best.count();
 }
 
 // F2 - F4: the counts

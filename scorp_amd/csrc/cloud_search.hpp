@@ -56,17 +56,10 @@ __global__ void __launch_bounds__(kCloudThreads) cloud_gather_kernel(const float
   tp[t] = make_float4(s[0], s[1], s[2], w);
 }
 
-// What a walk needs of the grid, and the query's cell.
-struct CloudWalk {
-  float x, y, z, lx, ly, lz, h;
-  int cx, cy, cz, dx, dy, dz;
+// IcpWalk with the widened reach.
+struct CloudWalk : IcpWalk {
   double slack;   // 2^-19 G
-  __device__ __forceinline__ CloudWalk(const float4 &me, const IcpGrid *__restrict__ g) {
-    x = me.x; y = me.y; z = me.z;
-    lx = g->lo[0]; ly = g->lo[1]; lz = g->lo[2]; h = g->h;
-    dx = g->dims[0]; dy = g->dims[1]; dz = g->dims[2];
-    const float ih = g->inv_h;
-    cx = icp_cell_axis(x, lx, ih, dx); cy = icp_cell_axis(y, ly, ih, dy); cz = icp_cell_axis(z, lz, ih, dz);
+  __device__ __forceinline__ CloudWalk(const float4 &me, const IcpGrid *__restrict__ g) : IcpWalk(me, g) {
     const double G = fmax(fmax(fabs((double)lx) + (double)dx * h, fabs((double)ly) + (double)dy * h), fabs((double)lz) + (double)dz * h);
     slack = G * (1.0 / 524288.0);
   }
@@ -74,10 +67,6 @@ struct CloudWalk {
   __device__ __forceinline__ float reach(double R) const {
     const double t = sqrt(R) + slack;
     return (float)(t * t * (1.0 + 1e-6));   // (past FLT_MAX: +inf, the walk then visits everything)
-  }
-  template <class Visit, class Reach>
-  __device__ __forceinline__ void run(Visit visit, Reach reach) const {
-    icp_ring_walk(x, y, z, cx, cy, cz, lx, ly, lz, h, dx, dy, dz, visit, reach);
   }
 };
 

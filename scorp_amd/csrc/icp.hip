@@ -29,8 +29,8 @@
 // A block's row depends only on (its source range, its init's T), and the rows are reduced in a fixed order: two calls
 // give the same bits, and init j run alone gives the bits of row j of a batch.
 // scorp_estimate_normals, one thread per point: its k exact nearest neighbours by the same outward ring walk, the list of
-// the k best (d^2, index) kept sorted in LDS (one column per lane), their float64 covariance, the eigenvector of its
-// smallest eigenvalue from svd3.hpp.
+// the k best (d^2, index) kept sorted in LDS (one column per lane; icp_search.hpp's KBest, the list of the FPFH
+// search too), their float64 covariance, the eigenvector of its smallest eigenvalue from svd3.hpp.
 #include <cmath>
 
 #include "common.hpp"
@@ -40,7 +40,7 @@
 namespace scorp {
 namespace {
 
-constexpr int kNormalsThreads = 64;
+constexpr int kNormalsThreads = kKBestLanes;
 constexpr int kNormalsMaxK = 32;
 
 // ---- the estimators: kSums sums per pair in a row of kRow doubles (the sums + pad), sums 0 and 1 are c and sum d^2 ----
@@ -437,9 +437,8 @@ __global__ void __launch_bounds__(64) icp_plane_solve_kernel(const double *__res
 // ---- the normal estimation ----
 
 // One thread per point, in cell order (thread i takes sorted point i, so a wave's queries are neighbours).  The k best
-// (d^2, original index) so far sit sorted in the lane's column of nd / ni; a candidate enters when the list is not full
-// or it is below the last entry, ties on d^2 by the lower index.  The walk is icp_nearest's (icp_ring_walk); it ends when
-// everything outside ring k's box is farther than the k-th best, or nothing is left outside it.
+// (fp32 d^2, original index) so far sit sorted in the lane's column of nd / ni (KBest).  The walk is icp_nearest's
+// (icp_ring_walk); it ends when everything outside ring k's box is farther than the k-th best, or nothing is left outside it.
 __global__ void __launch_bounds__(kNormalsThreads) icp_normals_kernel(const float4 *__restrict__ tq, const float *__restrict__ pts, int n,
                                                                       int k, int knn, const uint32_t *__restrict__ cell_start,
                                                                       const IcpGrid *__restrict__ g, float *__restrict__ out_normals,
@@ -450,53 +449,31 @@ __global__ void __launch_bounds__(kNormalsThreads) icp_normals_kernel(const floa
   const int i = blockIdx.x * kNormalsThreads + lane;
   if (i >= n) return;
   const float4 me = tq[i];
-  const float x = me.x, y = me.y, z = me.z;
   const uint32_t self = __float_as_uint(me.w);
-  const float lx = g->lo[0], ly = g->lo[1], lz = g->lo[2], h = g->h, ih = g->inv_h;
-  const int dx = g->dims[0], dy = g->dims[1], dz = g->dims[2];
-  const int cx = icp_cell_axis(x, lx, ih, dx), cy = icp_cell_axis(y, ly, ih, dy), cz = icp_cell_axis(z, lz, ih, dz);
-  int cnt = 0;
-  float kth = 3.4e38f;          // d^2 of the k-th best once the list is full
-  uint32_t kth_id = 0xFFFFFFFFu;
+  const IcpWalk walk(me, g);
+  KBest<float> best(nd, ni, lane, k, 3.4e38f);
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) {
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) {
       const float4 q = tq[t];
-      const float ux = q.x - x, uy = q.y - y, uz = q.z - z;
-      const float d2 = __builtin_fmaf(ux, ux, __builtin_fmaf(uy, uy, uz * uz));
-      const uint32_t id = __float_as_uint(q.w);
-      if (cnt == k && !(d2 < kth || (d2 == kth && id < kth_id))) continue;
-      int pos = cnt < k ? cnt : k - 1;   // the free slot, or the last entry, which leaves
-      while (pos > 0) {
-        const float pd = nd[pos - 1][lane];
-        const uint32_t pi = ni[pos - 1][lane];
-        if (!(pd > d2 || (pd == d2 && pi > id))) break;
-        nd[pos][lane] = pd;
-        ni[pos][lane] = pi;
-        pos--;
-      }
-      nd[pos][lane] = d2;
-      ni[pos][lane] = id;
-      if (cnt < k) cnt++;
-      if (cnt == k) { kth = nd[k - 1][lane]; kth_id = ni[k - 1][lane]; }
-    }
+      const float ux = q.x - walk.x, uy = q.y - walk.y, uz = q.z - walk.z;
+      best.offer(__builtin_fmaf(ux, ux, __builtin_fmaf(uy, uy, uz * uz)), __float_as_uint(q.w));
+    });
   };
-  icp_ring_walk(x, y, z, cx, cy, cz, lx, ly, lz, h, dx, dy, dz, visit, [&]() { return kth; });
-  if (out_neighbors) {
-    for (int a = 0; a < knn; a++) out_neighbors[(size_t)self * knn + a] = a < cnt ? (int32_t)ni[a][lane] : -1;
-  }
+  walk.run(visit, [&]() { return best.kth(); });
+  if (out_neighbors) best.write_neighbors(out_neighbors, self, knn);
+  const int cnt = best.count();
   float *o = out_normals + (size_t)self * 3;
   if (cnt < 3) { o[0] = 0.0f; o[1] = 0.0f; o[2] = 1.0f; return; }
   // float64 covariance of the neighbours about their mean (coordinates relative to c_t)
   double m0 = 0.0, m1 = 0.0, m2 = 0.0;
   for (int a = 0; a < cnt; a++) {
-    const float *p = pts + (size_t)ni[a][lane] * 3;
+    const float *p = pts + (size_t)best.id(a) * 3;
     m0 += (double)p[0] - g->ct[0]; m1 += (double)p[1] - g->ct[1]; m2 += (double)p[2] - g->ct[2];
   }
   m0 /= cnt; m1 /= cnt; m2 /= cnt;
   double c00 = 0.0, c01 = 0.0, c02 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0;
   for (int a = 0; a < cnt; a++) {
-    const float *p = pts + (size_t)ni[a][lane] * 3;
+    const float *p = pts + (size_t)best.id(a) * 3;
     const double e0 = ((double)p[0] - g->ct[0]) - m0, e1 = ((double)p[1] - g->ct[1]) - m1, e2 = ((double)p[2] - g->ct[2]) - m2;
     c00 = fma(e0, e0, c00); c01 = fma(e0, e1, c01); c02 = fma(e0, e2, c02);
     c11 = fma(e1, e1, c11); c12 = fma(e1, e2, c12); c22 = fma(e2, e2, c22);

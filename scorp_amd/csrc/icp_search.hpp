@@ -1,8 +1,10 @@
 // icp_search.hpp - what icp.hip (both ICP estimators and the normal estimation) and mesh_distance.hip (point-to-mesh
 // distance, nearest point of a cloud) share: the uniform grid over the target, the stable radix sort that orders the
 // target by cell and the source or the queries by Morton code, the exact outward ring walk over the grid (fp32 for the
-// point searches, float64 for the mesh's), the workspace check and the host calls that build all of it once per call.
-// Everything is in an unnamed namespace: each of the two files gets its own copy of the kernels.
+// point searches, float64 for the mesh's) with the one loop over a run of cells (icp_cell_run) and the one k-best list
+// (KBest) that the kernels put inside it, the workspace check and the host calls that build all of it once per call.
+// cloud_filter.hip and cloud_fpfh.hip include it through cloud_search.hpp.  Everything is in an unnamed namespace: each
+// includer gets its own copy of the kernels.
 #pragma once
 #include <cmath>
 #include <vector>
@@ -294,6 +296,79 @@ __device__ __forceinline__ void icp_ring_walk(F x, F y, F z, int cx, int cy, int
   }
 }
 
+// The body of every visit(ca, cb): cell ids are raster order (x fastest), so the entries of the cells ca..cb of one grid
+// row are one contiguous run of sorted positions; body(t) takes each.
+template <class Body>
+__device__ __forceinline__ void icp_cell_run(const uint32_t *cell_start, int ca, int cb, Body body) {
+  const uint32_t e = cell_start[cb + 1];
+  for (uint32_t t = cell_start[ca]; t < e; t++) body(t);
+}
+
+// What a walk from a filed point needs of the grid, and the point's own cell (inside the grid: icp_cell_axis clamps as the
+// filing did).  cloud_search.hpp's CloudWalk adds the widened reach; icp_nearest and the mesh query start from points that
+// were never filed and set their walks up themselves.
+struct IcpWalk {
+  float x, y, z, lx, ly, lz, h;
+  int cx, cy, cz, dx, dy, dz;
+  __device__ __forceinline__ IcpWalk(const float4 &me, const IcpGrid *__restrict__ g) {
+    x = me.x; y = me.y; z = me.z;
+    lx = g->lo[0]; ly = g->lo[1]; lz = g->lo[2]; h = g->h;
+    dx = g->dims[0]; dy = g->dims[1]; dz = g->dims[2];
+    const float ih = g->inv_h;
+    cx = icp_cell_axis(x, lx, ih, dx); cy = icp_cell_axis(y, ly, ih, dy); cz = icp_cell_axis(z, lz, ih, dz);
+  }
+  template <class Visit, class Reach>
+  __device__ __forceinline__ void run(Visit visit, Reach reach) const {
+    icp_ring_walk(x, y, z, cx, cy, cz, lx, ly, lz, h, dx, dy, dz, visit, reach);
+  }
+};
+
+// The k best (d^2, index) a lane has seen, sorted ascending by that pair, in the lane's column of two LDS arrays the
+// kernel owns (a runtime-indexed per-thread array would go to scratch): the one tie rule of the normals' list, the FPFH
+// search (F1) and the cloud kNN (R3; cloud_knn_kernel keeps the same statements on locals of its own, see there).  D is the kernel's d^2 type, float or double; the list only compares and moves, so
+// it holds nothing a contraction setting could change.  Workgroups of kKBestLanes lanes.
+constexpr int kKBestLanes = 64;
+
+template <class D>
+struct KBest {
+  D (*nd)[kKBestLanes];
+  uint32_t (*ni)[kKBestLanes];
+  int lane, k, cnt;
+  D kth_d2;          // d^2 of the k-th best once the list is full; until then the kernel's `none`
+  uint32_t kth_id;
+  // none: what kth() gives while the list is not full (the reach of a walk that must not end yet)
+  __device__ __forceinline__ KBest(D (*nd_)[kKBestLanes], uint32_t (*ni_)[kKBestLanes], int lane_, int k_, D none)
+      : nd(nd_), ni(ni_), lane(lane_), k(k_), cnt(0), kth_d2(none), kth_id(0xFFFFFFFFu) {}
+  // a candidate enters when the list is not full or it is below the last entry, ties on d^2 by the lower index
+  // (cnt >= k is full(): cnt never passes k.  Written as cnt == k here, the compiler puts k for cnt on the path that
+  // skips and then carries the count in two registers in icp_normals_kernel, with a move more on every insertion.)
+  __device__ __forceinline__ void offer(D d2, uint32_t id) {
+    if (cnt >= k && !(d2 < kth_d2 || (d2 == kth_d2 && id < kth_id))) return;
+    int pos = cnt < k ? cnt : k - 1;   // the free slot, or the last entry, which leaves
+    while (pos > 0) {
+      const D pd = nd[pos - 1][lane];
+      const uint32_t pi = ni[pos - 1][lane];
+      if (!(pd > d2 || (pd == d2 && pi > id))) break;
+      nd[pos][lane] = pd;
+      ni[pos][lane] = pi;
+      pos--;
+    }
+    nd[pos][lane] = d2;
+    ni[pos][lane] = id;
+    if (cnt < k) cnt++;
+    if (cnt == k) { kth_d2 = nd[k - 1][lane]; kth_id = ni[k - 1][lane]; }
+  }
+  __device__ __forceinline__ bool full() const { return cnt == k; }
+  __device__ __forceinline__ D kth() const { return kth_d2; }
+  __device__ __forceinline__ int count() const { return cnt; }
+  __device__ __forceinline__ D d2(int a) const { return nd[a][lane]; }
+  __device__ __forceinline__ uint32_t id(int a) const { return ni[a][lane]; }
+  // the list's indices into row `row` of out [., width], padded with -1
+  __device__ __forceinline__ void write_neighbors(int32_t *out, size_t row, int width) const {
+    for (int a = 0; a < width; a++) out[row * width + a] = a < cnt ? (int32_t)ni[a][lane] : -1;
+  }
+};
+
 // Original index of the nearest target point to x (relative fp32) with d^2 <= best on entry, -1 if none; ties go to the
 // lower original index.  icp_ring_walk around x's cell (clamped to one cell outside the grid), until the distance from x
 // to everything outside ring k's box exceeds the best d^2 so far, or nothing is left outside it.
@@ -310,16 +385,14 @@ __device__ __forceinline__ int icp_nearest(float x, float y, float z, float best
   const int cy = (int)floorf(fminf(fmaxf((y - ly) * ih, -1.0f), (float)dy));
   const int cz = (int)floorf(fminf(fmaxf((z - lz) * ih, -1.0f), (float)dz));
   uint32_t bidx = 0xFFFFFFFFu;
-  // cells ca..cb of one grid row: cell ids are raster order (x fastest), so their points are one contiguous run
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) {
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) {
       const float4 q = tq[t];
       const float ux = q.x - x, uy = q.y - y, uz = q.z - z;
       const float d2 = __builtin_fmaf(ux, ux, __builtin_fmaf(uy, uy, uz * uz));
       const uint32_t id = __float_as_uint(q.w);
       if (d2 < best || (d2 == best && id < bidx)) { best = d2; bidx = id; }
-    }
+    });
   };
   icp_ring_walk(x, y, z, cx, cy, cz, lx, ly, lz, h, dx, dy, dz, visit, [&]() { return best; });
   return bidx == 0xFFFFFFFFu ? -1 : (int)bidx;

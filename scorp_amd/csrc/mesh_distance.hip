@@ -235,15 +235,14 @@ __global__ void __launch_bounds__(kMeshDistThreads) mesh_query_kernel(MeshView m
   uint32_t bface = 0xFFFFFFFFu;
   // cells ca..cb of one grid row: one contiguous run of pairs
   auto visit = [&](int ca, int cb) {
-    const uint32_t e = cell_start[cb + 1];
-    for (uint32_t t = cell_start[ca]; t < e; t++) {
+    icp_cell_run(cell_start, ca, cb, [&](uint32_t t) {
       const uint32_t f = pairs[t];
-      if (f >= (uint32_t)m.F) continue;
+      if (f >= (uint32_t)m.F) return;
       Vec3d c;
       double d2;
-      if (!face_distance(m, ct, (int32_t)f, P, c, d2)) continue;
+      if (!face_distance(m, ct, (int32_t)f, P, c, d2)) return;
       if (d2 < best || (d2 == best && f < bface)) { best = d2; bface = f; }
-    }
+    });
   };
   icp_ring_walk(P.x, P.y, P.z, cx, cy, cz, lx, ly, lz, h, dx, dy, dz, visit, [&]() { return best; });   // rule 6
   if (bface == 0xFFFFFFFFu) {

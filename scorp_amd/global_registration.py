@@ -23,8 +23,9 @@ import numpy as np
 import torch
 
 from . import _C
-from .cloud import _at_least, _cloud, _positive, knn_mean_distance, voxel_down_sample
-from .icp import _check_finite, _device, _points, downsample_indices, estimate_normals, registration_icp
+from ._points import _at_least, _check_finite, _cloud, _device, _points, _positive
+from .cloud import knn_mean_distance, voxel_down_sample
+from .icp import downsample_indices, estimate_normals, registration_icp
 from .pose_fit import MAX_HYPOTHESES, ransac_fit
 
 FPFH_DIM = 33
@@ -151,11 +152,8 @@ def orient_normals_consistent_tangent_plane(points, normals, k=12, neighbors=Non
     if return_info:
         label = torch.empty(n, dtype=torch.int32, device=dev)
         tree = torch.empty(n, 2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        size = _C.lib().scorp_cloud_orient_workspace_bytes(n, kk)
-        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-        _C.call("scorp_cloud_orient_normals", P, N, nb, n, kk, c, COMPONENT_SIGNS[component_sign], out, flip, label, tree, counts,
-                workspace, size)
+    _C.call_with_workspace("scorp_cloud_orient_normals", "scorp_cloud_orient_workspace_bytes", (n, kk),
+                           P, N, nb, n, kk, c, COMPONENT_SIGNS[component_sign], out, flip, label, tree, counts)
     if given.dtype != torch.float32 or given.device != dev:   # the caller's dtype and device: a negation is exact in every float type
         out = torch.where(flip.to(given.device).bool()[:, None], -given, given)
     if not return_info:
@@ -191,10 +189,7 @@ def compute_fpfh_feature(points, normals, radius, max_nn=64, return_neighbors=Fa
         nb = torch.empty(n, max_nn, dtype=torch.int32, device=dev)
         deg = torch.empty(n, dtype=torch.int32, device=dev)
         cnt = torch.empty(n, FPFH_DIM, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        size = _C.lib().scorp_cloud_fpfh_workspace_bytes(n, max_nn)
-        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-        _C.call("scorp_cloud_fpfh", P, N, n, r, max_nn, feature, cnt, nb, deg, workspace, size)
+    _C.call_with_workspace("scorp_cloud_fpfh", "scorp_cloud_fpfh_workspace_bytes", (n, max_nn), P, N, n, r, max_nn, feature, cnt, nb, deg)
     return (feature, nb, deg, cnt) if return_neighbors else feature
 
 
@@ -216,10 +211,7 @@ def _match(S, T):
     ns, nt, dev = S.shape[0], T.shape[0], S.device
     index = torch.empty(ns, dtype=torch.int32, device=dev)
     d2 = torch.empty(ns, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        size = _C.lib().scorp_feature_match_workspace_bytes(ns, nt)
-        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-        _C.call("scorp_feature_match", S, ns, T, nt, index, d2, workspace, size)
+    _C.call_with_workspace("scorp_feature_match", "scorp_feature_match_workspace_bytes", (ns, nt), S, ns, T, nt, index, d2)
     return index, d2
 
 

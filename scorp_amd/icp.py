@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _C
+from ._points import _check_finite, _check_shape, _device, _points
 
 
 @dataclass
@@ -27,41 +28,6 @@ class ICPResult:
     fitness: np.ndarray
     inlier_rmse: np.ndarray
     iterations: np.ndarray
-
-
-def _check_finite(name, a):
-    if isinstance(a, torch.Tensor):
-        bad_nan, bad_inf = bool(torch.isnan(a).any()), bool(torch.isinf(a).any())
-    else:
-        a = np.asarray(a)
-        bad_nan, bad_inf = bool(np.isnan(a).any()), bool(np.isinf(a).any())
-    if bad_nan:
-        raise ValueError(f"{name} contains NaN values")
-    if bad_inf:
-        raise ValueError(f"{name} contains Inf values")
-
-
-def _check_shape(name, a):
-    shape = tuple(np.shape(a))
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError(f"{name} must be [n, 3]; got {shape}")
-    if shape[0] == 0:
-        raise ValueError(f"{name} is empty")
-    if shape[0] >= 2 ** 31:
-        raise ValueError(f"{name} has more than 2^31 - 1 points")
-
-
-def _points(name, a, device):
-    _check_shape(name, a)
-    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
-    return t.to(device=device, dtype=torch.float32).contiguous()
-
-
-def _device(*arrays):
-    for a in arrays:
-        if isinstance(a, torch.Tensor) and a.is_cuda:
-            return a.device
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 ESTIMATIONS = ("point_to_point", "point_to_plane", "generalized")
@@ -84,12 +50,9 @@ def estimate_normals(points, knn=30, return_neighbors=False):
     dev = _device(points)
     P = _points("points", points, dev)
     n, knn = P.shape[0], int(knn)
-    size = _C.lib().scorp_estimate_normals_workspace_bytes(n)
     normals = torch.empty(n, 3, dtype=torch.float32, device=dev)
     nb = torch.empty(n, knn, dtype=torch.int32, device=dev) if return_neighbors else None
-    with torch.cuda.device(dev):
-        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-        _C.call("scorp_estimate_normals", P, n, knn, normals, nb, workspace, size)
+    _C.call_with_workspace("scorp_estimate_normals", "scorp_estimate_normals_workspace_bytes", (n,), P, n, knn, normals, nb)
     return (normals, nb) if return_neighbors else normals
 
 
@@ -206,7 +169,6 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     P = _points("source", source, dev)
     Q = _points("target", target, dev)
     ni = T0.shape[0]
-    L = _C.lib()
     if plane:
         Nq = estimate_normals(Q, knn=30) if target_normals is None else _points("target_normals", target_normals, dev)
     if gicp:
@@ -214,19 +176,17 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
               else _covariances("source_covariances", source_covariances, P.shape[0], dev))
         Cq = (estimate_covariances(Q) if target_covariances is None
               else _covariances("target_covariances", target_covariances, Q.shape[0], dev))
-    size = (L.scorp_icp_generalized_workspace_bytes if gicp else L.scorp_icp_point_to_plane_workspace_bytes if plane
-            else L.scorp_icp_workspace_bytes)(P.shape[0], Q.shape[0], ni)
     T_in = torch.as_tensor(np.ascontiguousarray(T0), device=dev)
     T_out = torch.empty_like(T_in)
     fit = torch.empty(ni, dtype=torch.float64, device=dev)
     rmse = torch.empty(ni, dtype=torch.float64, device=dev)
     iters = torch.empty(ni, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-        name = "scorp_icp_generalized" if gicp else "scorp_icp_point_to_plane" if plane else "scorp_icp_point_to_point"
-        _C.call(name, P, *((Cp,) if gicp else ()), P.shape[0], Q, *((Cq,) if gicp else (Nq,) if plane else ()), Q.shape[0],
-                T_in, ni, r, int(max_iteration), float(relative_fitness), float(relative_rmse), T_out, fit, rmse, iters,
-                workspace, size)
+    name, size_name = (("scorp_icp_generalized", "scorp_icp_generalized_workspace_bytes") if gicp
+                       else ("scorp_icp_point_to_plane", "scorp_icp_point_to_plane_workspace_bytes") if plane
+                       else ("scorp_icp_point_to_point", "scorp_icp_workspace_bytes"))
+    _C.call_with_workspace(name, size_name, (P.shape[0], Q.shape[0], ni),
+                           P, *((Cp,) if gicp else ()), P.shape[0], Q, *((Cq,) if gicp else (Nq,) if plane else ()), Q.shape[0],
+                           T_in, ni, r, int(max_iteration), float(relative_fitness), float(relative_rmse), T_out, fit, rmse, iters)
     return ICPResult(T_out.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy())
 
 

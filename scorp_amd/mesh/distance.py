@@ -353,10 +353,7 @@ def nearest_point_distance(points, cloud, max_distance=float("inf")):
     d2 = torch.empty(Q, dtype=torch.float64, device=dev)
     idx = torch.empty(Q, dtype=torch.int32, device=dev)
     if Q:
-        with torch.cuda.device(dev):
-            size = _C.lib().scorp_nearest_point_workspace_bytes(Q, N)
-            workspace = torch.empty(size, dtype=torch.uint8, device=dev)
-            _C.call("scorp_nearest_point_distance", pts, Q, cloud, N, r, d2, idx, workspace, size)
+        _C.call_with_workspace("scorp_nearest_point_distance", "scorp_nearest_point_workspace_bytes", (Q, N), pts, Q, cloud, N, r, d2, idx)
     return NearestPoint(d2, idx)
 
 

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _C
+from ._points import _device
 
 METHODS = {"umeyama": _C.POSE_UMEYAMA, "kabsch": _C.POSE_KABSCH}
 MAX_HYPOTHESES = 65535
@@ -32,13 +33,6 @@ class RansacFit:
     count: int
     counts: np.ndarray
     mask: np.ndarray
-
-
-def _device(*arrays):
-    for a in arrays:
-        if isinstance(a, torch.Tensor) and a.is_cuda:
-            return a.device
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def _pairs(source, target, device, through_fp32=False):
