@@ -26,6 +26,12 @@
  * scorp_gs3d_num_pairs().  Errors: 0 = ok, negative = failure with a message in scorp_last_error()
  * (thread-local).  With `debug` set every kernel is followed by a stream sync + error check
  * (the reference's `pipe.debug`, gaussian_renderer/__init__.py:63).
+ *
+ * Style: the Python binding (scorp_amd/_C.py) is derived from this text by a reader that is no C parser and refuses what it
+ * does not know, so keep to what is here: block comments only; one declaration per `;`; scalars spelled int, int32_t,
+ * uint32_t, int64_t, uint64_t, size_t, float, double; pointers to those, to void, uint8_t or a struct declared above;
+ * `#define SCORP_<NAME> <literal>` with the literal written 4, 4u, (-4) or 0.3f.  No function pointers, no unions, no
+ * bit-fields, no nested structs by value, no macros in declarations.
  */
 #ifndef SCORP_GS_H
 #define SCORP_GS_H

@@ -116,8 +116,8 @@ class FusedAdam(torch.optim.Adam):
         # (counted once per step, by the step's first launch)
         count_ptr = None if skip is None or not stepped else ctypes.c_void_p(self.skipped_counter(skip.device).data_ptr())
         for (betas, eps, step), items in by_cfg.items():
-            for i in range(0, len(items), 8):
-                chunk = items[i:i + 8]
+            for i in range(0, len(items), _C.ADAM_MAX_TENSORS):
+                chunk = items[i:i + _C.ADAM_MAX_TENSORS]
                 arr = (_C.ScorpAdamTensor * len(chunk))()
                 for k, (p, g, st, lr) in enumerate(chunk):
                     assert p.is_contiguous() and p.dtype == torch.float32

@@ -99,12 +99,13 @@ def depth_losses(rend_depth, iteration, opt, gt_depth=None, gt_depth_est=None):
     """The depth terms of train_3dgs.py:109-133 / train_2dgs.py:95-133 (active after opt.depth_from_iter): L1 against a
     sensor depth inside (0.3, 7) where something was rendered, and L1 between min-max-normalised rendered and estimated
     (monocular) depth with the exponentially decaying weight 10 * dn_l1_weight(iteration)."""
+    from . import _C
     from .gaussian_model import get_expon_lr_func
     loss = torch.zeros((), device=rend_depth.device)
     if iteration <= opt.depth_from_iter:
         return loss
     if gt_depth is not None:
-        mask = (gt_depth > 0.3) & (gt_depth < 7) & (rend_depth > 0.0)
+        mask = (gt_depth > _C.DEPTH_SENSOR_MIN) & (gt_depth < _C.DEPTH_SENSOR_MAX) & (rend_depth > 0.0)
         loss = loss + opt.lambda_depth_sensor * l1_loss(rend_depth[mask], gt_depth[mask])
     if gt_depth_est is not None:
         w = get_expon_lr_func(opt.dn_l1_weight_init, opt.dn_l1_weight_final, max_steps=opt.iterations)(iteration)

@@ -357,7 +357,7 @@ def _adam_tensors(n, numel=16):
     from scorp_amd import _C
     arr = (_C.ScorpAdamTensor * n)()
     for k in range(n):
-        arr[k].param = arr[k].grad = arr[k].exp_avg = arr[k].exp_avg_sq = ctypes.cast(_DUMMY, _C.c_float_p)
+        arr[k].param = arr[k].grad = arr[k].exp_avg = arr[k].exp_avg_sq = ctypes.cast(_DUMMY, ctypes.c_void_p)
         arr[k].numel, arr[k].lr = numel, 1e-3
     return arr
 
@@ -372,7 +372,7 @@ def test_adam_refuses_too_many_tensors_step_zero_and_a_null_moment(L):
     assert b"step=0" in _refused(L, L.scorp_adam_step(_adam_tensors(2), 2, 0.9, 0.999, 1e-15, 0, None))
     for field in ("exp_avg", "exp_avg_sq"):
         arr = _adam_tensors(3)
-        setattr(arr[1], field, ctypes.cast(None, _C.c_float_p))
+        setattr(arr[1], field, ctypes.cast(None, ctypes.c_void_p))
         assert b"tensor 1" in _refused(L, L.scorp_adam_step_guarded(arr, 3, 0.9, 0.999, 1e-15, 1, None, None))
 
 
@@ -382,7 +382,7 @@ def test_gather_rows_refuses_too_many_tensors_and_an_empty_row(L):
     def tensors(n):
         arr = (_C.ScorpRowTensor * n)()
         for k in range(n):
-            arr[k].src = arr[k].dst = ctypes.cast(_DUMMY, _C.c_float_p)
+            arr[k].src = arr[k].dst = ctypes.cast(_DUMMY, ctypes.c_void_p)
             arr[k].row_floats = 3
         return arr
     assert b"n=25" in _refused(L, L.scorp_gather_rows(tensors(25), 25, _DUMMY, 10, None))
