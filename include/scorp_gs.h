@@ -304,6 +304,37 @@ int scorp_icp_generalized(const float *source, const float *source_covariances, 
                           double relative_rmse, double *out_transformation, double *out_fitness, double *out_inlier_rmse,
                           int32_t *out_iterations, void *workspace, size_t workspace_bytes, scorp_stream_t stream);
 
+/* ---- multi-start coloured ICP (Park, Zhou, Koltun 2017; what Open3D's registration_colored_icp is used for: surfaces
+ * that slide or spin at no geometric cost and carry a texture; from every init of a batch) ----
+ * Open3D could not be run where this was written: the rules below ARE the specification.
+ * Inputs, outputs, pass(T), the loop, the stop rule, the precision of the search, the determinism and the error codes are
+ * those of scorp_icp_point_to_point; fitness and inlier_rmse stay those of the pairs' positions (the Euclidean
+ * sqrt(sum |x - q|^2 / c): the colour residual does not enter them).  The arguments are those of
+ * scorp_icp_point_to_plane, plus source_intensity[n_source], target_intensity[n_target] and target_gradients[n_target, 3]
+ * fp32 (device; scorp_color_gradients makes the last) and lambda_geometric in [0, 1].  All are used as given.
+ *   update:    from the c pairs of a pass - x, q, the normal n, the gradient d and the intensity I_q of q, the intensity I_p
+ *              of the source point - in float64, every coordinate relative to c_t, with s as for point-to-plane:
+ *                rho_G = n . (x - q),               J_G = [(x cross n) / s ; n],
+ *                rho_C = d . (x - q) + (I_q - I_p), J_C = [(x cross d) / s ; d],
+ *                A = sum lambda J_G J_G^T + (1 - lambda) J_C J_C^T,
+ *                b = sum lambda J_G rho_G + (1 - lambda) J_C rho_C;
+ *              everything after that is the point-to-plane update unchanged: Jacobi on A, the minimum-norm step over the
+ *              eigenvalues above 1e-12 l_max, the identity when c = 0 or l_max = 0, omega = xi[0:3] / s, tau = xi[3:6],
+ *              R = Rz Ry Rx, composed about c_t.
+ * Because d is tangent, d . (x - q) is the gradient applied to the projection of x into the tangent plane of q: there is
+ * no separate projection step.  A zero normal contributes only its colour term, a zero gradient with equal intensities
+ * only its geometric term; either way the pair counts in c.  Constant colour, or lambda = 1, gives the point-to-plane step.
+ * SCORP_ERR_INVALID as for scorp_icp_point_to_plane, and: lambda_geometric outside [0, 1] or not finite, a NULL pointer
+ * among the new ones.  workspace: scorp_icp_colored_workspace_bytes (the point-to-plane workspace and the source's
+ * intensities in its sorted order), 256-byte aligned. */
+size_t scorp_icp_colored_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init);
+int scorp_icp_colored(const float *source, const float *source_intensity, int32_t n_source, const float *target,
+                      const float *target_normals, const float *target_intensity, const float *target_gradients,
+                      int32_t n_target, const double *inits, int32_t n_init, double max_correspondence_distance,
+                      int32_t max_iteration, double relative_fitness, double relative_rmse, double lambda_geometric,
+                      double *out_transformation, double *out_fitness, double *out_inlier_rmse, int32_t *out_iterations,
+                      void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+
 /* Normals of a cloud that brings none (3DGS centres).  points[n, 3] fp32, out_normals[n, 3] fp32 and the optional
  * out_neighbors[n, knn] int32 (NULL: skipped) are device pointers.  Per point:
  *   neighbours: its k = min(knn, n) exact nearest points, itself included, ordered by (d^2, index): ties go to the lower
@@ -319,6 +350,24 @@ int scorp_icp_generalized(const float *source, const float *source_covariances, 
 size_t scorp_estimate_normals_workspace_bytes(int32_t n);
 int scorp_estimate_normals(const float *points, int32_t n, int32_t knn, float *out_normals, int32_t *out_neighbors,
                            void *workspace, size_t workspace_bytes, scorp_stream_t stream);
+
+/* Colour gradients of a cloud, for scorp_icp_colored.  points[n, 3], normals[n, 3], intensity[n] fp32, neighbors[n, knn]
+ * int32 in the layout scorp_estimate_normals writes (sorted, padded with -1) and out_gradients[n, 3] fp32 are device
+ * pointers; knn in [3, 32].  Per point i, in float64:
+ *   nh = n_i / |n_i|; nh = 0 for a zero or non-finite normal (nothing is projected out);
+ *   over the row's entries j >= 0, j != i, in row order (an entry >= n is skipped):
+ *     u_j = p_j - p_i, e_j = u_j - (u_j . nh) nh, delta_j = I_j - I_i;
+ *   M = sum e_j e_j^T + (sum |e_j|^2) nh nh^T, g = sum e_j delta_j;
+ *   M = V L V^T (3x3 Jacobi, float64);
+ *   d = sum over { l_k > 1e-12 l_max } of v_k (v_k . g) / l_k;
+ *   d = 0 when fewer than two neighbours were used or l_max = 0;
+ *   d is rounded to fp32 on the store.
+ * The second term of M keeps d in the tangent plane (d . nh = 0 up to rounding) and M well-conditioned wherever the
+ * neighbours span that plane; collinear neighbours give the component along their line and nothing else.  One thread per
+ * point, no atomics: two calls give the same bits.  The inputs are only read.  No workspace.  SCORP_ERR_INVALID: knn outside
+ * [3, 32], an empty cloud, more than 2^30 points, a NULL pointer. */
+int scorp_color_gradients(const float *points, const float *normals, const float *intensity, const int32_t *neighbors,
+                          int32_t n, int32_t knn, float *out_gradients, scorp_stream_t stream);
 
 /* ---- cleaning a point cloud: k-nearest mean distances, radius counts, DBSCAN (what Open3D's remove_statistical_outlier,
  * remove_radius_outlier and cluster_dbscan are used for; the alignment scripts size their objects by the bounding box of

@@ -1,5 +1,6 @@
-// icp.hip — multi-start ICP (Open3D registration_icp, every init of a call in one batch) with one of three estimators, and
-// the normal estimation that feeds the second one when the target brings no normals.  The rules are written down in
+// icp.hip — multi-start ICP (Open3D registration_icp, every init of a call in one batch) with one of four estimators, the
+// normal estimation that feeds the second one when the target brings no normals, and the colour gradients that feed the
+// fourth.  The rules are written down in
 // include/scorp_gs.h.  The reference's alignment scripts run the point-to-point form from 67 initial poses with
 // max_iteration = 400 (align_3dgs_clpe_9dof.py:42-115 get_ICP_fitting_transformation_best).
 //
@@ -8,13 +9,15 @@
 //     LSD radix sort on the cell id) as float4 {q - c_t (fp32), original index};
 //   * the source P sorted by a 30-bit Morton code over its own bounding box (same sort), so that the 64 queries of a wave
 //     stay neighbours under every rigid T_i and the target cells they visit are shared through L2; the generalized
-//     estimator's source covariances are gathered into that order once, behind the shared workspace.
+//     estimator's source covariances, and the coloured estimator's source intensities, are gathered into that order once,
+//     behind the shared workspace.
 // Per iteration (no host synchronisation; the host reads the active flags every kIcpPollEvery iterations), one body each
 // for every estimator (icp_pass, icp_solve) behind thin kernels:
-//   * icp_pass_kernel / icp_plane_pass_kernel / icp_generalized_pass_kernel, grid (source blocks, inits): x = T_i p in float64 (the cumulative transform
+//   * icp_pass_kernel / icp_plane_pass_kernel / icp_generalized_pass_kernel / icp_colored_pass_kernel, grid (source blocks,
+//     inits): x = T_i p in float64 (the cumulative transform
 //     on the original point), exact nearest target point q within r by an outward ring search over the grid in fp32, the
 //     chosen pair's d^2 in float64 relative to c_t, then the estimator's sums: one fixed row per block, no float atomics;
-//   * icp_solve_kernel / icp_plane_solve_kernel (the generalized estimator's too), one wave per init: the rows reduced in a fixed order, fitness / rmse, the
+//   * icp_solve_kernel / icp_plane_solve_kernel (the generalized and coloured estimators' too), one wave per init: the rows reduced in a fixed order, fitness / rmse, the
 //     stop rule, the estimator's update [R | tau] about c_t, composed onto T in float64.
 // The estimators differ in their sums and their update alone:
 //   * PointToPoint (TransformationEstimationPointToPoint, no scaling): 17 sums (c, sum d^2, the first and second moments
@@ -25,12 +28,18 @@
 //     R = Rz Ry Rx;
 //   * Generalized (Segal et al. 2009): with the covariances C_p, C_q of the pair, W = (C_q + A_T C_p A_T^T)^-1 by cofactors
 //     where that matrix is positive definite, J = [-[x]x / s | I], the same 29 sums (J^T W J, J^T W (x - q)) and
-//     PointToPlane's solve; W = n n^T would give PointToPlane's sums.
+//     PointToPlane's solve; W = n n^T would give PointToPlane's sums;
+//   * Colored (Park, Zhou, Koltun 2017): with the normal n, the colour gradient d and the intensity I_q of q and the
+//     intensity I_p of the source point, PointToPlane's term at the weight lambda and the same term on d with
+//     rho_C = d . (x - q) + (I_q - I_p) at 1 - lambda, the same 29 sums and PointToPlane's solve; lambda = 1 gives
+//     PointToPlane's sums bit for bit.
 // A block's row depends only on (its source range, its init's T), and the rows are reduced in a fixed order: two calls
 // give the same bits, and init j run alone gives the bits of row j of a batch.
 // scorp_estimate_normals, one thread per point: its k exact nearest neighbours by the same outward ring walk, the list of
 // the k best (d^2, index) kept sorted in LDS (one column per lane; icp_search.hpp's KBest, the list of the FPFH
 // search too), their float64 covariance, the eigenvector of its smallest eigenvalue from svd3.hpp.
+// scorp_color_gradients, one thread per point: the least-squares gradient of the intensity over the stored neighbour row,
+// held in the tangent plane by a normal-normal term in its 3x3 system, solved through svd3.hpp.
 #include <cmath>
 
 #include "common.hpp"
@@ -48,7 +57,7 @@ constexpr int kNormalsMaxK = 32;
 // Row layout: [c, sum d^2, sum x (3), sum q (3), sum x_a q_b (9, a-major), pad]
 struct PointToPoint {
   static constexpr int kSums = 17, kRow = 18;
-  static constexpr bool kNormals = false, kCovariances = false;
+  static constexpr bool kNormals = false, kCovariances = false, kColors = false;
   static constexpr const char *kWho = "icp";
   __device__ PointToPoint(const IcpGrid *, const double *, const float *) {}
 
@@ -97,7 +106,7 @@ struct PointToPoint {
 // Row layout: [c, sum d^2, A_00 A_01 .. A_05 A_11 .. A_55 (21), b (6), pad]
 struct PointToPlane {
   static constexpr int kSums = 29, kRow = 30;
-  static constexpr bool kNormals = true, kCovariances = false;
+  static constexpr bool kNormals = true, kCovariances = false, kColors = false;
   static constexpr const char *kWho = "icp point-to-plane";
   double s;
   __device__ PointToPlane(const IcpGrid *g, const double *, const float *) : s(scale(g)) {}
@@ -209,7 +218,7 @@ struct PointToPlane {
 // sc: the source's covariances in the order of W.sp; the target's come by the pair's original index, as normals do.
 struct Generalized {
   static constexpr int kSums = PointToPlane::kSums, kRow = PointToPlane::kRow;
-  static constexpr bool kNormals = true, kCovariances = true;
+  static constexpr bool kNormals = true, kCovariances = true, kColors = false;
   static constexpr const char *kWho = "icp generalized";
   double s;
   double a00, a01, a02, a10, a11, a12, a20, a21, a22;   // A_T: the rotation block of the init's T, uniform per block
@@ -284,16 +293,73 @@ struct Generalized {
   }
 };
 
+// what the Colored estimator reads besides the normals: the target's colour gradients and intensities by the pair's
+// original index, and the weight of the geometric term
+struct IcpColors {
+  const float *__restrict__ target_gradients, *__restrict__ target_intensity;
+  double lambda;
+};
+
+// Row layout and solve: PointToPlane's (A = sum lambda J_G J_G^T + (1 - lambda) J_C J_C^T, b likewise with rho_G, rho_C).
+// si: the source's intensities in the order of W.sp; the target's normals, gradients and intensities come by the pair's
+// original index.  lambda = 1 leaves PointToPlane's sums bit for bit.
+struct Colored {
+  static constexpr int kSums = PointToPlane::kSums, kRow = PointToPlane::kRow;
+  static constexpr bool kNormals = true, kCovariances = false, kColors = true;
+  static constexpr const char *kWho = "icp colored";
+  double s, wg, wc;
+  const float *__restrict__ si, *__restrict__ tg, *__restrict__ ti;
+  __device__ Colored(const IcpGrid *g, const double *, const float *source_intensity, const IcpColors &c)
+      : s(PointToPlane::scale(g)), wg(c.lambda), wc(1.0 - c.lambda), si(source_intensity), tg(c.target_gradients),
+        ti(c.target_intensity) {}
+
+  // one term: acc += w J J^T, w J rho with J = [(x cross v) / s ; v]
+  __device__ __forceinline__ void term(double (&acc)[kSums], const double x[3], double v0, double v1, double v2, double rho,
+                                       double w) const {
+    double J[6], wJ[6];
+    J[0] = (x[1] * v2 - x[2] * v1) / s;
+    J[1] = (x[2] * v0 - x[0] * v2) / s;
+    J[2] = (x[0] * v1 - x[1] * v0) / s;
+    J[3] = v0; J[4] = v1; J[5] = v2;
+#pragma unroll
+    for (int a = 0; a < 6; a++) wJ[a] = w * J[a];
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+      for (int b = a; b < 6; b++) {
+        const int e = 2 + a * 6 - a * (a - 1) / 2 + (b - a);
+        acc[e] = fma(wJ[a], J[b], acc[e]);
+      }
+      acc[23 + a] = fma(wJ[a], rho, acc[23 + a]);
+    }
+  }
+
+  __device__ __forceinline__ void accumulate(double (&acc)[kSums], const double x[3], const double[3], const double u[3], double d2,
+                                             const float *__restrict__ tn, int id, int i) const {
+    acc[0] += 1.0;
+    acc[1] += d2;
+    {
+      const double n0 = tn[(size_t)id * 3 + 0], n1 = tn[(size_t)id * 3 + 1], n2 = tn[(size_t)id * 3 + 2];
+      term(acc, x, n0, n1, n2, fma(n0, u[0], fma(n1, u[1], n2 * u[2])), wg);
+    }
+    {
+      const double d0 = tg[(size_t)id * 3 + 0], d1 = tg[(size_t)id * 3 + 1], dz = tg[(size_t)id * 3 + 2];
+      const double di = (double)ti[id] - (double)si[i];
+      term(acc, x, d0, d1, dz, fma(d0, u[0], fma(d1, u[1], dz * u[2])) + di, wc);
+    }
+  }
+};
+
 // ---- the correspondence pass ----
 
 // grid (source blocks, inits); tn: the target's normals or covariances where Est::kNormals; sc: the source's covariances
-// in sp's order where Est::kCovariances
-template <class Est>
+// (Est::kCovariances) or intensities (Est::kColors) in sp's order; extra: what else the estimator's constructor takes
+template <class Est, class... Extra>
 __device__ __forceinline__ void icp_pass(const float4 *__restrict__ sp, const float *__restrict__ sc, int ns,
                                          const float4 *__restrict__ tq, const float *__restrict__ tgt, const float *__restrict__ tn,
                                          const uint32_t *__restrict__ cell_start, const IcpGrid *__restrict__ g,
                                          const double *__restrict__ T, const int32_t *__restrict__ active, double r2, float r2f,
-                                         double *__restrict__ rows) {
+                                         double *__restrict__ rows, const Extra &...extra) {
   const int j = blockIdx.y;
   if (!active[j]) return;
   const double *M = T + (size_t)j * 16;
@@ -301,7 +367,7 @@ __device__ __forceinline__ void icp_pass(const float4 *__restrict__ sp, const fl
   const double m10 = M[4], m11 = M[5], m12 = M[6], m13 = M[7] - g->ct[1];
   const double m20 = M[8], m21 = M[9], m22 = M[10], m23 = M[11] - g->ct[2];
   const double c0 = g->ct[0], c1 = g->ct[1], c2 = g->ct[2];
-  const Est est(g, M, sc);
+  const Est est(g, M, sc, extra...);
   double acc[Est::kSums];
 #pragma unroll
   for (int a = 0; a < Est::kSums; a++) acc[a] = 0.0;
@@ -362,6 +428,13 @@ __global__ void __launch_bounds__(kIcpThreads) icp_generalized_pass_kernel(
   icp_pass<Generalized>(sp, sc, ns, tq, tgt, tc, cell_start, g, T, active, r2, r2f, rows);
 }
 
+__global__ void __launch_bounds__(kIcpThreads) icp_colored_pass_kernel(
+    const float4 *__restrict__ sp, const float *__restrict__ si, int ns, const float4 *__restrict__ tq, const float *__restrict__ tgt,
+    const float *__restrict__ tn, const IcpColors colors, const uint32_t *__restrict__ cell_start, const IcpGrid *__restrict__ g,
+    const double *__restrict__ T, const int32_t *__restrict__ active, double r2, float r2f, double *__restrict__ rows) {
+  icp_pass<Colored>(sp, si, ns, tq, tgt, tn, cell_start, g, T, active, r2, r2f, rows, colors);
+}
+
 // the source's covariances [ns, 6] in the Morton order of W.sp
 __global__ void __launch_bounds__(256) icp_gather_covariances_kernel(const float *__restrict__ cov, const uint32_t *__restrict__ order,
                                                                      int ns, float *__restrict__ out) {
@@ -369,6 +442,13 @@ __global__ void __launch_bounds__(256) icp_gather_covariances_kernel(const float
   if (i >= ns) return;
   const float *c = cov + (size_t)order[i] * 6;
   for (int e = 0; e < 6; e++) out[(size_t)i * 6 + e] = c[e];
+}
+
+// the source's intensities [ns] in the Morton order of W.sp
+__global__ void __launch_bounds__(256) icp_gather_intensity_kernel(const float *__restrict__ intensity, const uint32_t *__restrict__ order,
+                                                                   int ns, float *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ns) out[i] = intensity[order[i]];
 }
 
 // ---- the solve ----
@@ -492,24 +572,93 @@ __global__ void __launch_bounds__(kNormalsThreads) icp_normals_kernel(const floa
   o[0] = (float)v0; o[1] = (float)v1; o[2] = (float)v2;
 }
 
+// ---- the colour gradients ----
+
+// One thread per point: the least-squares gradient of the intensity over the point's stored neighbours, in its tangent
+// plane (the rule is in include/scorp_gs.h).  The neighbour row is walked, not copied; an entry outside [0, n) is skipped.
+__global__ void __launch_bounds__(256) icp_color_gradients_kernel(const float *__restrict__ pts, const float *__restrict__ normals,
+                                                                  const float *__restrict__ intensity,
+                                                                  const int32_t *__restrict__ neighbors, int n, int knn,
+                                                                  float *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double p0 = pts[(size_t)i * 3 + 0], p1 = pts[(size_t)i * 3 + 1], p2 = pts[(size_t)i * 3 + 2], Ii = intensity[i];
+  double h0 = normals[(size_t)i * 3 + 0], h1 = normals[(size_t)i * 3 + 1], h2 = normals[(size_t)i * 3 + 2];
+  {
+    const double len = sqrt(h0 * h0 + h1 * h1 + h2 * h2);
+    if (len > 0.0 && isfinite(len)) { h0 /= len; h1 /= len; h2 /= len; } else { h0 = 0.0; h1 = 0.0; h2 = 0.0; }
+  }
+  double m00 = 0.0, m01 = 0.0, m02 = 0.0, m11 = 0.0, m12 = 0.0, m22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0, ee = 0.0;
+  int used = 0;
+  const int32_t *row = neighbors + (size_t)i * knn;
+  for (int a = 0; a < knn; a++) {
+    const int j = row[a];
+    if (j < 0 || j >= n || j == i) continue;
+    const double u0 = (double)pts[(size_t)j * 3 + 0] - p0, u1 = (double)pts[(size_t)j * 3 + 1] - p1,
+                 u2 = (double)pts[(size_t)j * 3 + 2] - p2;
+    const double un = fma(u0, h0, fma(u1, h1, u2 * h2));
+    const double e0 = u0 - un * h0, e1 = u1 - un * h1, e2 = u2 - un * h2;
+    const double delta = (double)intensity[j] - Ii;
+    m00 = fma(e0, e0, m00); m01 = fma(e0, e1, m01); m02 = fma(e0, e2, m02);
+    m11 = fma(e1, e1, m11); m12 = fma(e1, e2, m12); m22 = fma(e2, e2, m22);
+    g0 = fma(e0, delta, g0); g1 = fma(e1, delta, g1); g2 = fma(e2, delta, g2);
+    ee += fma(e0, e0, fma(e1, e1, e2 * e2));
+    used++;
+  }
+  float *o = out + (size_t)i * 3;
+  o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
+  if (used < 2) return;
+  const double M[3][3] = {{fma(ee * h0, h0, m00), fma(ee * h0, h1, m01), fma(ee * h0, h2, m02)},
+                          {fma(ee * h0, h1, m01), fma(ee * h1, h1, m11), fma(ee * h1, h2, m12)},
+                          {fma(ee * h0, h2, m02), fma(ee * h1, h2, m12), fma(ee * h2, h2, m22)}};
+  double U[3][3], V[3][3];
+  svd3(M, U, V);   // M symmetric and positive semi-definite: the columns of V are its eigenvectors
+  double l[3], lmax = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {   // l_k = v_k . M v_k
+    const double w0 = fma(M[0][0], V[0][k], fma(M[0][1], V[1][k], M[0][2] * V[2][k]));
+    const double w1 = fma(M[1][0], V[0][k], fma(M[1][1], V[1][k], M[1][2] * V[2][k]));
+    const double w2 = fma(M[2][0], V[0][k], fma(M[2][1], V[1][k], M[2][2] * V[2][k]));
+    l[k] = fma(V[0][k], w0, fma(V[1][k], w1, V[2][k] * w2));
+    lmax = fmax(lmax, l[k]);
+  }
+  if (!(lmax > 0.0)) return;
+  double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    if (!(l[k] > 1e-12 * lmax)) continue;
+    const double f = fma(V[0][k], g0, fma(V[1][k], g1, V[2][k] * g2)) / l[k];
+    d0 = fma(V[0][k], f, d0); d1 = fma(V[1][k], f, d1); d2 = fma(V[2][k], f, d2);
+  }
+  o[0] = (float)d0; o[1] = (float)d1; o[2] = (float)d2;
+}
+
 // ---- host ----
 
 // what a Generalized call needs after IcpLayout::total: the source's covariances in sorted order
 size_t icp_sorted_covariances_bytes(int64_t ns) { return align_up((size_t)(ns > 0 ? ns : 1) * 6 * 4, 256); }
+// and a Colored call: the source's intensities in sorted order
+size_t icp_sorted_intensity_bytes(int64_t ns) { return align_up((size_t)(ns > 0 ? ns : 1) * 4, 256); }
 
 // normals: the target's per-point attribute where Est::kNormals (normals, or covariances); source_covariances where
-// Est::kCovariances
+// Est::kCovariances, the source's intensities where Est::kColors; colors: the rest of what Colored reads
 template <class Est>
 int icp_run(const float *source, const float *source_covariances, int32_t ns, const float *target, const float *normals, int32_t nt,
             const double *inits, int32_t ni,
             double r, int32_t max_iteration, double rel_fitness, double rel_rmse, double *out_T, double *out_fitness,
-            double *out_rmse, int32_t *out_iters, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+            double *out_rmse, int32_t *out_iters, void *workspace, size_t workspace_bytes, hipStream_t stream,
+            const IcpColors &colors = IcpColors{nullptr, nullptr, 1.0}) {
   if (int e = icp_check_args(Est::kWho, r, ns, nt, max_iteration, ni,
-                             source && target && (normals || !Est::kNormals) && (source_covariances || !Est::kCovariances) && inits && out_T && out_fitness && out_rmse && out_iters))
+                             source && target && (normals || !Est::kNormals) && (source_covariances || !(Est::kCovariances || Est::kColors)) &&
+                                 ((colors.target_gradients && colors.target_intensity) || !Est::kColors) && inits && out_T && out_fitness && out_rmse && out_iters))
     return e;
+  if (Est::kColors && !(colors.lambda >= 0.0 && colors.lambda <= 1.0)) {
+    set_error("%s: lambda_geometric must be in [0, 1]", Est::kWho);
+    return SCORP_ERR_INVALID;
+  }
   const IcpLayout L(ns, nt, ni, Est::kRow);
   if (int e = check_workspace(Est::kWho, workspace, workspace_bytes,
-                              L.total + (Est::kCovariances ? icp_sorted_covariances_bytes(ns) : 0)))
+                              L.total + (Est::kCovariances ? icp_sorted_covariances_bytes(ns) : Est::kColors ? icp_sorted_intensity_bytes(ns) : 0)))
     return e;
   const IcpWorkspace W(workspace, L);
   if (int e = icp_build_target(target, nt, L, W, stream)) return e;
@@ -519,6 +668,10 @@ int icp_run(const float *source, const float *source_covariances, int32_t ns, co
   if constexpr (Est::kCovariances) {
     icp_gather_covariances_kernel<<<(ns + 255) / 256, 256, 0, stream>>>(source_covariances, order, ns, sc);
     SCORP_KERNEL_CHECK("icp_gather_covariances", 0, stream);
+  }
+  if constexpr (Est::kColors) {
+    icp_gather_intensity_kernel<<<(ns + 255) / 256, 256, 0, stream>>>(source_covariances, order, ns, sc);
+    SCORP_KERNEL_CHECK("icp_gather_intensity", 0, stream);
   }
   icp_init_kernel<<<(ni + 63) / 64, 64, 0, stream>>>(inits, ni, out_T, out_fitness, out_rmse, out_iters, W.active);
   SCORP_KERNEL_CHECK("icp_init", 0, stream);
@@ -531,6 +684,9 @@ int icp_run(const float *source, const float *source_covariances, int32_t ns, co
     if constexpr (Est::kCovariances)
       icp_generalized_pass_kernel<<<grid, kIcpThreads, 0, stream>>>(W.sp, sc, ns, W.tq, target, normals, W.cell_start, W.g, out_T,
                                                                     W.active, r2, r2f, W.rows);
+    else if constexpr (Est::kColors)
+      icp_colored_pass_kernel<<<grid, kIcpThreads, 0, stream>>>(W.sp, sc, ns, W.tq, target, normals, colors, W.cell_start, W.g, out_T,
+                                                                W.active, r2, r2f, W.rows);
     else if constexpr (Est::kNormals)
       icp_plane_pass_kernel<<<grid, kIcpThreads, 0, stream>>>(W.sp, ns, W.tq, target, normals, W.cell_start, W.g, out_T, W.active, r2,
                                                               r2f, W.rows);
@@ -558,6 +714,17 @@ int normals_impl(const float *points, int32_t n, int32_t knn, float *out_normals
   icp_normals_kernel<<<(n + kNormalsThreads - 1) / kNormalsThreads, kNormalsThreads, 0, stream>>>(
       W.tq, points, n, k, knn, W.cell_start, W.g, out_normals, out_neighbors);
   SCORP_KERNEL_CHECK("icp_normals", 0, stream);
+  return SCORP_OK;
+}
+
+int color_gradients_impl(const float *points, const float *normals, const float *intensity, const int32_t *neighbors, int32_t n,
+                         int32_t knn, float *out_gradients, hipStream_t stream) {
+  if (knn < 3 || knn > kNormalsMaxK) { set_error("color_gradients: knn must be in [3, %d]", kNormalsMaxK); return SCORP_ERR_INVALID; }
+  if (n <= 0) { set_error("color_gradients: empty cloud"); return SCORP_ERR_INVALID; }
+  if (n > (1 << 30)) { set_error("color_gradients: more than 2^30 points"); return SCORP_ERR_INVALID; }
+  if (!points || !normals || !intensity || !neighbors || !out_gradients) { set_error("color_gradients: NULL argument"); return SCORP_ERR_INVALID; }
+  icp_color_gradients_kernel<<<(n + 255) / 256, 256, 0, stream>>>(points, normals, intensity, neighbors, n, knn, out_gradients);
+  SCORP_KERNEL_CHECK("icp_color_gradients", 0, stream);
   return SCORP_OK;
 }
 
@@ -608,6 +775,27 @@ extern "C" int scorp_icp_generalized(const float *source, const float *source_co
   return icp_run<Generalized>(source, source_covariances, n_source, target, target_covariances, n_target, inits, n_init,
                               max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, out_transformation,
                               out_fitness, out_inlier_rmse, out_iterations, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t scorp_icp_colored_workspace_bytes(int32_t n_source, int32_t n_target, int32_t n_init) {
+  return IcpLayout(n_source, n_target, n_init, Colored::kRow).total + icp_sorted_intensity_bytes(n_source);
+}
+
+extern "C" int scorp_icp_colored(const float *source, const float *source_intensity, int32_t n_source, const float *target,
+                                 const float *target_normals, const float *target_intensity, const float *target_gradients,
+                                 int32_t n_target, const double *inits, int32_t n_init, double max_correspondence_distance,
+                                 int32_t max_iteration, double relative_fitness, double relative_rmse, double lambda_geometric,
+                                 double *out_transformation, double *out_fitness, double *out_inlier_rmse, int32_t *out_iterations,
+                                 void *workspace, size_t workspace_bytes, scorp_stream_t stream) {
+  return icp_run<Colored>(source, source_intensity, n_source, target, target_normals, n_target, inits, n_init,
+                          max_correspondence_distance, max_iteration, relative_fitness, relative_rmse, out_transformation, out_fitness,
+                          out_inlier_rmse, out_iterations, workspace, workspace_bytes, (hipStream_t)stream,
+                          IcpColors{target_gradients, target_intensity, lambda_geometric});
+}
+
+extern "C" int scorp_color_gradients(const float *points, const float *normals, const float *intensity, const int32_t *neighbors,
+                                     int32_t n, int32_t knn, float *out_gradients, scorp_stream_t stream) {
+  return color_gradients_impl(points, normals, intensity, neighbors, n, knn, out_gradients, (hipStream_t)stream);
 }
 
 extern "C" size_t scorp_estimate_normals_workspace_bytes(int32_t n) { return IcpLayout(0, n, 0, PointToPlane::kRow).total; }

@@ -339,12 +339,16 @@ def get_FPFH_fitting_transformation(pc_xyz_original, pc_xyz_refined, threshold, 
     as the sweep thins it.  The 5 x and 1.5 x ratios are the customary ones of Open3D's global-registration example; they
     are UNMEASURED on real objects.  With return_icp a tuple (transform, ICPResult of the one run).
     estimation="generalized" refines with generalized ICP on estimate_covariances of the two clouds that run registers.
+    estimation="colored" is refused: this function takes no colours (refine with registration_icp from the returned pose).
 
     orientation="tangent_plane": the normals are signed by orient_normals_consistent_tangent_plane over the first 12 columns
     of estimate_normals' own neighbour list instead, for objects that are not star-shaped (cups, shelves).  The default
     stays "away_from": no existing call changes its result."""
     if orientation not in ("away_from", "tangent_plane"):
         raise ValueError(f"unknown orientation {orientation!r}: expected 'away_from' or 'tangent_plane'")
+    if estimation == "colored":
+        raise ValueError("estimation='colored' needs colours, which this function does not take: refine its pose with "
+                         "registration_icp(..., estimation='colored', source_colors=, target_colors=)")
     threshold = _positive("threshold", threshold)
     orig, ref = np.asarray(pc_xyz_original), np.asarray(pc_xyz_refined)
     for name, a in (("pc_xyz_original", orig), ("pc_xyz_refined", ref)):

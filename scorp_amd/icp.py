@@ -1,4 +1,4 @@
-"""Multi-start ICP on the GPU, point-to-point, point-to-plane or generalized: the alignment scripts'
+"""Multi-start ICP on the GPU, point-to-point, point-to-plane, generalized or coloured: the alignment scripts'
 get_ICP_fitting_transformation_best (align_3dgs_clpe_9dof.py:42-115, align_2dgs_clpe_9dof.py:48-121) without Open3D.
 
 The reference runs Open3D's registration_icp (TransformationEstimationPointToPoint, no scaling, max_iteration=400) once
@@ -8,7 +8,10 @@ batch through scorp_icp_point_to_plane (the same file, the other estimator) on t
 model_normals(gaussians) for a trained model, estimate_normals(points) for a bare cloud.  estimation="generalized" runs
 it through scorp_icp_generalized on a covariance per point of both clouds (Segal et al. 2009; the estimator for two
 independent samplings of one surface): model_covariances(gaussians) for a trained model, estimate_covariances(points) for
-a bare cloud.  Swap it in with one import:
+a bare cloud.  estimation="colored" runs it through scorp_icp_colored (Park, Zhou, Koltun 2017; the estimator for surfaces
+that slide or spin at no geometric cost and carry a texture) on an intensity per point of both clouds and the target's
+normals and colour gradients: model_colors(gaussians) for a trained model, estimate_color_gradients(points, colors) for the
+gradients.  Swap it in with one import:
 
     from scorp_amd.icp import get_ICP_fitting_transformation_best
 """
@@ -30,7 +33,7 @@ class ICPResult:
     iterations: np.ndarray
 
 
-ESTIMATIONS = ("point_to_point", "point_to_plane", "generalized")
+ESTIMATIONS = ("point_to_point", "point_to_plane", "generalized", "colored")
 
 
 def _check_estimation(estimation):
@@ -117,6 +120,69 @@ def model_covariances(gaussians, mode="plane", epsilon=1e-3):
         return (0.5 * (C[:, ia, ib] + C[:, ib, ia])).to(torch.float32).contiguous()
 
 
+def intensities(colors):
+    """The intensity [n] fp32 (a device tensor) of colours [n, 3] (the mean of the channels) or [n] (passed through),
+    numpy or torch."""
+    t = colors if isinstance(colors, torch.Tensor) else torch.as_tensor(np.array(colors))
+    if not (t.ndim == 1 or (t.ndim == 2 and t.shape[1] == 3)):
+        raise ValueError(f"colors must be [n, 3] or [n]; got {tuple(t.shape)}")
+    _check_finite("colors", t)
+    dev = t.device if t.is_cuda else _device(t)
+    if t.ndim == 2:
+        t = t.to(torch.float64).mean(dim=1)
+    return t.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _intensity(name, a, n, device):
+    """A colour argument, [n, 3] or [n] (numpy or torch), as the intensity [n] fp32 on the device."""
+    shape = tuple(np.shape(a))
+    if shape not in ((n, 3), (n,)):
+        raise ValueError(f"{name} must be [{n}, 3] or [{n}]; got {shape}")
+    try:
+        return intensities(a).to(device)
+    except ValueError as e:
+        raise ValueError(str(e).replace("colors", name, 1)) from None
+
+
+def color_gradients(points, normals, intensity, neighbors):
+    """scorp_color_gradients on device tensors: gradients [n, 3] fp32 of the intensity [n] over the stored neighbour lists
+    [n, knn] int32 (estimate_normals' layout), in the tangent planes of `normals`."""
+    n, knn = neighbors.shape
+    if tuple(points.shape) != (n, 3) or tuple(normals.shape) != (n, 3) or tuple(intensity.shape) != (n,):
+        raise ValueError(f"points and normals must be [{n}, 3] and intensity [{n}]; got {tuple(points.shape)}, "
+                         f"{tuple(normals.shape)}, {tuple(intensity.shape)}")
+    if bool((neighbors >= n).any()):
+        raise ValueError(f"neighbors holds an index >= {n}")
+    out = torch.empty(n, 3, dtype=torch.float32, device=points.device)
+    with torch.cuda.device(points.device):
+        _C.call("scorp_color_gradients", points, normals, intensity, neighbors, n, knn, out)
+    return out
+
+
+def estimate_color_gradients(points, colors, normals=None, knn=30):
+    """Colour gradients [n, 3] fp32 (a device tensor) of a cloud, for target_gradients: per point the least-squares gradient
+    of intensities(colors) over the neighbour list of estimate_normals(points, knn, return_neighbors=True), kept in the
+    tangent plane of its normal (scorp_color_gradients; the rule is in include/scorp_gs.h).  normals [n, 3]: the cloud's
+    own, when it brings them; None takes the estimated ones."""
+    est, nb = estimate_normals(points, knn=knn, return_neighbors=True)
+    dev = est.device
+    P = _points("points", points, dev)
+    if normals is not None:
+        if tuple(np.shape(normals)) != tuple(P.shape):
+            raise ValueError(f"normals must have the points' shape {tuple(P.shape)}; got {tuple(np.shape(normals))}")
+        _check_finite("normals", normals)
+        est = _points("normals", normals, dev)
+    return color_gradients(P, est, _intensity("colors", colors, P.shape[0], dev), nb)
+
+
+def model_colors(gaussians):
+    """Per-Gaussian colours [N, 3] of a trained model (either kind), for source_colors / target_colors: the view-independent
+    part of its spherical harmonics, clamp(0.5 + C0 * _features_dc[:, 0, :], 0, 1).  Plain torch, once per object."""
+    from .sh import C0
+    with torch.no_grad():
+        return (0.5 + C0 * gaussians._features_dc[:, 0, :]).clamp(0.0, 1.0).contiguous()
+
+
 def _covariances(name, a, n, device):
     """A covariance argument, [n, 6] or [n, 3, 3] (numpy or torch), as [n, 6] fp32 on the device."""
     t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.array(a))
@@ -135,7 +201,8 @@ def _covariances(name, a, n, device):
 
 def registration_icp(source, target, max_correspondence_distance, inits, max_iteration=30, relative_fitness=1e-6,
                      relative_rmse=1e-6, estimation="point_to_point", target_normals=None, source_covariances=None,
-                     target_covariances=None):
+                     target_covariances=None, source_colors=None, target_colors=None, target_gradients=None,
+                     lambda_geometric=0.968):
     """Open3D's registration_icp(source, target, r, init, TransformationEstimationPointToPoint(),
     ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration)) from every init of `inits` ([4, 4] or
     [n_init, 4, 4]) at once.  source [n, 3] and target [m, 3]: numpy arrays or torch tensors (searched in fp32; pair
@@ -143,6 +210,10 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     (no robust kernel) on target_normals [m, 3]; without them the normals are estimate_normals(target, knn=30).
     estimation="generalized" is generalized ICP (the rules of include/scorp_gs.h) on source_covariances and
     target_covariances, each [n, 6] (xx, xy, xz, yy, yz, zz) or [n, 3, 3]; one left out is estimate_covariances(cloud).
+    estimation="colored" is coloured ICP (the rules of include/scorp_gs.h) on source_colors and target_colors ([n, 3] or
+    intensities [n]; both required), target_normals and target_gradients [m, 3], weighing the geometric term by
+    lambda_geometric and the colour term by 1 - lambda_geometric; normals left out are estimate_normals(target, knn=30),
+    gradients left out estimate_color_gradients(target, target_colors, those normals).
     Returns an ICPResult of numpy arrays."""
     _check_estimation(estimation)
     r = float(max_correspondence_distance)
@@ -154,7 +225,19 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     _check_finite("target", target)
     plane = estimation == "point_to_plane"
     gicp = estimation == "generalized"
-    if plane and target_normals is not None:
+    colored = estimation == "colored"
+    if colored:
+        if source_colors is None or target_colors is None:
+            raise ValueError("estimation='colored' needs source_colors and target_colors")
+        lam = float(lambda_geometric)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lambda_geometric must be in [0, 1]; got {lambda_geometric}")
+        if target_gradients is not None:
+            if tuple(np.shape(target_gradients)) != tuple(np.shape(target)):
+                raise ValueError(f"target_gradients must have the target's shape {tuple(np.shape(target))}; "
+                                 f"got {tuple(np.shape(target_gradients))}")
+            _check_finite("target_gradients", target_gradients)
+    if (plane or colored) and target_normals is not None:
         if tuple(np.shape(target_normals)) != tuple(np.shape(target)):
             raise ValueError(f"target_normals must have the target's shape {tuple(np.shape(target))}; "
                              f"got {tuple(np.shape(target_normals))}")
@@ -171,6 +254,20 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     ni = T0.shape[0]
     if plane:
         Nq = estimate_normals(Q, knn=30) if target_normals is None else _points("target_normals", target_normals, dev)
+    if colored:
+        Ip = _intensity("source_colors", source_colors, P.shape[0], dev)
+        Iq = _intensity("target_colors", target_colors, Q.shape[0], dev)
+        nb = None
+        if target_normals is None:
+            Nq, nb = estimate_normals(Q, knn=30, return_neighbors=True)
+        else:
+            Nq = _points("target_normals", target_normals, dev)
+        if target_gradients is None:
+            if nb is None:
+                nb = estimate_normals(Q, knn=30, return_neighbors=True)[1]
+            Gq = color_gradients(Q, Nq, Iq, nb)
+        else:
+            Gq = _points("target_gradients", target_gradients, dev)
     if gicp:
         Cp = (estimate_covariances(P) if source_covariances is None
               else _covariances("source_covariances", source_covariances, P.shape[0], dev))
@@ -181,6 +278,11 @@ def registration_icp(source, target, max_correspondence_distance, inits, max_ite
     fit = torch.empty(ni, dtype=torch.float64, device=dev)
     rmse = torch.empty(ni, dtype=torch.float64, device=dev)
     iters = torch.empty(ni, dtype=torch.int32, device=dev)
+    if colored:
+        _C.call_with_workspace("scorp_icp_colored", "scorp_icp_colored_workspace_bytes", (P.shape[0], Q.shape[0], ni),
+                               P, Ip, P.shape[0], Q, Nq, Iq, Gq, Q.shape[0], T_in, ni, r, int(max_iteration),
+                               float(relative_fitness), float(relative_rmse), lam, T_out, fit, rmse, iters)
+        return ICPResult(T_out.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), iters.cpu().numpy())
     name, size_name = (("scorp_icp_generalized", "scorp_icp_generalized_workspace_bytes") if gicp
                        else ("scorp_icp_point_to_plane", "scorp_icp_point_to_plane_workspace_bytes") if plane
                        else ("scorp_icp_point_to_point", "scorp_icp_workspace_bytes"))
@@ -214,14 +316,19 @@ def icp_inits(rotations, center_original, center_refined):
 
 def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refined: np.ndarray, rotations: np.ndarray,
                                         threshold: float, *, estimation="point_to_point", target_normals=None,
-                                        max_iteration=400, source_covariances=None, target_covariances=None) -> np.ndarray:
+                                        max_iteration=400, source_covariances=None, target_covariances=None,
+                                        source_colors=None, target_colors=None, target_gradients=None,
+                                        lambda_geometric=0.968) -> np.ndarray:
     """The reference's function of the same name, statement for statement, with every ICP run on the GPU in one batch:
     the 4x4 float64 transform (refined -> original) of the FIRST init with the highest fitness.  The keyword-only
     arguments are this project's: estimation="point_to_plane" with target_normals [len(pc_xyz_original), 3] (a surfel
     model's come from model_normals; None estimates them from the cloud) normally needs far fewer updates;
     estimation="generalized" with source_covariances for pc_xyz_refined (subsampled here with its points) and
     target_covariances for pc_xyz_original (a trained model's come from model_covariances; None estimates them from the
-    cloud that is registered) weighs every pair by both."""
+    cloud that is registered) weighs every pair by both; estimation="colored" with source_colors for pc_xyz_refined
+    (subsampled here with its points), target_colors for pc_xyz_original (a trained model's come from model_colors) and
+    optionally target_gradients (None: estimate_color_gradients of the cloud that is registered) adds the colour term of
+    coloured ICP at the weight 1 - lambda_geometric."""
     _check_estimation(estimation)
     if np.any(np.isnan(pc_xyz_original)) or np.any(np.isnan(pc_xyz_refined)):
         raise ValueError("Point clouds contain NaN values")
@@ -238,9 +345,15 @@ def get_ICP_fitting_transformation_best(pc_xyz_original: np.ndarray, pc_xyz_refi
             raise ValueError(f"source_covariances must have one entry per point of pc_xyz_refined ({len(ref)}); "
                              f"got {len(source_covariances)}")
         source_covariances = source_covariances[keep]
+    if estimation == "colored" and source_colors is not None:
+        if len(source_colors) != len(ref):
+            raise ValueError(f"source_colors must have one entry per point of pc_xyz_refined ({len(ref)}); "
+                             f"got {len(source_colors)}")
+        source_colors = source_colors[keep]
     inits = icp_inits(rotations, center_original, center_refined)
     res = registration_icp(src, orig, threshold, inits, max_iteration=max_iteration, estimation=estimation,
                            target_normals=target_normals, source_covariances=source_covariances,
-                           target_covariances=target_covariances)
+                           target_covariances=target_covariances, source_colors=source_colors, target_colors=target_colors,
+                           target_gradients=target_gradients, lambda_geometric=lambda_geometric)
     best = int(np.argmax(res.fitness))   # the first maximum: the reference keeps a pose only on a strictly higher fitness
     return res.transformation[best].copy()

@@ -5,7 +5,7 @@ library and compared with another's in dtype, shape and bytes (profiles/icp_unif
     SCORP_GS_LIB=<library B> python scripts/dev/icp_unify_dump.py dump b.npz
     python scripts/dev/icp_unify_dump.py compare a.npz b.npz out.json
 
-Cases: both estimators on the aggregate fixtures at every AGGREGATE_NS (max_iteration 0 and 1), the two margin fixtures
+Cases: every estimator on the aggregate fixtures at every AGGREGATE_NS (max_iteration 0 and 1), the two margin fixtures
 at max_iteration 0, 1 and 5, the realistic fixture, the four rank-deficient systems, the no-pair and zero-normal cases and
 a 3-init batch next to each init alone; estimate_normals with its neighbours on every NORMALS fixture; the mesh-distance
 query and nearest_point_distance on every mesh fixture and on the block-edge query counts."""
@@ -24,6 +24,7 @@ def dump(path):
     import torch
     from scorp_amd import icp
     from scorp_amd.mesh import nearest_point_distance, point_mesh_distance
+    from tests import icp_color_fixtures as cfx
     from tests import icp_plane_fixtures as pfx
     from tests import icp_probe_fixtures as fx
     from tests import icp_reference as ref
@@ -35,8 +36,10 @@ def dump(path):
 
     def both(case, src, tgt, nrm, r, inits, **kw):
         for est in icp.ESTIMATIONS:
+            # the coloured estimator's colours: a smooth texture of position, the source's taken where it lies
+            colors = {"source_colors": cfx.smooth_texture(src), "target_colors": cfx.smooth_texture(tgt)} if est == "colored" else {}
             res = icp.registration_icp(np.array(src), np.array(tgt), r, inits, estimation=est,
-                                       target_normals=None if nrm is None or est == "point_to_point" else np.array(nrm), **kw)
+                                       target_normals=None if nrm is None or est == "point_to_point" else np.array(nrm), **colors, **kw)
             for f in FIELDS:
                 out[f"icp/{case}/{est}/{f}"] = getattr(res, f)
 
@@ -89,16 +92,22 @@ def dump(path):
 def compare(a_path, b_path, out_path):
     a, b = np.load(a_path), np.load(b_path)
     cases = {}
+    # an estimator that only one of the two libraries has (a new one) is named and left out; everything else must match
+    ests = [{k.split("/")[2] for k in f.files if k.startswith("icp/")} for f in (a, b)]
+    lone = sorted(ests[0] ^ ests[1])
     for k in sorted((set(a.files) | set(b.files)) - {"library_source_sha"}):
+        if k.startswith("icp/") and k.split("/")[2] in lone:
+            continue
         c = cases.setdefault(k.rsplit("/", 1)[0], {"tensors": 0, "bytes": 0, "different": []})
         c["tensors"] += 1
         same = k in a.files and k in b.files and a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes()
         c["bytes"] += a[k].nbytes if k in a.files else 0
         if not same:
             c["different"].append(k.rsplit("/", 1)[1])
-    res = {"what": "ICP (both estimators), estimate_normals, mesh-distance query and nearest_point_distance on the test fixtures, parent "
+    res = {"what": "ICP (every estimator both libraries have), estimate_normals, mesh-distance query and nearest_point_distance on the test fixtures, parent "
                    "commit's library against this tree's, one fresh process each; every output compared in dtype, shape and bytes",
-           "library_source_sha": [str(a["library_source_sha"]), str(b["library_source_sha"])], "cases": len(cases), "tensors": sum(c["tensors"] for c in cases.values()),
+           "library_source_sha": [str(a["library_source_sha"]), str(b["library_source_sha"])], "estimators_compared": sorted(ests[0] & ests[1]),
+           "estimators_in_one_library_only": lone, "cases": len(cases), "tensors": sum(c["tensors"] for c in cases.values()),
            "tensors_different": sum(len(c["different"]) for c in cases.values()),
            "per_case": [dict(case=k, **c) for k, c in cases.items()]}
     with open(out_path, "w") as f:
