@@ -1216,6 +1216,17 @@ int scorp_gs3d_debug_work(const void *state, int32_t num_gaussians, int32_t imag
 int scorp_gs3d_debug_tiles(const void *state, const void *pairs, uint64_t capacity, int32_t num_gaussians,
                            int32_t image_width, int32_t image_height, uint32_t *tile_start, uint32_t *point_list,
                            scorp_stream_t stream);
+/* What the last scorp_gs3d_render (after scorp_gs3d_preprocess) left on this state and pair buffer for the backward:
+ * final_T[H*W] (float), n_contrib[H*W] (uint32: per pixel the 1-based position of its last contributor in its 8x8 block's
+ * hit list, 0 = none), block_hits[tiles*4] (uint32: hits the block's wave blended; block = tile * 4 + quad, quad = 2 * (lower
+ * half) + (right half)) and the four hit-list regions in RASTER tile order like point_list above: with num_pairs =
+ * tile_start[tiles] of scorp_gs3d_debug_tiles, entry k of block (t, quad) is out_hits[quad * num_pairs + tile_start[t] + k],
+ * out_hits[4 * num_pairs] (uint32 splat ids).  A block's entries are defined up to the largest n_contrib of its pixels (what
+ * the backward replays) and undefined beyond.  Any output may be NULL.  Read-only: launches nothing, changes nothing on
+ * the device. */
+int scorp_gs3d_debug_blend(const void *state, const void *pairs, uint64_t capacity, int32_t num_gaussians,
+                           int32_t image_width, int32_t image_height, float *final_T, uint32_t *n_contrib,
+                           uint32_t *block_hits, uint32_t *out_hits, scorp_stream_t stream);
 
 /* ---- 2D Gaussian splatting (surfels): replaces diff_surfel_rasterization (gs2dgs/gaussian_renderer/__init__.py:111-120) ----
  * Same ScorpGs3dInputs / ScorpGs3dGrads structs with two reinterpretations: `scales` is [N,2]

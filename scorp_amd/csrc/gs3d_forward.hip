@@ -453,3 +453,43 @@ extern "C" int scorp_gs3d_debug_tiles(const void *state, const void *pairs, uint
                                       int32_t H, uint32_t *tile_start, uint32_t *point_list, scorp_stream_t stream) {
   return debug_tiles(false, state, pairs, capacity, N, W, H, tile_start, point_list, (hipStream_t)stream);
 }
+
+// What the blend forward left behind for the backward and the vote, copied out as it stands (no kernel, nothing written on
+// the device): the hit lists re-addressed from the pair buffer's order into the raster tile order of debug_tiles.
+extern "C" int scorp_gs3d_debug_blend(const void *state, const void *pairs, uint64_t capacity, int32_t N, int32_t W, int32_t H,
+                                      float *final_T, uint32_t *n_contrib, uint32_t *block_hits, uint32_t *out_hits,
+                                      scorp_stream_t stream_) {
+  if (W <= 0 || H <= 0 || N < 0) { set_error("scorp_gs3d_debug_blend: N (%d) negative or W x H (%d x %d) empty", N, W, H); return SCORP_ERR_INVALID; }
+  if (int e = check_buffers(state, pairs, capacity)) return e;
+  hipStream_t stream = (hipStream_t)stream_;
+  const StateLayout L(N, W, H);
+  const PairLayout P(capacity);
+  StateHeader h;
+  if (int e = read_header(state, stream, &h)) return e;
+  const size_t n = h.num_pairs < capacity ? h.num_pairs : (size_t)capacity, hw = (size_t)W * H, nb = (size_t)L.tiles * 4;
+  const bool lists = out_hits && n > 0;
+  uint32_t *range = lists ? (uint32_t *)malloc((size_t)L.tiles * 8) : nullptr, *raw = lists ? (uint32_t *)malloc(n * 16) : nullptr;
+  if (lists && (!range || !raw)) { free(range); free(raw); set_error("host allocation failed"); return SCORP_ERR_INVALID; }
+  const char *sb = (const char *)state, *pb = (const char *)pairs;
+  hipError_t e = hipSuccess;
+  if (final_T) e = hipMemcpyAsync(final_T, sb + L.final_T, hw * 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && n_contrib) e = hipMemcpyAsync(n_contrib, sb + L.n_contrib, hw * 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && block_hits) e = hipMemcpyAsync(block_hits, sb + L.block_hits, nb * 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && lists) e = hipMemcpyAsync(range, sb + L.tile_start, (size_t)L.tiles * 8, hipMemcpyDeviceToHost, stream);
+  for (int q = 0; q < 4 && e == hipSuccess && lists; q++)   // hits[quad][capacity]: the first n entries of each region
+    e = hipMemcpyAsync(raw + (size_t)q * n, pb + P.hits + (size_t)q * capacity * 4, n * 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) { free(range); free(raw); set_error("debug_blend copy failed: %s", hipGetErrorString(e)); return SCORP_ERR_HIP; }
+  if (lists) {
+    size_t run = 0;
+    for (int t = 0; t < L.tiles; t++) {   // (the ranges clamped as debug_tiles clamps them: the same tile_start)
+      const size_t b = range[2 * t] < n ? range[2 * t] : n, en = range[2 * t + 1] < n ? range[2 * t + 1] : n;
+      if (en > b) {
+        for (int q = 0; q < 4; q++) memcpy(out_hits + (size_t)q * n + run, raw + (size_t)q * n + b, (en - b) * 4);
+        run += en - b;
+      }
+    }
+  }
+  free(range); free(raw);
+  return SCORP_OK;
+}
